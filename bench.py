@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — distill-step throughput on N x MI355X (BASELINE.json metric: image-text pairs/sec of one full distill step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lclip|image|text|lclip336]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lclip|image|text|lclip336] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes (one per GPU, RCCL over
 xGMI) BEFORE it touches the GPU itself, relays rank 0's JSON line and exits non-zero if any rank fails.  Under
@@ -15,7 +15,10 @@ data-parallel exchange (N > 1: bucketed reduce-scatter under the backward -> sha
 optimizer step, on synthetic inputs already resident in HBM.  Weak scaling: per-GPU batch fixed, local negatives like the
 reference's training_step.  `--config` selects the other BASELINE configurations (image.yaml B=256,
 text.yaml B=1024, l_clip at 336 px B=512), each with its own unit and FLOP count.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` (rank 0) also writes what the last timed step handed its caller as
+DIR/<name>.npy (float32): `loss`, the logged loss terms `term.<name>` and the updated student weights `student.<name>`, each
+sampled at fixed positions when larger than its share of a 48 MiB budget (see dump_outputs), so that two builds can be compared
+output for output on identical seeded inputs.
 """
 import argparse
 import json
@@ -26,8 +29,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-# one hardware queue per tower stream (+ main + RCCL): read at HIP initialisation, see distillclip_amd/__init__.py
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 
 PEAK_BF16_TFLOPS = 2500.0        # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
@@ -101,6 +102,26 @@ def make_inputs(wl, seed, B):
     caps = synth.captions(seed, B) if wl['kind'] != 'image' else None
     text = torch.from_numpy(caps) if caps is not None else None
     return image, text, caps
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20      # --dump-outputs: all arrays together, well inside 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  Every array gets an equal share of the budget; an array larger than
+    its share is written as a 1-D sample of its flattened elements at sorted positions drawn by a generator seeded with the name,
+    so every run (and every build) samples the same positions."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = budget_bytes // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
 
 
 def log(msg):
@@ -339,7 +360,7 @@ def dry_launch():
     dist.all_reduce(t)
     if rank == 0:
         print(json.dumps({'dry_launch': True, 'n_gpus': dist.get_world_size(), 'ranks_seen': int(t.item()), 'backend': 'gloo'}), flush=True)
-    dist.barrier()
+    dist.monitored_barrier()                # (dist.barrier() would query, and so open, the GPU from every CPU rank)
     if os.environ.get('DCLIP_DRY_HANG_RANK') in (str(rank), 'all'):
         time.sleep(3600)
     dist.destroy_process_group()
@@ -364,7 +385,11 @@ def main():
     ap.add_argument('--teacher-text-prefix', action='store_true',
                     help='opt-in: run the causal text teacher only on the prefix that contains every EOT (identical output, '
                          'less work; NOT used for the headline number, which processes all 77 positions)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write the last step\'s loss, loss terms and updated student weights as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # nothing above touched the GPU (torch is not even imported)
@@ -484,6 +509,14 @@ def main():
         dt = t.item()
     final_loss = loss.item()
     log(f'{args.steps} steps in {dt:.3f} s (host enqueue {t_issue:.3f} s); loss {final_loss:.5f}')
+    if args.dump_outputs and rank == 0:
+        # before the roofline probe below runs further steps; join() orders this stream after the towers' deferred updates
+        opt.join()
+        outs = {'loss': loss}
+        outs.update({f'term.{k}': v for k, v in model.last_cal_res.items()})
+        outs.update({f'student.{k}': v for k, v in model.student.state_dict().items()})
+        dump_outputs(args.dump_outputs, outs)
+        log(f'{len(outs)} outputs of the last timed step written to {args.dump_outputs}')
 
     roofline = None
     if not args.no_roofline:

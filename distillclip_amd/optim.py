@@ -191,7 +191,9 @@ class FusedAdamW:
         (zero_grad() and state_dict() call it)."""
         from .model.component._tower import autograd_params_mode
         self.step_count += 1
-        main = torch.cuda.current_stream() if torch.cuda.is_available() else None
+        # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
+        on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
+        main = torch.cuda.current_stream() if on_gpu else None
         joined = []
         for tw in self.towers:
             if tw.flat is None:
@@ -259,14 +261,13 @@ class FusedAdamW:
 
     def join(self):
         """order the current stream after every tower's pending (un-joined) update"""
-        if not torch.cuda.is_available():
+        pending = [tw for tw in self.towers if getattr(tw, 'opt_done', None) is not None]
+        if not pending:
             return
         cur = torch.cuda.current_stream()
-        for tw in self.towers:
-            ev = getattr(tw, 'opt_done', None)
-            if ev is not None:
-                cur.wait_event(ev)
-                tw.opt_done = None
+        for tw in pending:
+            cur.wait_event(tw.opt_done)
+            tw.opt_done = None
 
     def _full_moments(self, tw):
         """(m, v) in the flat layout of the tower; collective in a sharded data-parallel run (all-gather of the ranks' shards)"""

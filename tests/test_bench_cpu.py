@@ -26,3 +26,35 @@ def test_every_workload_names_a_pinned_yaml():
     for name, wl in bench.WORKLOADS.items():
         assert wl['yaml'] in bench.YAML_ARGS, name
         assert wl['kind'] in ('dual', 'image', 'text')
+
+
+def test_dump_outputs_stays_in_budget_and_samples_fixed_positions(tmp_path):
+    """--dump-outputs: float32 files, the whole dump within the budget, small arrays whole, large ones sampled at the same sorted
+    positions on every call."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {'loss': torch.tensor(0.5), 'term.out_l1': torch.tensor(0.25, dtype=torch.float64),
+              'student.small': torch.randn(3, 5, generator=g), 'student.big': torch.arange(10 ** 6, dtype=torch.float32).view(1000, 1000)}
+    budget = 2 ** 20
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget_bytes=budget)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(n + '.npy' for n in arrays)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= budget + 128 * len(files)      # + .npy headers
+    for n, t in arrays.items():
+        a, b = np.load(tmp_path / 'a' / (n + '.npy')), np.load(tmp_path / 'b' / (n + '.npy'))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        if n != 'student.big':
+            assert a.shape == tuple(t.shape) and np.array_equal(a, t.float().numpy()), n
+    big = np.load(tmp_path / 'a' / 'student.big.npy')
+    assert big.ndim == 1 and 0 < big.size < 10 ** 6
+    assert np.all(np.diff(big) > 0)                 # every element is its own position: distinct positions, in index order
+
+
+def test_steps_below_one_is_refused():
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and '--steps' in r.stderr

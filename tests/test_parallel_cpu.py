@@ -84,7 +84,7 @@ def _worker(rank, world, rdzv, q):
     sync.launch(h)
     sync.wait()
     q.put((rank, g.clone(), h.clone()))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -103,7 +103,7 @@ def _gather_worker(rank, world, rdzv, q):
     b = torch.full((3, 2), 10.0 * rank)
     (ga, gb), r, w = gather_embeddings([a, b])
     q.put((rank, r, w, ga.clone(), gb.clone()))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -135,10 +135,11 @@ def test_global_negative_gradient_identity():
 def _global_rows_worker(rank, world, rdzv, q):
     """global-negative mode as the model runs it (dual_distill_model.py here, SURVEY.md 8e Collective 2): ONE fused all-gather of the four
     [B, E] embeddings, every rank evaluates the loss of ITS ROW BLOCK against all world * B columns — here with the oracle standing in for
-    dclip_distill_loss_rows, which needs the GPU — and hands back W x (gradient rows of its own samples)"""
+    dclip_distill_loss_rows, which needs the GPU — and hands back W x (gradient rows of its own samples).  The rank hands back what it
+    gathered and the parent evaluates that rank's loss on it: an autograd backward inside the rank would open the GPU (the engine
+    counts the devices on its first backward) from all 8 rank processes of a GPU machine."""
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group('gloo', init_method='file://' + rdzv, rank=rank, world_size=world)
-    import oracle
     from distillclip_amd.parallel import gather_embeddings, check_equal_batch
     B, E = 3, 32
     g = torch.Generator().manual_seed(7)
@@ -147,13 +148,8 @@ def _global_rows_worker(rank, world, rdzv, q):
     check_equal_batch(B, torch.device('cpu'))
     (gsi, gst, gti, gtt), r, w = gather_embeddings([mine['si'], mine['st'], mine['ti'], mine['tt']])
     assert (r, w) == (rank, world) and all(torch.equal(a, full[k]) for a, k in ((gsi, 'si'), (gst, 'st'), (gti, 'ti'), (gtt, 'tt')))
-    si, st = gsi.clone().requires_grad_(True), gst.clone().requires_grad_(True)
-    lc = oracle.LossOracle(['out_l1', 'out_cos', 'cos_diff', 'hard_label'], {'cos_diff': 0.1})
-    loss, _ = lc(oracle.clip_forward({'last_representation': si}, {'last_representation': st}),
-                 oracle.clip_forward({'last_representation': gti}, {'last_representation': gtt}), 'all')
-    loss.backward()
-    q.put((rank, float(loss), world * si.grad[rank * B:(rank + 1) * B].clone(), world * st.grad[rank * B:(rank + 1) * B].clone()))
-    dist.barrier()
+    q.put((rank, gsi, gst, gti, gtt))
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -162,19 +158,28 @@ def test_global_negative_row_blocks_at_world_8_equal_one_process_on_the_concaten
     is the single-process gradient on the concatenated batch, the gathered rows arrive in rank-major order on all 8 ranks"""
     import oracle
     world, B, E = 8, 3, 32
-    res = sorted(_run_ranks(_global_rows_worker, world, timeout=240), key=lambda r: r[0])
+    gathered = sorted(_run_ranks(_global_rows_worker, world, timeout=240), key=lambda r: r[0])
+    lc = oracle.LossOracle(['out_l1', 'out_cos', 'cos_diff', 'hard_label'], {'cos_diff': 0.1})
+
+    def loss_and_grads(si, st, ti, tt):
+        si, st = si.clone().requires_grad_(True), st.clone().requires_grad_(True)
+        loss, _ = lc(oracle.clip_forward({'last_representation': si}, {'last_representation': st}),
+                     oracle.clip_forward({'last_representation': ti}, {'last_representation': tt}), 'all')
+        loss.backward()
+        return loss, si.grad, st.grad
+
+    res = []
+    for rank, gsi, gst, gti, gtt in gathered:       # each rank's loss on what that rank gathered -> W x (its own gradient rows)
+        l, gsi_grad, gst_grad = loss_and_grads(gsi, gst, gti, gtt)
+        res.append((rank, l.item(), world * gsi_grad[rank * B:(rank + 1) * B], world * gst_grad[rank * B:(rank + 1) * B]))
     g = torch.Generator().manual_seed(7)
     full = {k: torch.randn(world * B, E, generator=g) for k in ('si', 'st', 'ti', 'tt')}
-    si, st = full['si'].clone().requires_grad_(True), full['st'].clone().requires_grad_(True)
-    lc = oracle.LossOracle(['out_l1', 'out_cos', 'cos_diff', 'hard_label'], {'cos_diff': 0.1})
-    loss, _ = lc(oracle.clip_forward({'last_representation': si}, {'last_representation': st}),
-                 oracle.clip_forward({'last_representation': full['ti']}, {'last_representation': full['tt']}), 'all')
-    loss.backward()
+    loss, si_grad, st_grad = loss_and_grads(full['si'], full['st'], full['ti'], full['tt'])
     for rank, l, gi, gt in res:
         assert abs(l - loss.item()) <= 1e-6 * abs(loss.item())
         # what the tower's backward receives on rank r, divided by W by the DP average, is that rank's rows of the global gradient
-        assert torch.allclose(gi / world, si.grad[rank * B:(rank + 1) * B], rtol=1e-6, atol=1e-8)
-        assert torch.allclose(gt / world, st.grad[rank * B:(rank + 1) * B], rtol=1e-6, atol=1e-8)
+        assert torch.allclose(gi / world, si_grad[rank * B:(rank + 1) * B], rtol=1e-6, atol=1e-8)
+        assert torch.allclose(gt / world, st_grad[rank * B:(rank + 1) * B], rtol=1e-6, atol=1e-8)
 
 
 def test_grad_sync_is_a_noop_without_process_group():
@@ -216,7 +221,7 @@ def _gather_rows_worker(rank, world, rdzv, q):
     from distillclip_amd.metrics import gather_rows
     x = torch.arange(6, dtype=torch.float32).reshape(3, 2) + 100 * rank
     q.put((rank, gather_rows(x).clone()))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -332,7 +337,7 @@ def _sharded_worker(rank, world, rdzv, q):
         resized = str(e)
     assert 'optimizer state of' in resized, resized
     q.put(result)
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -408,7 +413,7 @@ def _extras_worker(rank, world, rdzv, q):
     opt2.load_state_dict(sd)
     same = all(torch.equal(opt2._extra_state[id(p)][k], opt._extra_state[id(p)][k]) for p in extras[:2] for k in (0, 1))
     q.put((rank, [p.detach().clone() for p in extras], len(sd['param_groups'][0]['params']), same))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -466,7 +471,7 @@ def _sparse_worker(rank, world, rdzv, q):
             out['rows'] = tw.sparse_rows_last
             out['ids'] = ids
     q.put((rank, out))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -560,7 +565,7 @@ def _sparse_edge_worker(rank, world, rdzv, q):
                 big = str(e)
             assert 'sized for 12' in big, big
     q.put((rank, out))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -718,7 +723,7 @@ def _ragged_worker(rank, world, rdzv, q):
         q.put((rank, 'no error'))
     except ValueError as e:
         q.put((rank, str(e)))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

@@ -4,7 +4,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/../.."
-export GPU_MAX_HW_QUEUES=8 DCLIP_MULTI_STREAM=0
+export DCLIP_MULTI_STREAM=0
 for v in "" "--hidden"; do
   tag=clipstu${v:+_hidden}
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$tag -- python3 tools/diag/clip_student_step.py $v --steps 5 --warmup 2 > gpurun_out/prof_$tag.log 2>&1 || exit 1

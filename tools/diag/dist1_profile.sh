@@ -1,6 +1,5 @@
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-export GPU_MAX_HW_QUEUES=8
 export DCLIP_FORCE_DIST=1
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r03_dist1 -- python3 bench.py --no-cpu-baseline --steps 5 --warmup 3 > gpurun_out/prof_r03_dist1.log 2>&1
 python3 - <<'PY'

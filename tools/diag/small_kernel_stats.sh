@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-export GPU_MAX_HW_QUEUES=8 DCLIP_MULTI_STREAM=0
+export DCLIP_MULTI_STREAM=0
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_small -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 2 --no-roofline > gpurun_out/prof_small.log 2>&1
 python3 - <<'PY'
 import csv,glob,os

@@ -6,7 +6,6 @@ TAG=${1:-r03}
 CONFIGS=${2:-"default image text lclip336"}     # subset per call when the box time is limited (gpurun caps a call at 20 min)
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
-export GPU_MAX_HW_QUEUES=8        # read at HIP initialisation, which the profiler's preload performs before python starts
 # the four towers normally run on four streams: co-running kernels stretch each other's durations in a kernel trace, so the
 # profiled passes put every tower on one stream (same kernels, same launches; the multi-stream step time is bench.py's number)
 export DCLIP_MULTI_STREAM=0
