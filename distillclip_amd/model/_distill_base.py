@@ -1,0 +1,108 @@
+"""What DistillModel (one student tower) and DualDistillModel (two) share: the data-parallel backward, the optimizer, the retrieval
+metrics of validation and the rules that freeze and unfreeze student parameters.  Each module keeps its own constructor, forward,
+training / validation steps and `towers()`, the list of student towers everything here works on."""
+from torch import nn
+
+from .component.image_encoder import ImageEncoder
+from .component.weight_share_model import RepeatVisionTransformer
+from ..optim import FusedAdamW, EpochCosineSchedule
+from ..parallel import GradSync
+from ..metrics import retrieval_metrics
+
+
+class _HParams(dict):
+    __getattr__ = dict.__getitem__
+    __setattr__ = dict.__setitem__
+
+
+_TEACHER_EMBED_KEYS = ['visual.conv1.weight', 'visual.class_embedding', 'visual.positional_embedding']
+_REPEAT_EMBED_KEYS = ['patch_embed.proj.weight', 'cls_token', 'pos_embed']
+
+
+def freeze_image_embedding(enc, teacher_state, prefix):
+    """reference distil_model.py:197-219 / dual_distill_model.py:240-268: the teacher's patch / class / positional embeddings
+    (`prefix` + OpenAI key in `teacher_state`) copied into the image student `enc` and frozen.  A plain CLIP student has the teacher's
+    keys; a RepeatVisionTransformer takes them as patch_embed / cls_token [1, 1, D] / pos_embed [1, N, D]; the reference does nothing
+    for other student classes."""
+    if isinstance(enc, ImageEncoder):
+        keys = _TEACHER_EMBED_KEYS
+    elif isinstance(enc, RepeatVisionTransformer):
+        keys = _REPEAT_EMBED_KEYS
+    else:
+        return
+    sw = enc.state_dict()
+    for s_k, t_k in zip(keys, _TEACHER_EMBED_KEYS):
+        w = teacher_state[prefix + t_k]
+        if s_k == 'cls_token':
+            w = w.unsqueeze(0).unsqueeze(0)
+        elif s_k == 'pos_embed':
+            w = w.unsqueeze(0)
+        sw[s_k] = w
+    enc.load_state_dict(sw)
+    for n, p in enc.named_parameters():
+        if n in keys:
+            p.requires_grad = False
+
+
+class DistillBase(nn.Module):
+    def towers(self):
+        """the student towers (HipTower), in the order the optimizer and the gradient exchange see them"""
+        raise NotImplementedError
+
+    def _ensure_sync(self):
+        """data-parallel plumbing of the student towers (lazy: torch.distributed may be initialised after __init__)"""
+        self._sync = GradSync.current(self._sync).attach(self.towers())
+        return self._sync
+
+    def backward_and_sync(self, loss, defer_wait=False):
+        """loss.backward() + the data-parallel gradient exchange (reference strategy ddp_find_unused_parameters_false,
+        l_clip.yaml:56).  Sharded mode: every gradient bucket is reduce-scattered from inside its tower's backward (per-block
+        release, reverse layer order) and FusedAdamW.step() updates the owned shards and all-gathers the parameters; fallback:
+        each tower's flat buffer is all-reduced on a side stream right after its backward has been enqueued."""
+        sync = self._ensure_sync()
+        if loss is not None:                                   # None: the caller already ran loss.backward()
+            sync.armed = sync.enabled                          # per-bucket release from inside the towers' backward: only here
+            try:
+                loss.backward()
+            finally:
+                sync.armed = False
+        if not sync.enabled:
+            return
+        for tw in self.towers():
+            if tw.dp is not None:
+                tw.grads_ready = sync.finish(tw)
+                tw._grad_clean = True                          # exchanged buckets were cleared behind their reduce-scatter
+            else:
+                tw.grads_ready = sync.launch(tw.flat_grad, after=tw.bwd_done)
+        if not defer_wait:       # defer_wait: FusedAdamW.step waits per tower on `grads_ready` / runs on the exchange stream
+            sync.wait()
+        else:
+            sync.forget()
+
+    def configure_optimizers(self):
+        # reference distil_model.py:160-169, dual_distill_model.py:194-202: AdamW over every requires_grad parameter (one group)
+        # + cosine schedule stepped per epoch
+        towers = self.towers()
+        dev = next(self.student.parameters()).device
+        for tw in towers:
+            tw.materialize(dev)
+        extras = [p for tw in towers                             # a plain CLIP student's projection linears (tw.module: its encoder)
+                  for p in getattr(tw.module, 'extra_parameters', lambda: [])()]
+        opt = FusedAdamW(towers, lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras)
+        sched = EpochCosineSchedule(opt, self.hparams.warm_steps, self.hparams.total_steps)
+        self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with
+        return [opt], [sched]
+
+    def unfreeze_embed(self):
+        for _, p in self.student.named_parameters():
+            p.requires_grad = True
+
+    def _acc(self, log, rows, cols, section, prefix, acc=True, score=False):
+        # reference distil_model.py norm_and_logits :224-231 builds stu_logits = stu_encode @ encode.T : rows = this tower, cols = the other
+        m = retrieval_metrics(rows, cols, self.k_list)
+        if acc:                        # reference log_acc: distil_model.py:187-191, dual_distill_model.py:220-224
+            for k in self.k_list:
+                log[f'{section}/{prefix}_acc_top{k}'] = m[f'acc_top{k}']
+        if score:                      # reference log_diag_score: distil_model.py:171-179, dual_distill_model.py:204-212
+            log[f'{section}/{prefix}_softmax_mean_score'] = m['softmax_mean_score']
+            log[f'{section}/{prefix}_mean_score'] = m['mean_score']

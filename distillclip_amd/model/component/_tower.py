@@ -106,6 +106,7 @@ class HipTower:
         self.dp = None                             # parallel._Shards: bucket / shard plan of this tower's flat buffers
         self.gshard = None                         # this rank's averaged gradient shards (reduce-scatter output)
         self.dp_released = 0
+        self._anchor = None                        # run_tower: requires-grad scalar input of the tower's autograd Function
         # trainable towers re-cast their bf16 weight cache at every forward unless an optimizer that maintains
         # `wcache_dirty` itself (FusedAdamW) has taken over; any other in-place update of the masters needs the re-cast
         self._prepare_always = True
@@ -123,8 +124,9 @@ class HipTower:
     # ---- parameter plumbing -------------------------------------------------------------------------------------
     def _params(self):
         """reference-named parameters in the canonical order of include/dclip.h.  The module tree of a tower never changes
-        after construction (load_state_dict / .cuda() keep the Parameter objects), so names are resolved once; a replaced
-        Parameter object is caught by an identity check of the first one (looked up through its owning sub-module)."""
+        after construction (load_state_dict / .cuda() keep the Parameter objects), so names are resolved, and the flat layout
+        computed, once; a replaced Parameter object is caught by an identity check of the first one (looked up through its
+        owning sub-module)."""
         cached = getattr(self, '_plist', None)
         if cached is not None and self._first_owner._parameters.get(self._first_key) is self._first_param:
             return cached
@@ -136,56 +138,41 @@ class HipTower:
         for part in path:
             owner = getattr(owner, part)
         self._first_owner, self._first_key, self._first_param = owner, key, owner._parameters.get(key)
+        # flat layout: every live parameter starts a segment of its size rounded up to 64 elements
+        offs = [0]
+        for p in plist:
+            offs.append(offs[-1] + (0 if p is None else (p.numel() + 63) // 64 * 64))
+        self._param_offs = offs
+        self._offsets = [off for p, off in zip(plist, offs) if p is not None]     # flat offset of every live parameter
         self._plist = plist
         return plist
 
     def materialize(self, device):
         """(Re)build the flat buffers when the parameters are not (any more) views of them (first use, .to(), .cuda())."""
-        ps = self._params()
-        live = [p for p in ps if p is not None]
-        ok = self.flat is not None and self.flat.device == device
-        if ok:
-            off = 0
-            for p in live:
-                if p.data_ptr() != self.flat.data_ptr() + off * 4 or p.dtype != torch.float32:
-                    ok = False
-                    break
-                off += (p.numel() + 63) // 64 * 64
-        if ok:
+        live = [p for p in self._params() if p is not None]
+        if self.flat is not None and self.flat.device == device and all(
+                p.data_ptr() == self.flat.data_ptr() + off * 4 and p.dtype == torch.float32 for p, off in zip(live, self._offsets)):
             return
         if device.type != 'cuda':
             raise RuntimeError('distillclip_amd towers run on MI355X only (no CPU fallback): move the module and its inputs to cuda')
-        total = sum((p.numel() + 63) // 64 * 64 for p in live)
+        total = self._param_offs[-1]
         flat = torch.zeros(total, dtype=torch.float32, device=device)
         flat_grad = torch.zeros(total, dtype=torch.float32, device=device)
-        off = 0
         with torch.no_grad():
-            for p in live:
+            for p, off in zip(live, self._offsets):
                 n = p.numel()
                 flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
                 p.data = flat[off:off + n].view(p.shape)
                 p.grad = None
-                off += (n + 63) // 64 * 64
         self.flat, self.flat_grad = flat, flat_grad
-        self._offsets = []
-        off = 0
-        for p in live:
-            self._offsets.append(off)
-            off += (p.numel() + 63) // 64 * 64
         wbytes = lib().dclip_encoder_wcache_bytes(self._handle)
         self.wcache = torch.empty(wbytes, dtype=torch.uint8, device=device)
         self.wcache_dirty = True
 
     def param_offsets(self):
         """flat element offset of every canonical parameter index (absent parameters take the next live one's), + total"""
-        ps = self._params()
-        offs, off = [], 0
-        for p in ps:
-            offs.append(off)
-            if p is not None:
-                off += (p.numel() + 63) // 64 * 64
-        offs.append(off)
-        return offs
+        self._params()
+        return list(self._param_offs)
 
     def grad_buckets(self):
         """[(begin, end)] flat ranges in the order the backward completes them (include/dclip.h: dclip_encoder_grad_bucket)"""
@@ -199,12 +186,11 @@ class HipTower:
 
     def trainable_ranges(self):
         """contiguous [begin, end) element ranges of the requires_grad parameters inside the flat buffers"""
-        live = [p for p in self._params() if p is not None]
+        ps, offs = self._params(), self._param_offs
         out = []
-        for p, off in zip(live, self._offsets):
-            if not p.requires_grad:
+        for p, off, end in zip(ps, offs, offs[1:]):
+            if p is None or not p.requires_grad:
                 continue
-            end = off + (p.numel() + 63) // 64 * 64
             if out and out[-1][1] == off:
                 out[-1][1] = end
             else:
@@ -454,8 +440,19 @@ class _TowerFn(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(g for p, g in zip(tower._params(), gs) if p is not None)
 
 
-def run_tower(tower, x, anchor, need_rep=False, need_emb=False):
+def refuse_attention_maps(co):
+    """the HIP towers keep attention scores / probabilities / value maps on chip: a ControlOutput asking for them is refused"""
+    if co.need_attn_score or co.need_attn_prob or co.need_value_map:
+        raise NotImplementedError('the HIP towers keep attention scores / probabilities / value maps on chip; the loss terms '
+                                  'that need them (attention_*, last_value_map_kl) are outside the hot path (SURVEY.md §2.1)')
+
+
+def run_tower(tower, x, need_rep=False, need_emb=False):
     """-> (last_representation, [hidden state per block execution], embedding or None)"""
+    # a requires-grad scalar that makes the tower's autograd Function part of the graph whatever its other inputs are
+    anchor = tower._anchor
+    if anchor is None or anchor.device != x.device:
+        anchor = tower._anchor = torch.zeros(1, device=x.device, requires_grad=True)
     if torch.is_grad_enabled() and any(p.requires_grad for p in tower.module.parameters()):
         params = ()
         if autograd_params_mode(tower):

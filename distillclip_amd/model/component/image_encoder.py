@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from .output import ControlOutput, VisionTransformerOutput
-from ._tower import EncoderCfg, HipTower, run_tower
+from ._tower import EncoderCfg, HipTower, refuse_attention_maps, run_tower
 from ._proj import HipLinear
 
 
@@ -85,15 +85,6 @@ class _Visual(nn.Module):
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
 
 
-def student_anchor(module, device):
-    """a requires-grad scalar that makes the tower's autograd Function part of the graph whatever its other inputs are"""
-    a = getattr(module, '_anchor', None)
-    if a is None or a.device != device:
-        a = torch.zeros(1, device=device, requires_grad=True)
-        object.__setattr__(module, '_anchor', a)
-    return a
-
-
 def init_layers_from_teacher(module, own_state, load, pattern, layer_map, teacher_state_dict, init_type):
     """reference image_encoder.py:70-99 / text_encoder.py:124-155: copy every teacher tensor whose key the student also has; keys of
     transformer layer i take teacher layer i ('begin'), tea - stu + i ('end') or i * layer_map.step ('mid')."""
@@ -119,6 +110,33 @@ def init_layers_from_teacher(module, own_state, load, pattern, layer_map, teache
         else:
             own_state[key] = teacher_state_dict[re.sub(digit, to(int(found[0])), string=key, count=1)]
     load(own_state)
+
+
+def encode_clip(enc, x, control_output, output_cls, max_tokens=None):
+    """forward of a plain CLIP encoder `enc` (ImageEncoder / TextEncoder) in either role -> output_cls.  Student (reference
+    image_encoder.py:50-61, text_encoder.py:66-82): the trainable tower, then the hidden-state / embedding projections to the teacher's
+    width unless `enc.no_trans`.  Teacher: one no-grad forward with hidden states only for `need_layers` (reference _common.py:154-158);
+    `max_tokens` (the text teacher's hint) limits it to the caption prefix that holds every EOT when only the pooled output is asked for."""
+    co = control_output or ControlOutput()
+    refuse_attention_maps(co)
+    want_all = getattr(co, 'need_last_layer_output', False)
+    if enc.is_student:
+        if enc.need_layers is not None and list(enc.need_layers) != list(range(enc.layers)):
+            raise NotImplementedError('a trainable CLIP tower exports every layer\'s hidden state (need_layers = all)')
+        out, reps, emb = run_tower(enc._tower, x, co.need_rep, co.need_emb)
+        if not enc.no_trans:
+            if co.need_rep:
+                reps = [enc.hidden_projection(r) for r in reps]
+            if co.need_emb:
+                emb = enc.embedding_projection(emb)
+    else:
+        hint = max_tokens if (max_tokens and not co.need_rep and not co.need_emb and not want_all) else 0
+        with torch.no_grad():
+            out, _, reps, emb = enc._tower.forward(x, training=False, need_rep=co.need_rep, need_emb=co.need_emb,
+                                                   rep_layers=list(enc.need_layers) if enc.need_layers is not None else None,
+                                                   tokens_eff=min(int(hint), enc._tower.cfg.tokens))
+    llo = enc._tower.last_layer_output() if want_all else None
+    return output_cls(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb)
 
 
 class ImageEncoder(nn.Module):
@@ -148,7 +166,6 @@ class ImageEncoder(nn.Module):
                  'visual.ln_pre.bias'] + teacher_block_names('visual.', self.layers) + \
                 ['visual.ln_post.weight', 'visual.ln_post.bias', 'visual.proj']
         object.__setattr__(self, '_tower', HipTower(self, cfg, names))
-        self.register_load_state_dict_post_hook(lambda m, keys: setattr(m._tower, 'wcache_dirty', True))
 
     @property
     def need_layers(self):
@@ -163,25 +180,7 @@ class ImageEncoder(nn.Module):
         return [p for m in (self.embedding_projection, self.hidden_projection) if m is not None for p in m.parameters()]
 
     def encode_image(self, image, control_output: ControlOutput = None):
-        co = control_output or ControlOutput()
-        if co.need_attn_score or co.need_attn_prob or co.need_value_map:
-            raise NotImplementedError('teacher attention maps are not exported by the HIP tower (SURVEY.md §2.1)')
-        if self.is_student:
-            if self.need_layers is not None and list(self.need_layers) != list(range(self.layers)):
-                raise NotImplementedError('a trainable CLIP tower exports every layer\'s hidden state (need_layers = all)')
-            out, reps, emb = run_tower(self._tower, image, student_anchor(self, image.device), co.need_rep, co.need_emb)
-            if not self.no_trans:                                                        # reference :54-59
-                if co.need_rep:
-                    reps = [self.hidden_projection(r) for r in reps]
-                if co.need_emb:
-                    emb = self.embedding_projection(emb)
-            llo = self._tower.last_layer_output() if getattr(co, 'need_last_layer_output', False) else None
-            return VisionTransformerOutput(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb)
-        with torch.no_grad():   # hidden states only for `need_layers` (reference _common.py:154-158)
-            out, _, reps, emb = self._tower.forward(image, training=False, need_rep=co.need_rep, need_emb=co.need_emb,
-                                                    rep_layers=list(self.need_layers) if self.need_layers is not None else None)
-        llo = self._tower.last_layer_output() if getattr(co, 'need_last_layer_output', False) else None
-        return VisionTransformerOutput(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb)
+        return encode_clip(self, image, control_output, VisionTransformerOutput)
 
     def last_layer_output(self):
         """[B, N, E] = ln_post(x) @ proj for every token of the most recent forward (reference _common.py:210-215)"""

@@ -9,9 +9,9 @@ import torch
 from torch import nn
 
 from .output import ControlOutput, TextTransformerOutput
-from ._tower import EncoderCfg, HipTower, run_tower
+from ._tower import EncoderCfg, HipTower
 from ._proj import HipLinear
-from .image_encoder import TeacherTransformer, _LN, teacher_block_names, student_anchor, init_layers_from_teacher
+from .image_encoder import ImageEncoder, TeacherTransformer, _LN, teacher_block_names, encode_clip, init_layers_from_teacher
 
 
 class TextEncoder(nn.Module):
@@ -54,39 +54,15 @@ class TextEncoder(nn.Module):
         names = ['token_embedding.weight', 'positional_embedding']
         names += teacher_block_names('', transformer_layers) + ['ln_final.weight', 'ln_final.bias', 'text_projection']
         object.__setattr__(self, '_tower', HipTower(self, cfg, names))
-        self.register_load_state_dict_post_hook(lambda m, keys: setattr(m._tower, 'wcache_dirty', True))
 
     @property
     def need_layers(self):
         return self._need_layers
 
-    def extra_parameters(self):
-        """trainable parameters that are not part of the tower's flat buffers (the optimizer updates them one by one)"""
-        return [p for m in (self.embedding_projection, self.hidden_projection) if m is not None for p in m.parameters()]
+    extra_parameters = ImageEncoder.extra_parameters
 
     def encode_text(self, text, control_output: ControlOutput = None):
-        co = control_output or ControlOutput()
-        if co.need_attn_score or co.need_attn_prob or co.need_value_map:
-            raise NotImplementedError('teacher attention maps are not exported by the HIP tower (SURVEY.md §2.1)')
-        want_all = getattr(co, 'need_last_layer_output', False)
-        if self.is_student:
-            if self.need_layers is not None and list(self.need_layers) != list(range(self.layers)):
-                raise NotImplementedError('a trainable CLIP tower exports every layer\'s hidden state (need_layers = all)')
-            out, reps, emb = run_tower(self._tower, text, student_anchor(self, text.device), co.need_rep, co.need_emb)
-            if not self.no_trans:                                                        # reference :75-80
-                if co.need_rep:
-                    reps = [self.hidden_projection(r) for r in reps]
-                if co.need_emb:
-                    emb = self.embedding_projection(emb)
-            llo = self._tower.last_layer_output() if want_all else None
-            return TextTransformerOutput(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb)
-        with torch.no_grad():   # hidden states only for `need_layers` (reference _common.py:154-158)
-            hint = self.max_tokens if (self.max_tokens and not co.need_rep and not co.need_emb and not want_all) else 0
-            out, _, reps, emb = self._tower.forward(text, training=False, need_rep=co.need_rep, need_emb=co.need_emb,
-                                                    rep_layers=list(self.need_layers) if self.need_layers is not None else None,
-                                                    tokens_eff=min(int(hint), self.context_length))
-        llo = self._tower.last_layer_output() if want_all else None
-        return TextTransformerOutput(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb)
+        return encode_clip(self, text, control_output, TextTransformerOutput, max_tokens=self.max_tokens)
 
     def last_layer_output(self):
         """[B, N, E] = ln_final(x) @ text_projection for every token of the most recent forward (text_encoder.py:69-72)"""

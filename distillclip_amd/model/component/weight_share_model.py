@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from .output import ControlOutput, VisionTransformerOutput, TextTransformerOutput
-from ._tower import EncoderCfg, HipTower, run_tower
+from ._tower import EncoderCfg, HipTower, refuse_attention_maps, run_tower
 
 
 def _trunc_normal_(t, std=.02):
@@ -133,13 +133,6 @@ def _block_param_names(n_blocks, repeats, qkv_bias, use_transform):
 class _StudentBase(nn.Module):
     _tower: Optional[HipTower] = None
 
-    def _anchor_for(self, device):
-        a = getattr(self, '_anchor', None)
-        if a is None or a.device != device:
-            a = torch.zeros(1, device=device, requires_grad=True)
-            object.__setattr__(self, '_anchor', a)
-        return a
-
     @property
     def output_layer(self):
         return self.head
@@ -151,10 +144,13 @@ class _StudentBase(nn.Module):
         """[B, N, E] all-token output of norm + head for the most recent forward (weight_share_model.py:363-366, :503-506)"""
         return self._tower.last_layer_output()
 
-    def _check_control(self, co: Optional[ControlOutput]):
-        if co is not None and (co.need_attn_score or co.need_attn_prob or co.need_value_map):
-            raise NotImplementedError('the HIP towers keep attention scores / probabilities / value maps on chip; the loss terms '
-                                      'that need them (attention_*, last_value_map_kl) are outside the hot path (SURVEY.md §2.1)')
+    def _features(self, x, control_output: Optional[ControlOutput], output_cls):
+        co = control_output or ControlOutput()
+        refuse_attention_maps(co)
+        rep, hidden, emb = run_tower(self._tower, x, co.need_rep, co.need_emb)
+        # like the reference, EVERY block execution contributes a hidden state (weight_share_model.py:211, :356-357)
+        llo = self._tower.last_layer_output() if getattr(co, 'need_last_layer_output', False) else None
+        return output_cls(last_representation=rep, last_layer_output=llo, representations=hidden, embedding=emb)
 
 
 class RepeatVisionTransformer(_StudentBase):
@@ -200,12 +196,7 @@ class RepeatVisionTransformer(_StudentBase):
         return self.head
 
     def forward_features(self, x, control_output: ControlOutput = None):
-        self._check_control(control_output)
-        co = control_output or ControlOutput()
-        rep, hidden, emb = run_tower(self._tower, x, self._anchor_for(x.device), co.need_rep, co.need_emb)
-        # like the reference, EVERY block execution contributes a hidden state (weight_share_model.py:211, :356-357)
-        llo = self._tower.last_layer_output() if getattr(co, 'need_last_layer_output', False) else None
-        return VisionTransformerOutput(last_representation=rep, last_layer_output=llo, representations=hidden, embedding=emb)
+        return self._features(x, control_output, VisionTransformerOutput)
 
     def forward(self, x, control_output: ControlOutput = None):
         return self.forward_features(x, control_output)
@@ -263,11 +254,7 @@ class RepeatTextTransformer(_StudentBase):
         return self.head
 
     def forward_features(self, text, control_output: ControlOutput = None):
-        self._check_control(control_output)
-        co = control_output or ControlOutput()
-        rep, hidden, emb = run_tower(self._tower, text, self._anchor_for(text.device), co.need_rep, co.need_emb)
-        llo = self._tower.last_layer_output() if getattr(co, 'need_last_layer_output', False) else None
-        return TextTransformerOutput(last_representation=rep, last_layer_output=llo, representations=hidden, embedding=emb)
+        return self._features(text, control_output, TextTransformerOutput)
 
     def forward(self, x, control_output: ControlOutput = None):
         return self.forward_features(x, control_output)

@@ -2,30 +2,21 @@
 
 The reference class is a pytorch_lightning.LightningModule; Lightning is not installed here, so the same constructor,
 `forward`, `training_step`, `configure_optimizers`, `freeze_image_embedding` are provided on a plain nn.Module (the
-methods Lightning would call).  `validation_step` / `validation_epoch_end` return the scalars the reference logs, computed
+methods Lightning would call; those DualDistillModel shares come from _distill_base.py).  `validation_step` / `validation_epoch_end` return the scalars the reference logs, computed
 by the HIP retrieval kernel (distillclip_amd/metrics.py) instead of torchmetrics; wandb / heat-map logging is not mirrored.
 """
 from typing import Dict, List
 
 import torch
-from torch import nn
 
+from ._distill_base import DistillBase, _HParams, freeze_image_embedding
 from ._loss import LossCalculator
 from .utils import teacher_load
-from .component.weight_share_model import RepeatVisionTransformer
-from .component.image_encoder import ImageEncoder
 from .component._tower import shared_image_patches
-from ..optim import FusedAdamW, EpochCosineSchedule
-from ..parallel import GradSync
-from ..metrics import retrieval_metrics, gather_rows
+from ..metrics import gather_rows
 
 
-class _HParams(dict):
-    __getattr__ = dict.__getitem__
-    __setattr__ = dict.__setitem__
-
-
-class DistillModel(nn.Module):
+class DistillModel(DistillBase):
     def __init__(self, student_encoder: torch.nn.Module, loss_control_para: Dict, download_root: str,
                  teacher_name: str = 'ViT-B/32', freeze_embed: bool = False, teacher_need_layers: List = None,
                  model_type: str = 'image', warm_steps=10, total_steps=200, weight_decay=1e-3, lr: float = 1e-3,
@@ -75,44 +66,6 @@ class DistillModel(nn.Module):
     def towers(self):
         return [self.student._tower]
 
-    def _ensure_sync(self):
-        """data-parallel plumbing of the student towers (lazy: torch.distributed may be initialised after __init__)"""
-        self._sync = GradSync.current(self._sync).attach(self.towers())
-        return self._sync
-
-    def backward_and_sync(self, loss, defer_wait=False):
-        """loss.backward() + the data-parallel gradient exchange (reference strategy ddp_find_unused_parameters_false):
-        bucketed reduce-scatter released from inside the backward + sharded AdamW + parameter all-gather (parallel.py)."""
-        sync = self._ensure_sync()
-        if loss is not None:
-            sync.armed = sync.enabled                          # per-bucket release from inside the tower's backward: only here
-            try:
-                loss.backward()
-            finally:
-                sync.armed = False
-        if not sync.enabled:
-            return
-        tw = self.student._tower
-        if tw.dp is not None:
-            tw.grads_ready = sync.finish(tw)
-            tw._grad_clean = True
-        else:
-            tw.grads_ready = sync.launch(tw.flat_grad, after=tw.bwd_done)
-        if not defer_wait:
-            sync.wait()
-        else:
-            sync.forget()
-
-    def _acc(self, log, rows, cols, section, prefix, acc=True, score=False):
-        # reference norm_and_logits :224-231 builds stu_logits = stu_encode @ encode.T : rows = this tower, cols = the other
-        m = retrieval_metrics(rows, cols, self.k_list)
-        if acc:
-            for k in self.k_list:                                          # reference log_acc :187-191
-                log[f'{section}/{prefix}_acc_top{k}'] = m[f'acc_top{k}']
-        if score:                                                          # reference log_diag_score :171-179
-            log[f'{section}/{prefix}_softmax_mean_score'] = m['softmax_mean_score']
-            log[f'{section}/{prefix}_mean_score'] = m['mean_score']
-
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
         """reference :104-126.  batch = (imgs, texts, _) where the modality that is not distilled arrives as a
@@ -141,49 +94,10 @@ class DistillModel(nn.Module):
             self._acc(log, cat['teacher'], cat['contrary_rep'], 'val_tea_acc', 'tea')
         return log
 
-    def configure_optimizers(self):
-        # reference :160-169: AdamW over every requires_grad parameter (one group) + cosine schedule stepped per epoch
-        self.student._tower.materialize(next(self.student.parameters()).device)
-        extras = getattr(self.student, 'extra_parameters', lambda: [])()       # a plain CLIP encoder's projection linears
-        opt = FusedAdamW([self.student._tower], lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras)
-        sched = EpochCosineSchedule(opt, self.hparams.warm_steps, self.hparams.total_steps)
-        self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with
-        return [opt], [sched]
-
     def on_train_epoch_start(self):
         if self.hparams.unfreeze_epoch and self.current_epoch >= self.hparams.unfreeze_epoch:
             self.unfreeze_embed()
             self.hparams.unfreeze_epoch = False
 
-    def unfreeze_embed(self):
-        for _, p in self.student.named_parameters():
-            p.requires_grad = True
-
     def freeze_image_embedding(self):
-        # reference :197-213
-        if isinstance(self.student, ImageEncoder):             # reference :211-219
-            freeze_key = ['visual.conv1.weight', 'visual.class_embedding', 'visual.positional_embedding']
-            sw, tw = self.student.state_dict(), self.teacher.state_dict()
-            for k in freeze_key:
-                sw[k] = tw[k]
-            self.student.load_state_dict(sw)
-            for n, p in self.student.named_parameters():
-                if n in freeze_key:
-                    p.requires_grad = False
-            return
-        if not isinstance(self.student, RepeatVisionTransformer):
-            return                                             # (the reference does nothing for other student classes)
-        stu_keys = ['patch_embed.proj.weight', 'cls_token', 'pos_embed']
-        tea_keys = ['visual.conv1.weight', 'visual.class_embedding', 'visual.positional_embedding']
-        sw, tw = self.student.state_dict(), self.teacher.state_dict()
-        for s_k, t_k in zip(stu_keys, tea_keys):
-            w = tw[t_k]
-            if 'cls_token' in s_k:
-                w = w.unsqueeze(0).unsqueeze(0)
-            if 'pos_embed' in s_k:
-                w = w.unsqueeze(0)
-            sw[s_k] = w
-        self.student.load_state_dict(sw)
-        for n, p in self.student.named_parameters():
-            if n in stu_keys:
-                p.requires_grad = False
+        freeze_image_embedding(self.student, self.teacher.state_dict(), '')                   # reference :197-219

@@ -11,17 +11,13 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
+from ._distill_base import DistillBase, _HParams, freeze_image_embedding
 from ._loss import LossCalculator
 from .utils import teacher_load
 from .component.clip_model import CLIPModel
 from .component.output import CLIPOutput
-from .component.weight_share_model import RepeatVisionTransformer
-from .component.image_encoder import ImageEncoder
 from .component._tower import shared_image_patches
-from .distil_model import _HParams
-from ..optim import FusedAdamW, EpochCosineSchedule
-from ..parallel import GradSync
-from ..metrics import retrieval_metrics, gather_rows
+from ..metrics import gather_rows
 
 
 def load_weight(image_student, text_student, load_path):
@@ -38,7 +34,7 @@ def load_weight(image_student, text_student, load_path):
     return load_one_model(image_student, load_path['image']), load_one_model(text_student, load_path['text'])
 
 
-class DualDistillModel(nn.Module):
+class DualDistillModel(DistillBase):
     def __init__(self, image_student: nn.Module, text_student: nn.Module, loss_control_para: Dict, warm_steps, total_steps,
                  weight_decay, lr: float, download_root: str, norm=False, teacher_name: str = 'ViT-B/32',
                  freeze_embed: bool = False, unfreeze_epoch: int = None, load_path: Dict = None,
@@ -170,45 +166,6 @@ class DualDistillModel(nn.Module):
         self.last_cal_res = cal_res
         return loss
 
-    def _ensure_sync(self):
-        """data-parallel plumbing of the student towers (lazy: torch.distributed may be initialised after __init__)"""
-        self._sync = GradSync.current(self._sync).attach(self.towers())
-        return self._sync
-
-    def backward_and_sync(self, loss, defer_wait=False):
-        """loss.backward() + the data-parallel gradient exchange (reference strategy ddp_find_unused_parameters_false,
-        l_clip.yaml:56).  Sharded mode: every gradient bucket is reduce-scattered from inside its tower's backward (per-block
-        release, reverse layer order) and FusedAdamW.step() updates the owned shards and all-gathers the parameters; fallback:
-        each tower's flat buffer is all-reduced on a side stream right after its backward has been enqueued."""
-        sync = self._ensure_sync()
-        if loss is not None:                                   # None: the caller already ran loss.backward()
-            sync.armed = sync.enabled                          # per-bucket release from inside the towers' backward: only here
-            try:
-                loss.backward()
-            finally:
-                sync.armed = False
-        if not sync.enabled:
-            return
-        for tw in self.towers():
-            if tw.dp is not None:
-                tw.grads_ready = sync.finish(tw)
-                tw._grad_clean = True                          # exchanged buckets were cleared behind their reduce-scatter
-            else:
-                tw.grads_ready = sync.launch(tw.flat_grad, after=tw.bwd_done)
-        if not defer_wait:       # defer_wait: FusedAdamW.step waits per tower on `grads_ready` / runs on the exchange stream
-            sync.wait()
-        else:
-            sync.forget()
-
-    def _acc(self, log, img, txt, section, prefix, acc=True, score=False):
-        m = retrieval_metrics(img, txt, self.k_list)
-        if acc:
-            for k in self.k_list:                                          # reference log_acc :220-224
-                log[f'{section}/{prefix}_acc_top{k}'] = m[f'acc_top{k}']
-        if score:                                                          # reference log_diag_score :204-212
-            log[f'{section}/{prefix}_softmax_mean_score'] = m['softmax_mean_score']
-            log[f'{section}/{prefix}_mean_score'] = m['mean_score']
-
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
         """reference :129-147.  -> (gathered representations for validation_epoch_end, {log key: 0-dim tensor})"""
@@ -239,18 +196,6 @@ class DualDistillModel(nn.Module):
             self._acc(log, cat['tea_image_outs'], cat['tea_text_outs'], 'val_tea_acc', 'tea')
         return log
 
-    def configure_optimizers(self):
-        # reference :194-202
-        dev = next(self.student.parameters()).device
-        for tw in self.towers():
-            tw.materialize(dev)
-        extras = [p for enc in (self.student.image_encoder, self.student.text_encoder)
-                  for p in getattr(enc, 'extra_parameters', lambda: [])()]     # plain CLIP encoders' projection linears
-        opt = FusedAdamW(self.towers(), lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras)
-        sched = EpochCosineSchedule(opt, self.hparams.warm_steps, self.hparams.total_steps)
-        self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with
-        return [opt], [sched]
-
     def on_train_epoch_start(self):
         if self.unfreeze_epoch and self.current_epoch >= self.unfreeze_epoch:
             self.unfreeze_embed()
@@ -264,36 +209,6 @@ class DualDistillModel(nn.Module):
             if any(n.startswith(prefix) for prefix in prefix_list):
                 p.requires_grad = False
 
-    def unfreeze_embed(self):
-        for _, p in self.student.named_parameters():
-            p.requires_grad = True
-
     def freeze_image_embedding(self):
-        # reference :240-268: teacher patch / class / positional embeddings copied into the image student and frozen
-        enc = self.student.image_encoder
-        if isinstance(enc, ImageEncoder):                      # reference :258-266: same keys on both sides
-            freeze_key = ['visual.conv1.weight', 'visual.class_embedding', 'visual.positional_embedding']
-            sw, tw = enc.state_dict(), self.teacher.state_dict()
-            for k in freeze_key:
-                sw[k] = tw['image_encoder.' + k]
-            enc.load_state_dict(sw)
-            for n, p in enc.named_parameters():
-                if n in freeze_key:
-                    p.requires_grad = False
-            return
-        if not isinstance(enc, RepeatVisionTransformer):
-            return                                             # (the reference does nothing for other student classes)
-        keys = {'patch_embed.proj.weight': 'image_encoder.visual.conv1.weight',
-                'cls_token': 'image_encoder.visual.class_embedding', 'pos_embed': 'image_encoder.visual.positional_embedding'}
-        sw, tw = enc.state_dict(), self.teacher.state_dict()
-        for s_k, t_k in keys.items():
-            w = tw[t_k]
-            if s_k == 'cls_token':
-                w = w.unsqueeze(0).unsqueeze(0)
-            if s_k == 'pos_embed':
-                w = w.unsqueeze(0)
-            sw[s_k] = w
-        enc.load_state_dict(sw)
-        for n, p in enc.named_parameters():
-            if n in keys:
-                p.requires_grad = False
+        # reference :240-268
+        freeze_image_embedding(self.student.image_encoder, self.teacher.state_dict(), 'image_encoder.')
