@@ -638,7 +638,8 @@ __global__ __launch_bounds__(256) void attn_softmax_fwd_kernel(SoftmaxFwd p) {
 // Head-mixing softmax forward on MFMA (one wave per (b, query row), tiles [32 heads][COLS keys] in wave-private LDS):
 //   A_g = sum_h Wl[g,h] S_h     3 MFMAs per step with split-bf16 operands (Wl_hi S_hi + Wl_hi S_lo + Wl_lo S_hi): ~16 mantissa
 //                               bits on the pre-softmax scores instead of 8
-//   e   = exp(A - rowmax)       ONE cross-lane max per query row (shared by the heads; softmax is shift-invariant per head)
+//   e   = exp(A - m_g)          m_g = max_j A[g, j], one maximum per output head g of the query row: a maximum shared by the heads
+//                               would underflow every e of a head whose scores sit ~87 below another head's (sum 0 -> P = NaN)
 //   sum_g = sum_j e[g,j]        MFMA of the e tile against a ones operand -> lands in accumulator layout (row g)
 //   P = e / sum (saved for backward) ; R_g = sum_h Ww[g,h] P_h (MFMA) ; P and R leave through LDS as 16-byte rows
 template <int H, int NS>
@@ -710,7 +711,9 @@ __global__ __launch_bounds__(256) void attn_softmax_fwd_mix_kernel(SoftmaxFwd p)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         f32x16 am[NCT];
-        float m = -INFINITY;
+        float m[16];                            // accumulator register r holds head g(r, hh) for every key: its maximum, per register
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m[r] = -INFINITY;
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
             am[ct] = f32x16{0};
@@ -725,11 +728,15 @@ __global__ __launch_bounds__(256) void attn_softmax_fwd_mix_kernel(SoftmaxFwd p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int g = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                if (jok && g < H) m = fmaxf(m, am[ct][r]);
+                if (jok && g < H) m[r] = fmaxf(m[r], am[ct][r]);
             }
         }
-        m = wave_max(m);
-        // e = exp(A - m) as bf16 rows [g][j] in LDS (pad keys / pad heads stay zero)
+        // the keys of head g(r, hh) are spread over the 32 lanes of half hh (and the column tiles, folded in above)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) m[r] = fmaxf(m[r], __shfl_xor(m[r], o));
+        // e = exp(A - m_g) as bf16 rows [g][j] in LDS (pad keys / pad heads stay zero; head g's largest e is 1, so its sum is >= 1)
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
@@ -737,7 +744,7 @@ __global__ __launch_bounds__(256) void attn_softmax_fwd_mix_kernel(SoftmaxFwd p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int g = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                const float e = (jok && g < H) ? __expf(am[ct][r] - m) : 0.f;
+                const float e = (jok && g < H) ? __expf(am[ct][r] - m[r]) : 0.f;
                 am[ct][r] = e;
                 *(bf16_t*)(tP + g * ROWB + (32 * ct + c) * 2) = f2bf(e);
             }

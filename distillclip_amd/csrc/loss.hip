@@ -7,11 +7,13 @@
 // Inputs are the four [B,E] f32 embeddings (student/teacher x image/text).  Outputs: 16 scalars (total + raw per-term
 // values) and d loss / d student embeddings.  The [B,B] student / teacher logits are never written to HBM: they are
 // recomputed as 16x16 tiles on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32) inside "stripe" workgroups:
-//   pass A  stripe (direction, 16 rows): row sums of exp((x-1)/tau) for S (tau=1 and tau) and T (tau)  -> stats
-//           (direction 1 works on the transposed logits, so its row sums are the column sums of S / T)
+//   pass A  stripe (direction, 16 rows): row log-sum-exps of S (tau = 1), S / tau and T / tau  -> stats
+//           (direction 1 works on the transposed logits, so its row statistics are the column statistics of S / T)
 //   pass B  stripe: recompute tiles, form dL/dS for the stripe in LDS ([16, B] f32; the teacher tile only lives in
 //           registers), then dS_stripe @ other-modality embeddings on MFMA -> gradient rows (plain stores: deterministic)
-// Cosine logits are bounded by 1, so softmax uses the fixed maximum 1/tau and row/column sums are plain additions.
+// Every softmax statistic is a natural-log log-sum-exp with the row's true maximum: a running (max, sum) per lane while pass A walks
+// its column tiles, merged across lanes, waves and column slices with the usual rescale (slices in order: deterministic).  A fixed
+// maximum of 1 / tau (cosines are bounded by 1) would underflow the whole row sum once the row's largest cosine sits ~87 tau below 1.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -39,7 +41,8 @@ struct LossArgs {
     float* ds[2];
     float* nrm[4];                            // normalised s_img, s_txt, t_img, t_txt  [B,E]
     float* inv[2];                            // 1 / |s|
-    float* stats;                             // [zs][6][Bl]: r1S rtS rtT c1S ctS ctT of the owned rows, one partial per column slice
+    float* stats;                             // [zs][6][Bl]: log-sum-exps of S, S / tau, T / tau over the rows (3) and the columns (3)
+                                              // of the owned rows, one partial per column slice
     const float* gstats;                      // row-block mode with hard / soft label: [6][B] statistics of EVERY row (all ranks'
                                               // pass-A results, gathered by the caller); null otherwise
     float* stats_out;                         // row-block pass-A-only call: [6][Bl] slice-summed statistics for that gather
@@ -188,8 +191,27 @@ __device__ __forceinline__ f32x4 logits_tile(const float* __restrict__ xa, const
     return acc;
 }
 
-__device__ __forceinline__ float rowgroup_sum(float v) {   // sum over the 16 lanes that share l >> 4
-    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
+// log(exp(a) + exp(b)); -inf stands for an empty sum
+__device__ __forceinline__ float log_add_exp(float a, float b) {
+    const float m = fmaxf(a, b);
+    return m == -INFINITY ? m : m + __logf(__expf(a - m) + __expf(b - m));
+}
+
+// running softmax statistic of one lane: maximum m and sum l of exp(x - m) over the values seen so far
+struct RunLse {
+    float m = -INFINITY, l = 0.f;
+    __device__ __forceinline__ void add(float x) {
+        const float mn = fmaxf(m, x);
+        l = l * __expf(m - mn) + __expf(x - mn);
+        m = mn;
+    }
+    __device__ __forceinline__ float lse() const { return l > 0.f ? m + __logf(l) : -INFINITY; }
+};
+
+__device__ __forceinline__ float rowgroup_lse(const RunLse& r) {   // log-sum-exp over the 16 lanes that share l >> 4
+    float v = r.lse();
+    v = log_add_exp(v, __shfl_xor(v, 1)); v = log_add_exp(v, __shfl_xor(v, 2));
+    v = log_add_exp(v, __shfl_xor(v, 4)); v = log_add_exp(v, __shfl_xor(v, 8));
     return v;
 }
 
@@ -204,7 +226,7 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
     const float* ta = a.nrm[2 + dir], *tb = a.nrm[3 - dir];       // teacher rows / cols
     const float itau = a.c.w_sl != 0.f ? 1.f / a.c.tau : 1.f;
     const int ia = min(i0 + (lane & 15), B - 1) - (lane & 15);    // clamp the row panel inside the matrix
-    float r1[4] = {0, 0, 0, 0}, rs[4] = {0, 0, 0, 0}, rt[4] = {0, 0, 0, 0};
+    RunLse r1[4], rs[4], rt[4];
     float pos = 0.f, neg = 0.f, mse = 0.f, diag = 0.f;
     const int ntile = (B + 15) / 16;
     const int z = blockIdx.z, t0 = (int)((int64_t)ntile * z / a.zs), t1 = (int)((int64_t)ntile * (z + 1) / a.zs);   // this slice's column tiles
@@ -219,8 +241,8 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
             const int row = i0 + (lane >> 4) * 4 + q;
             if (row < iend && col < B) {
                 const float s = S[q], t = T[q];
-                if (a.c.w_hl != 0.f) r1[q] += __expf(s - 1.f);
-                if (a.c.w_sl != 0.f) { rs[q] += __expf((s - 1.f) * itau); rt[q] += __expf((t - 1.f) * itau); }
+                if (a.c.w_hl != 0.f) r1[q].add(s);
+                if (a.c.w_sl != 0.f) { rs[q].add(s * itau); rt[q].add(t * itau); }
                 if (dir == 0) {
                     if (row == col) { pos += fmaxf(t - s, 0.f); diag += s; }
                     else neg += fmaxf(s - t, 0.f);
@@ -231,7 +253,7 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const float x = rowgroup_sum(r1[q]), y = rowgroup_sum(rs[q]), z = rowgroup_sum(rt[q]);
+        const float x = rowgroup_lse(r1[q]), y = rowgroup_lse(rs[q]), z = rowgroup_lse(rt[q]);
         if ((lane & 15) == 0) {
             red[wave][(lane >> 4) * 4 + q][0] = x; red[wave][(lane >> 4) * 4 + q][1] = y; red[wave][(lane >> 4) * 4 + q][2] = z;
         }
@@ -248,7 +270,7 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
     if (threadIdx.x < 48) {
         const int r = threadIdx.x % 16, k = threadIdx.x / 16;
         if (i0 + r < iend) {
-            const float v = (red[0][r][k] + red[1][r][k]) + (red[2][r][k] + red[3][r][k]);
+            const float v = log_add_exp(log_add_exp(red[0][r][k], red[1][r][k]), log_add_exp(red[2][r][k], red[3][r][k]));
             a.stats[((int64_t)z * 6 + dir * 3 + k) * a.Bl + i0 - a.r0 + r] = v;
         }
     }
@@ -299,10 +321,10 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
     // (the column statistics exist only when the call owns every row: hard_label / soft_label are not offered in row-block mode)
     const float* rst = a.stats + (int64_t)dir * 3 * Bl;
     const float* cst = a.stats + (int64_t)(1 - dir) * 3 * Bl;
-    // the row / column sums arrive as one partial per column slice of pass A: added in slice order (deterministic)
+    // the row / column log-sum-exps arrive as one partial per column slice of pass A: merged in slice order (deterministic)
     auto stat = [&](const float* base, int idx) {
-        float v = 0.f;
-        for (int zz = 0; zz < a.zs; ++zz) v += base[(int64_t)zz * 6 * Bl + idx];
+        float v = -INFINITY;
+        for (int zz = 0; zz < a.zs; ++zz) v = log_add_exp(v, base[(int64_t)zz * 6 * Bl + idx]);
         return v;
     };
     // with gathered statistics: row k of direction d is a.gstats[(d * 3 + k) * B + global index]
@@ -330,7 +352,7 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
         const int col = j0 + (lane & 15);
         const int cc = min(col, B - 1);
         const bool cstat = a.c.w_hl != 0.f || a.c.w_sl != 0.f;      // only then (and only with every row owned) are they read
-        float c1 = 1.f, cs = 1.f, ct = 1.f;
+        float c1 = 0.f, cs = 0.f, ct = 0.f;
         if (cstat && gcol) { c1 = gcol[cc]; cs = gcol[B + cc]; ct = gcol[2 * B + cc]; }
         else if (cstat) { c1 = stat(cst, cc); cs = stat(cst, Bl + cc); ct = stat(cst, 2 * Bl + cc); }
 #pragma unroll
@@ -343,16 +365,13 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
                 if (row == col) d -= (t > s) ? k_cd_pos : 0.f;
                 else d += (s > t) ? k_cd_neg : 0.f;
                 d += k_mse * (s - t);
-                if (a.c.w_hl != 0.f) {
-                    const float e = __expf(s - 1.f);
-                    d += k_hl * (e / rr1[q] + e / c1 - (row == col ? 2.f : 0.f));
-                }
+                if (a.c.w_hl != 0.f) d += k_hl * (__expf(s - rr1[q]) + __expf(s - c1) - (row == col ? 2.f : 0.f));
                 if (a.c.w_sl != 0.f) {
-                    const float es = __expf((s - 1.f) * itau), et = __expf((t - 1.f) * itau);
-                    d += k_sl * ((es / rrs[q] - et / rrt[q]) + (es / cs - et / ct));
+                    const float xs = s * itau, xt = t * itau;
                     // KLDiv(sum) of this direction's rows: p_t (log p_t - log p_s)
-                    const float lpt = (t - 1.f) * itau - __logf(rrt[q]), lps = (s - 1.f) * itau - __logf(rrs[q]);
-                    klacc += (et / rrt[q]) * (lpt - lps);
+                    const float lpt = xt - rrt[q], lps = xs - rrs[q], pt = __expf(lpt);
+                    d += k_sl * ((__expf(lps) - pt) + (__expf(xs - cs) - __expf(xt - ct)));
+                    klacc += pt * (lpt - lps);
                 }
             }
             dsl[rl * ldl + col - t0 * 16] = d;
@@ -363,7 +382,7 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
         if (lane == 0) unsafeAtomicAdd(scal_slot(a) + (dir ? SC_KL1 : SC_KL0), klacc);
     }
     if (a.c.w_hl != 0.f && z == 0 && wave == 0 && lane < 16 && i0 + lane < iend)
-        unsafeAtomicAdd(scal_slot(a) + (dir ? SC_LSE1 : SC_LSE0), __logf(grow ? grow[i0 + lane] : stat(rst, i0 - a.r0 + lane)) + 1.f);
+        unsafeAtomicAdd(scal_slot(a) + (dir ? SC_LSE1 : SC_LSE0), grow ? grow[i0 + lane] : stat(rst, i0 - a.r0 + lane));
     __syncthreads();
     // gradient rows: G[16, E] = dS_stripe[16, B] @ Y[B, E],  Y = normalised student embedding of the other modality
     // (this slice's columns only: the slices' partial rows are added by the stripe's last-arriving slice, loss_finalize_row)
@@ -392,12 +411,12 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
     }
 }
 
-// pass-A-only call of the row-block mode: the owned rows' statistics, slices added in order, for the caller's all-gather
+// pass-A-only call of the row-block mode: the owned rows' log-sum-exps, slices merged in order, for the caller's all-gather
 __global__ void loss_stats_out_kernel(LossArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 6 * a.Bl) return;
-    float v = 0.f;
-    for (int zz = 0; zz < a.zs; ++zz) v += a.stats[(int64_t)zz * 6 * a.Bl + i];
+    float v = -INFINITY;
+    for (int zz = 0; zz < a.zs; ++zz) v = log_add_exp(v, a.stats[(int64_t)zz * 6 * a.Bl + i]);
     a.stats_out[i] = v;
 }
 

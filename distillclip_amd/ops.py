@@ -165,8 +165,9 @@ def distill_loss(s_img, t_img, s_txt=None, t_txt=None, *, weights, temperature=N
     """Fused loss fwd+bwd.  weights: {term: scale*percent}.  -> (scalars[16] device tensor, d_s_img, d_s_txt).
     row0 / rows: evaluate only the row block [row0, row0 + rows) of the (gathered) batch against all columns — gradients
     [rows, E] of the owned samples, scalars = this block's share (sum over the blocks = the whole-batch values).
-    hard_label / soft_label in row-block mode: first `stats_only=True` -> [6, rows] statistics of the owned rows; gather all
-    blocks into [6, B] and pass them as `gathered_stats` to the second call."""
+    hard_label / soft_label in row-block mode: first `stats_only=True` -> [6, rows] statistics of the owned rows (natural-log
+    log-sum-exps of S, S / tau, T / tau over each row, then over each column); gather all blocks into [6, B] and pass them as
+    `gathered_stats` to the second call."""
     import ctypes
     _chk(s_img, t_img, s_txt, t_txt)
     B, E = s_img.shape

@@ -300,7 +300,9 @@ int dclip_retrieval_metrics(const float* img, const float* txt, int64_t n, int64
  * every scalar: summing the 16 values over the ranks (one small all-reduce) gives the loss of the concatenated batch.
  * hard_label / soft_label need the softmax statistics of EVERY row (both directions): call once with stats_out (f32 [6, rows]; only the
  * statistics pass runs, no gradients), all-gather the ranks' blocks into [6, B] (statistic-major, rows in rank order), and call again
- * with gathered_stats.  Both pointers null: only terms without such statistics (cos_diff, logits_mse, tower terms) may be enabled.
+ * with gathered_stats.  Statistic k of row r is a natural-log log-sum-exp over the B logits of that row (k = 0..2) or column (k = 3..5):
+ * log sum_j exp(x_j) for x = S (hard_label), S / tau and T / tau (soft_label); S / T = student / teacher cosine logits, tau = cfg[8].
+ * Both pointers null: only terms without such statistics (cos_diff, logits_mse, tower terms) may be enabled.
  * Same workspace query (with the gathered B).
  */
 int dclip_distill_loss_rows(const float* s_img, const float* t_img, const float* s_txt, const float* t_txt, int64_t B, int64_t E,
