@@ -47,6 +47,7 @@ struct Plan {
     dclip_encoder_cfg c;
     int D, H, hd, N, Np, F, E, L, R, K;        // K = patch GEMM contraction (image)
     bool student, image, compressed;           // student = the weight-shared MiniViT architecture (kind 1)
+    bool mixing;                               // conv_l / conv_w cross-head mixing (head_mix; students only)
     bool train;                                // the tower has a backward (kind 1, 2): transposed weights cached, f32 residual stream
     // parameter indices
     int p_embed0;                              // first embedding parameter
@@ -63,7 +64,7 @@ int64_t wtake(int64_t& off, int64_t n) { int64_t o = off; off += (n + 127) & ~(i
 
 bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
     p.c = c;
-    p.student = c.kind == 1; p.train = c.kind != 0; p.image = c.modality == 0;
+    p.student = c.kind == 1; p.train = c.kind != 0; p.image = c.modality == 0; p.mixing = p.student && c.head_mix;
     p.D = c.width; p.H = c.heads; p.N = c.tokens; p.F = c.mlp_dim; p.E = c.out_dim; p.L = c.layers; p.R = c.repeats;
     if (c.kind < 0 || c.kind > 2 || c.modality < 0 || c.modality > 1) { dclip_set_error("encoder: bad kind/modality"); return false; }
     if (p.D <= 0 || p.H <= 0 || p.D % p.H) { dclip_set_error("encoder: width %d not divisible by heads %d", p.D, p.H); return false; }
@@ -86,7 +87,7 @@ bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
         if (p.compressed && c.embed_rank % 64) { dclip_set_error("encoder: embed_rank must be a multiple of 64"); return false; }
         if (p.compressed && !p.student) { dclip_set_error("encoder: a compressed token embedding exists for the weight-shared student only (kind 1)"); return false; }
     }
-    if (p.student && c.head_mix && p.H != 2 && p.H != 4 && p.H != 8 && p.H != 12 && p.H != 24) {
+    if (p.mixing && p.H != 2 && p.H != 4 && p.H != 8 && p.H != 12 && p.H != 24) {
         dclip_set_error("encoder: head count %d unsupported by the head-mixing kernels", p.H); return false;
     }
     // parameter order
@@ -118,16 +119,34 @@ bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
     return true;
 }
 
+// The score stage a tower's attention runs; the workspace layout and both directions' launches follow it.
+//   Fused   : inference without head mixing (the frozen teacher): one kernel, no score tensors in HBM.
+//   Mix     : head-mixing students whose shape has an instantiation of the register-resident score stage (attention_mix.hip:
+//             both head mixes on the matrix pipe).  S, P, dR never reach HBM: the backward recomputes them from qkv and the
+//             forward's softmax statistics.
+//   Unfused : everything else (training without head mixing, head counts dclip_attn_mix_supported rejects, DCLIP_ATTN_MIX=0):
+//             attn_nt -> softmax -> attn_nn with scores and probabilities through HBM.
+enum class AttnPath { Fused, Mix, Unfused };
+inline AttnPath attn_path(const Plan& p, bool training) {
+    static const int mode = [] { const char* e = getenv("DCLIP_ATTN_MIX"); return e ? atoi(e) : 1; }();
+    if (!training && !p.mixing) return AttnPath::Fused;
+    if (p.mixing && mode != 0 && !p.c.causal && dclip_attn_mix_supported(p.H, p.N, p.hd) != 0) return AttnPath::Mix;
+    return AttnPath::Unfused;
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // workspace layout
 // ------------------------------------------------------------------------------------------------------------
-struct ExecSave {          // per block execution (student training)
+struct ExecSave {          // one block execution: its own set per execution in training, one set shared by all in inference
     void* x_mid;           // residual stream after the attention branch: f32 (students), f16 (the frozen teacher)
     float* mean1; float* rstd1; float* mean2; float* rstd2;
-    bf16_t *h1, *qkv, *P, *Rm, *ctx, *h2, *u;
+    bf16_t *h1, *qkv, *ctx, *h2, *u;
     uint8_t* z;            // gelu'(fc1 pre-activation) as 8-bit fixed point (DCLIP_ACT_GELU_SAVE -> DCLIP_ACT_MULAUX)
-    float* S;
-    float* stats;          // [B, H, N] log-sum-exp rows of the register-resident attention path
+    // score stage, [B, H, N, Np]; null where the tower's AttnPath does not read them
+    float* S;              // Unfused: raw scores, f32
+    bf16_t* P;             // Unfused: probabilities (saved for the backward)
+    bf16_t* Rm;            // Mix: mixed probabilities, quad-blocked; Unfused: mixed probabilities (= P without head mixing)
+    float* stats;          // Mix: [B, H, N] log-sum-exp rows
 };
 
 struct Work {
@@ -149,11 +168,14 @@ struct Work {
     // gradients that are wgrad operands keep one slot per repeat: the R executions of a weight-shared block feed ONE
     // wgrad GEMM over R * M rows (half the launches and half the f32 atomic traffic at R = 2)
     bf16_t *gb_f2, *gb_pr;                 // [R][M, D] bf16 residual gradient as seen by fc2 / attn.proj
-    bf16_t *dbig, *dh, *dqkv, *dR, *dS, *dout;   // dbig [R][M, F], dqkv [R][M, 3D]
+    bf16_t *dbig, *dh, *dqkv, *dout;       // dbig [R][M, F], dqkv [R][M, 3D]
+    bf16_t* dR;                            // Unfused: [B, H, N, Np] gradient of the mixed probabilities
+    bf16_t* dS;                            // [B, H, N, Np] gradient of the scaled pre-mix scores (Mix: quad-blocked)
     float* tok_sum; float* demb;           // [N, D] ; compressed: [M, rank] f32
-    float* wg_dummy;                       // [2, H, H] sink for conv_l / conv_w gradients when those parameters are frozen
-    float* mix_ws; size_t mix_ws_bytes;    // per-workgroup weight-gradient partials of dclip_attn_mix_bwd
+    float* wg_dummy;                       // Mix: [2, H, H] sink for conv_l / conv_w gradients when those parameters are frozen
+    float* mix_ws; size_t mix_ws_bytes;    // Mix: per-workgroup weight-gradient partials of dclip_attn_mix_bwd
     void* tn_ws; size_t tn_ws_bytes;       // partial tiles of the 256 x 256 wgrad launches (dclip_gemm_tn_acc)
+    AttnPath path;                         // the score stage every buffer above was sized for
     size_t bytes;
 };
 
@@ -164,6 +186,15 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
     const int64_t M = B * N, D = p.D, F = p.F, SN = B * p.H * N * Npad;
     const int nex = p.L * p.R;
     const bool save = p.train && training;
+    w.path = attn_path(p, save);
+    const bool mix = w.path == AttnPath::Mix, unfused = w.path == AttnPath::Unfused;
+    // score buffers are reserved only on the paths that read them; the others stay null (see ExecSave)
+    auto take_scores = [&](ExecSave& s) {
+        s.S = unfused ? b.take<float>(SN) : nullptr;
+        s.P = unfused ? b.take<bf16_t>(SN) : nullptr;
+        s.Rm = p.mixing ? b.take<bf16_t>(SN) : s.P;
+        s.stats = mix ? b.take<float>(B * p.H * N) : nullptr;
+    };
     w.X.assign(nex + 1, nullptr);
     w.ex.assign(nex, ExecSave{});
     // teacher / inference: a single ping-pong set reused by every block
@@ -174,9 +205,7 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         xs = w.h16 ? (void*)b.take<_Float16>(M * D) : (void*)b.take<float>(M * D);
         shared.x_mid = xs;   // in-place residual stream
         shared.h1 = b.take<bf16_t>(M * D); shared.qkv = b.take<bf16_t>(M * 3 * D);
-        shared.S = b.take<float>(SN); shared.P = (p.student && p.c.head_mix) ? b.take<bf16_t>(SN) : nullptr;
-        shared.Rm = b.take<bf16_t>(SN);
-        shared.stats = b.take<float>(B * p.H * N);
+        take_scores(shared);
         shared.ctx = b.take<bf16_t>(M * D); shared.h2 = shared.h1; shared.z = nullptr; shared.u = b.take<bf16_t>(M * F);
         shared.mean1 = shared.rstd1 = shared.mean2 = shared.rstd2 = nullptr;
     }
@@ -187,8 +216,7 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         s.x_mid = b.take<float>(M * D);
         s.mean1 = b.take<float>(M); s.rstd1 = b.take<float>(M); s.mean2 = b.take<float>(M); s.rstd2 = b.take<float>(M);
         s.qkv = b.take<bf16_t>(M * 3 * D);
-        s.S = b.take<float>(SN); s.P = b.take<bf16_t>(SN); s.Rm = p.c.head_mix ? b.take<bf16_t>(SN) : s.P;
-        s.stats = b.take<float>(B * p.H * N);
+        take_scores(s);
         s.z = b.take<uint8_t>(M * F);
         if (e % p.R == 0) {
             // the wgrad operands (inputs of the four linears) of a block's R executions lie back to back: [R][M, .]
@@ -212,10 +240,10 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         w.G = b.take<float>(M * D); w.Gb = b.take<bf16_t>(M * D);
         w.gb_f2 = b.take<bf16_t>(p.R * M * D); w.gb_pr = b.take<bf16_t>(p.R * M * D);
         w.dbig = b.take<bf16_t>(p.R * M * F); w.dh = b.take<bf16_t>(M * D); w.dqkv = b.take<bf16_t>(p.R * M * 3 * D);
-        w.dR = b.take<bf16_t>(SN); w.dS = b.take<bf16_t>(SN); w.dout = b.take<bf16_t>(B * p.E);
+        w.dR = unfused ? b.take<bf16_t>(SN) : nullptr; w.dS = b.take<bf16_t>(SN); w.dout = b.take<bf16_t>(B * p.E);
         w.tok_sum = b.take<float>((int64_t)N * D);
-        w.wg_dummy = b.take<float>(2 * p.H * p.H);
-        w.mix_ws_bytes = p.c.head_mix ? dclip_attn_mix_bwd_workspace_bytes(B, p.H, N) : 0;
+        w.wg_dummy = mix ? b.take<float>(2 * p.H * p.H) : nullptr;
+        w.mix_ws_bytes = mix ? dclip_attn_mix_bwd_workspace_bytes(B, p.H, N) : 0;
         w.mix_ws = w.mix_ws_bytes ? (float*)b.take<char>(w.mix_ws_bytes) : nullptr;
         w.tn_ws_bytes = dclip_gemm_tn_workspace_bytes();
         w.tn_ws = b.take<char>(w.tn_ws_bytes);
@@ -228,14 +256,6 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
 }
 
 inline const float* PF(const void* const* params, int i) { return (const float*)params[i]; }
-
-// Head-mixing students whose shape has an instantiation of the register-resident score stage (attention_mix.hip: both head mixes
-// on the matrix pipe) keep S, A, P, dR out of HBM; forward and backward must agree (the backward recomputes from qkv + the forward's
-// softmax statistics), hence one predicate for both.  DCLIP_ATTN_MIX=0 selects the unfused kernels (attn_nt -> softmax -> ...).
-inline bool mix_attn(const Plan& p, int64_t N) {
-    static const int mode = [] { const char* e = getenv("DCLIP_ATTN_MIX"); return e ? atoi(e) : 1; }();
-    return mode != 0 && p.student && p.c.head_mix && !p.c.causal && dclip_attn_mix_supported(p.H, N, p.hd) != 0;
-}
 
 // split count of the wgrad contraction: minimise  rounds(tiles*s / 512 resident workgroups) * work per workgroup
 //                                                   + atomic traffic (s * P*Q*4 bytes at ~1.3 TB/s, half hidden)
@@ -276,6 +296,39 @@ inline int export_stream(bool h16, const void* src, float* dst, int64_t n, void*
         return DCLIP_ELAUNCH;
     }
     return DCLIP_OK;
+}
+
+// The score stage of one block execution, on the path its workspace was laid out for: ctx = attention(qkv).
+// wl / ww: the execution's conv_l / conv_w weights (head-mixing students), else null.
+int attn_forward(AttnPath path, const Plan& p, const ExecSave& s, const float* wl, const float* ww, int64_t B, int64_t N, void* st) {
+    const int64_t D = p.D, H = p.H, hd = p.hd, Np = (N + 7) & ~(int64_t)7;
+    const float scale = 1.f / sqrtf((float)hd);
+    if (path == AttnPath::Fused) return dclip_attn_fused_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, p.c.causal, st);
+    if (path == AttnPath::Mix) {
+        CK(dclip_attn_mix_fwd(s.qkv, 3 * D, wl, ww, s.Rm, s.stats, B, H, N, Np, hd, scale, st));
+        return dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 1, st);
+    }
+    CK(dclip_attn_nt(s.qkv, 3 * D, s.qkv + D, 3 * D, s.S, 1, B, H, N, Np, hd, scale, st));
+    CK(dclip_attn_softmax_fwd(s.S, wl, ww, wl ? s.P : nullptr, s.Rm, B, H, N, Np, p.c.causal, st));
+    return dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 0, st);
+}
+
+// Its backward (Mix or Unfused): dqkv from dctx = dO.  gl / gw: the conv_l / conv_w gradients (+=), null when frozen.
+int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w, const float* wl, const float* ww, float* gl, float* gw,
+                  const bf16_t* dctx, bf16_t* dqkv, int64_t B, void* st) {
+    const int64_t D = p.D, H = p.H, hd = p.hd, N = p.N, Np = p.Np;
+    const float scale = 1.f / sqrtf((float)hd);
+    const int blk = path == AttnPath::Mix ? 1 : 0;                // R and dS of the register-resident score stage are quad-blocked
+    CK(dclip_attn_tn(s.Rm, dctx, D, dqkv + 2 * D, 3 * D, B, H, N, Np, hd, 1.f, blk, st));                    // dV = R^T dO
+    if (path == AttnPath::Mix) {
+        CK(dclip_attn_mix_bwd(s.qkv, 3 * D, dctx, D, wl, ww, s.stats, w.dS, gl ? gl : w.wg_dummy, gw ? gw : w.wg_dummy + H * H,
+                              w.mix_ws, w.mix_ws_bytes, B, H, N, Np, hd, scale, st));
+    } else {
+        CK(dclip_attn_nt(dctx, D, s.qkv + 2 * D, 3 * D, w.dR, 0, B, H, N, Np, hd, 1.f, st));               // dR = dO V^T
+        CK(dclip_attn_softmax_bwd(w.dR, s.P, s.S, 0, wl, ww, w.dS, gl, gw, B, H, N, Np, st));
+    }
+    CK(dclip_attn_nn(w.dS, s.qkv + D, 3 * D, dqkv, 3 * D, B, H, N, Np, hd, scale, blk, st));                 // dQ = dS K
+    return dclip_attn_tn(w.dS, s.qkv, 3 * D, dqkv + D, 3 * D, B, H, N, Np, hd, scale, blk, st);              // dK = dS^T Q
 }
 
 }  // namespace
@@ -397,8 +450,7 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
     DCLIP_REQUIRE(ws_bytes >= w.bytes, "dclip_encoder_forward: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
     DCLIP_REQUIRE(((uintptr_t)workspace % 256) == 0 && ((uintptr_t)wcache % 256) == 0, "dclip_encoder_forward: buffers must be 256-byte aligned");
     const bf16_t* W = (const bf16_t*)wcache;
-    const int64_t N = tokens_eff ? tokens_eff : p.N, D = p.D, F = p.F, E = p.E, M = B * N, H = p.H, hd = p.hd, Np = (N + 7) & ~(int64_t)7;
-    const float scale = 1.f / sqrtf((float)hd);
+    const int64_t N = tokens_eff ? tokens_eff : p.N, D = p.D, F = p.F, E = p.E, M = B * N;
     const int nex = p.L * p.R;
 
     // ---- embedding -----------------------------------------------------------------------------------------
@@ -436,26 +488,14 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
             const BX bx = bexec(p, l, r);
             n1w = PF(params, bx.n1w); n1b = PF(params, bx.n1b); n2w = PF(params, bx.n2w); n2b = PF(params, bx.n2b);
             bq = PF(params, bx.qkvb); bp = PF(params, bx.prb); b1 = PF(params, bx.f1b); b2 = PF(params, bx.f2b);
-            if (p.student && p.c.head_mix) { wl = PF(params, bx.cl); ww = PF(params, bx.cw); }
+            if (p.mixing) { wl = PF(params, bx.cl); ww = PF(params, bx.cw); }
         }
         void* xin = w.X[ei];
         void* xout = w.X[ei + 1];
         const int sdt = w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;        // dtype of the residual stream
         CK(ln_stream(w.h16, xin, D, nullptr, n1w, n1b, s.h1, D, DCLIP_OUT_BF16, s.mean1, s.rstd1, M, D, st));
         CK(gemm(s.h1, D, W + bw.qkv, D, s.qkv, 3 * D, M, 3 * D, D, bq, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
-        if (!training && !wl) {
-            // inference without head mixing (the frozen teacher): one fused kernel, no score tensors in HBM
-            CK(dclip_attn_fused_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, p.c.causal, st));
-        } else {
-            if (wl && mix_attn(p, N)) {
-                CK(dclip_attn_mix_fwd(s.qkv, 3 * D, wl, ww, s.Rm, s.stats, B, H, N, Np, hd, scale, st));
-                CK(dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 1, st));
-            } else {
-                CK(dclip_attn_nt(s.qkv, 3 * D, s.qkv + D, 3 * D, s.S, 1, B, H, N, Np, hd, scale, st));
-                CK(dclip_attn_softmax_fwd(s.S, wl, ww, wl ? s.P : nullptr, s.Rm, B, H, N, Np, p.c.causal, st));
-                CK(dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 0, st));
-            }
-        }
+        CK(attn_forward(w.path, p, s, wl, ww, B, N, st));
         CK(gemm(s.ctx, D, W + bw.proj, D, s.x_mid, D, M, D, D, bp, 0, nullptr, nullptr, xin, D, sdt, 0, nullptr, st));
         CK(ln_stream(w.h16, s.x_mid, D, nullptr, n2w, n2b, s.h2, D, DCLIP_OUT_BF16, s.mean2, s.rstd2, M, D, st));
         CK(gemm(s.h2, D, W + bw.fc1, D, s.u, F, M, F, D, b1, p.student ? (s.z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (s.z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU), nullptr, s.z, nullptr, 0, 0, 0, nullptr, st));
@@ -526,8 +566,7 @@ static int encoder_backward_impl(const dclip_encoder* e, const void* input, cons
     layout(p, B, true, workspace, w);
     DCLIP_REQUIRE(ws_bytes >= w.bytes, "dclip_encoder_backward: workspace too small");
     const bf16_t* W = (const bf16_t*)wcache;
-    const int64_t N = p.N, D = p.D, F = p.F, E = p.E, M = B * N, H = p.H, hd = p.hd, Np = p.Np;
-    const float scale = 1.f / sqrtf((float)hd);
+    const int64_t N = p.N, D = p.D, F = p.F, E = p.E, M = B * N;
     const int nex = p.L * p.R;
     auto GR = [&](int i) -> float* { return (float*)grads[i]; };
     hipStream_t hs = (hipStream_t)st;
@@ -564,7 +603,8 @@ static int encoder_backward_impl(const dclip_encoder* e, const void* input, cons
         const ExecSave& s = w.ex[ei];
         const BX bx = bexec(p, l, r);
         const float *wl = nullptr, *ww = nullptr;
-        if (p.student && p.c.head_mix) { wl = PF(params, bx.cl); ww = PF(params, bx.cw); }
+        float *gl = nullptr, *gw = nullptr;
+        if (p.mixing) { wl = PF(params, bx.cl); ww = PF(params, bx.cw); gl = GR(bx.cl); gw = GR(bx.cw); }
         // this execution's slots; a block's wgrads run once, after its first execution's gradients are there (r == 0)
         bf16_t* gb_f2 = w.gb_f2 + (int64_t)r * M * D;
         bf16_t* gb_pr = w.gb_pr + (int64_t)r * M * D;
@@ -586,19 +626,7 @@ static int encoder_backward_impl(const dclip_encoder* e, const void* input, cons
         if (r == 0 && GR(bx.prw)) CK(dclip_gemm_tn_acc(w.gb_pr, D, s0.ctx, D, GR(bx.prw), D, MR, D, D, wsplits(MR, D, D), w.tn_ws, w.tn_ws_bytes, st));
         bf16_t* dctx = w.dh;
         CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx, D, M, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
-        const int blk = (wl && mix_attn(p, N)) ? 1 : 0;        // R and dS of the register-resident score stage are quad-blocked
-        CK(dclip_attn_tn(s.Rm, dctx, D, dqkv + 2 * D, 3 * D, B, H, N, Np, hd, 1.f, blk, st));                    // dV = R^T dO
-        if (wl && mix_attn(p, N)) {
-            float* gl = GR(bx.cl) ? GR(bx.cl) : w.wg_dummy;
-            float* gw = GR(bx.cw) ? GR(bx.cw) : w.wg_dummy + H * H;
-            CK(dclip_attn_mix_bwd(s.qkv, 3 * D, dctx, D, wl, ww, s.stats, w.dS, gl, gw, w.mix_ws, w.mix_ws_bytes, B, H, N, Np, hd, scale, st));
-        } else {
-            CK(dclip_attn_nt(dctx, D, s.qkv + 2 * D, 3 * D, w.dR, 0, B, H, N, Np, hd, 1.f, st));               // dR = dO V^T
-            CK(dclip_attn_softmax_bwd(w.dR, s.P, s.S, 0, wl, ww, w.dS, wl ? GR(bx.cl) : nullptr,
-                                      wl ? GR(bx.cw) : nullptr, B, H, N, Np, st));
-        }
-        CK(dclip_attn_nn(w.dS, s.qkv + D, 3 * D, dqkv, 3 * D, B, H, N, Np, hd, scale, blk, st));                 // dQ = dS K
-        CK(dclip_attn_tn(w.dS, s.qkv, 3 * D, dqkv + D, 3 * D, B, H, N, Np, hd, scale, blk, st));                 // dK = dS^T Q
+        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, st));
         if (r == 0 && GR(bx.qkvw)) CK(dclip_gemm_tn_acc(w.dqkv, 3 * D, s0.h1, D, GR(bx.qkvw), D, MR, 3 * D, D, wsplits(MR, 3 * D, D), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && params[bx.qkvb] && GR(bx.qkvb)) CK(dclip_colsum_acc(w.dqkv, 3 * D, GR(bx.qkvb), MR, 3 * D, st));
         CK(gemm(dqkv, 3 * D, W + bw.qkv_t, 3 * D, w.dh, D, M, D, 3 * D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));

@@ -363,6 +363,7 @@ dclip_encoder* dclip_encoder_create(const dclip_encoder_cfg* cfg);   /* NULL + l
 void dclip_encoder_destroy(dclip_encoder* enc);
 int64_t dclip_encoder_num_params(const dclip_encoder* enc);
 size_t dclip_encoder_wcache_bytes(const dclip_encoder* enc);
+/* the size depends on the tower's attention path (training, head mixing, DCLIP_ATTN_MIX): only the score buffers it reads are reserved */
 size_t dclip_encoder_workspace_bytes(const dclip_encoder* enc, int64_t B, int training);
 /* refresh the bf16 GEMM-weight cache from the f32 parameters (student: every step; teacher: once) */
 int dclip_encoder_prepare(const dclip_encoder* enc, const void* const* params, void* wcache, void* stream);

@@ -98,6 +98,42 @@ def test_encoder_plan_is_host_side():
                                 repeated_times=2, use_transform=True)
 
 
+def test_encoder_workspace_follows_the_attention_path():
+    """The workspace reserves only the score buffers of the tower's attention path (encoder.cpp attn_path).  (a) Inference without
+    head mixing runs the fused kernel: no per-head buffer, so 8 and 16 heads of one width need the same bytes.  (b) The bench image
+    student trains on the register-resident path; DCLIP_ATTN_MIX=0 (read once per process: child processes) moves it to the unfused
+    kernels, which keep f32 scores S and bf16 probabilities P per block execution: at least L*R*6*B*H*N*Np bytes more."""
+    import subprocess
+    import sys
+    from distillclip_amd._lib import lib
+    from distillclip_amd.model.component._tower import EncoderCfg
+    l = lib()
+    teacher = dict(kind=0, modality=0, tokens=50, width=512, layers=2, repeats=1, mlp_dim=2048, out_dim=512, patch=32, resolution=224,
+                   in_chans=3, vocab=0, embed_rank=0, head_mix=0, causal=0)
+    infer = []
+    for heads in (8, 16):
+        h = l.dclip_encoder_create(ctypes.byref(EncoderCfg(heads=heads, **teacher)))
+        infer.append(l.dclip_encoder_workspace_bytes(h, 512, 0))
+        l.dclip_encoder_destroy(h)
+    assert infer[0] == infer[1] > 0, infer
+
+    B, L, R, H, N, Np = 512, 6, 2, 24, 50, 56
+    student = dict(kind=1, modality=0, tokens=N, width=768, heads=H, layers=L, repeats=R, mlp_dim=3072, out_dim=512, patch=32,
+                   resolution=224, in_chans=3, vocab=0, embed_rank=0, head_mix=1, causal=0)
+    prog = ('import ctypes\n'
+            'from distillclip_amd._lib import lib\n'
+            'from distillclip_amd.model.component._tower import EncoderCfg\n'
+            f'h = lib().dclip_encoder_create(ctypes.byref(EncoderCfg(**{student!r})))\n'
+            f'print(lib().dclip_encoder_workspace_bytes(h, {B}, 1))\n')
+    train = {}
+    for mode in ('1', '0'):
+        r = subprocess.run([sys.executable, '-c', prog], env=dict(os.environ, DCLIP_ATTN_MIX=mode), capture_output=True, text=True,
+                           timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        train[mode] = int(r.stdout.strip().splitlines()[-1])
+    assert train['0'] - train['1'] >= L * R * 6 * B * H * N * Np, train
+
+
 def test_state_dict_keys_match_reference_layout():
     from distillclip_amd import synth
     from distillclip_amd.model.component import RepeatVisionTransformer, RepeatTextTransformer, ImageEncoder, TextEncoder
