@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <mutex>
 #include <new>
 #include <vector>
 #include "common.h"
@@ -314,8 +315,10 @@ int attn_forward(AttnPath path, const Plan& p, const ExecSave& s, const float* w
 }
 
 // Its backward (Mix or Unfused): dqkv from dctx = dO.  gl / gw: the conv_l / conv_w gradients (+=), null when frozen.
+// mg: the gradients of this execution's exported head-mean maps (null when it has none), added to dS before dQ / dK are formed.
+struct MapGrad { const float* d_score; const float* d_prob; void* scratch; size_t scratch_bytes; };
 int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w, const float* wl, const float* ww, float* gl, float* gw,
-                  const bf16_t* dctx, bf16_t* dqkv, int64_t B, void* st) {
+                  const bf16_t* dctx, bf16_t* dqkv, int64_t B, const MapGrad* mg, void* st) {
     const int64_t D = p.D, H = p.H, hd = p.hd, N = p.N, Np = p.Np;
     const float scale = 1.f / sqrtf((float)hd);
     const int blk = path == AttnPath::Mix ? 1 : 0;                // R and dS of the register-resident score stage are quad-blocked
@@ -327,6 +330,8 @@ int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w
         CK(dclip_attn_nt(dctx, D, s.qkv + 2 * D, 3 * D, w.dR, 0, B, H, N, Np, hd, 1.f, st));               // dR = dO V^T
         CK(dclip_attn_softmax_bwd(w.dR, s.P, s.S, 0, wl, ww, w.dS, gl, gw, B, H, N, Np, st));
     }
+    if (mg) CK(dclip_attn_maps_bwd(s.qkv, 3 * D, wl, mg->d_score, mg->d_prob, w.dS, blk, gl, mg->scratch, mg->scratch_bytes, B, H, N, Np, hd,
+                                   scale, p.c.causal, st));
     CK(dclip_attn_nn(w.dS, s.qkv + D, 3 * D, dqkv, 3 * D, B, H, N, Np, hd, scale, blk, st));                 // dQ = dS K
     return dclip_attn_tn(w.dS, s.qkv, 3 * D, dqkv + D, 3 * D, B, H, N, Np, hd, scale, blk, st);              // dK = dS^T Q
 }
@@ -337,7 +342,15 @@ int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w
 // the most recent training forward of this handle left cleared — the only mutable word of the handle.  dclip_encoder_backward
 // consumes it; a backward that does not find its workspace there (a second backward on one forward, a retry after a failed one,
 // another workspace in between) clears the seeds itself, so the call is self-contained whatever the caller does.
-struct dclip_encoder { Plan p; mutable std::atomic<void*> seeded{nullptr}; };
+// exported: which head-mean maps (bit 0 score, bit 1 probabilities, per block execution) the most recent training forward of the workspace
+// `exported_ws` wrote; the backward accepts map gradients for those only.
+struct dclip_encoder {
+    Plan p;
+    mutable std::atomic<void*> seeded{nullptr};
+    mutable std::mutex maps_mu;
+    mutable void* exported_ws = nullptr;
+    mutable std::vector<uint8_t> exported;
+};
 
 extern "C" dclip_encoder* dclip_encoder_create(const dclip_encoder_cfg* cfg) {
     if (!cfg) { dclip_set_error("dclip_encoder_create: null cfg"); return nullptr; }
@@ -435,7 +448,7 @@ static int clear_backward_seeds(const Plan& p, const Work& w, int64_t M, void* s
 static int encoder_forward_impl(const dclip_encoder* e, const void* input, const bf16_t* ext_patches, int64_t B, const void* const* params,
                                 const void* wcache, void* workspace, size_t ws_bytes, int training,
                                 float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
-                                void* st) {
+                                const dclip_attn_maps* maps, void* st) {
     DCLIP_REQUIRE(e && (input || ext_patches) && params && wcache && workspace && last_representation, "dclip_encoder_forward: null argument");
     DCLIP_REQUIRE(B > 0, "dclip_encoder_forward: empty batch");
     const Plan& p = e->p;
@@ -445,6 +458,21 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
     // attention; LN / MLP are per token), so the tower may run on the first tokens_eff positions with identical output.
     DCLIP_REQUIRE(tokens_eff == 0 || (!p.train && !p.image && p.c.causal && tokens_eff > 0 && tokens_eff <= p.N && !rep_out && !emb_out),
                   "dclip_encoder_forward: tokens_eff is only valid for the causal text teacher without hidden-state export");
+    // head-mean attention maps per block execution (bit 0 score, bit 1 probabilities)
+    std::vector<float*> map_s(p.L * p.R, nullptr), map_p(p.L * p.R, nullptr);
+    std::vector<uint8_t> mapped(p.L * p.R, 0);
+    if (maps && maps->n) {
+        DCLIP_REQUIRE(maps->n > 0 && maps->exec, "dclip_encoder_forward: maps need n > 0 execution indices");
+        DCLIP_REQUIRE(tokens_eff == 0, "dclip_encoder_forward: attention maps cannot be exported from a caption prefix (tokens_eff)");
+        for (int k = 0; k < maps->n; ++k) {
+            const int ei = maps->exec[k];
+            DCLIP_REQUIRE(ei >= 0 && ei < p.L * p.R, "dclip_encoder_forward: map %d: block execution %d out of range 0..%d", k, ei, p.L * p.R - 1);
+            float* sm = maps->score ? maps->score[k] : nullptr;
+            float* pm = maps->prob ? maps->prob[k] : nullptr;
+            if (sm) { map_s[ei] = sm; mapped[ei] |= 1; }
+            if (pm) { map_p[ei] = pm; mapped[ei] |= 2; }
+        }
+    }
     Work w;
     layout(p, B, training != 0, workspace, w, tokens_eff);
     DCLIP_REQUIRE(ws_bytes >= w.bytes, "dclip_encoder_forward: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
@@ -496,6 +524,8 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
         CK(ln_stream(w.h16, xin, D, nullptr, n1w, n1b, s.h1, D, DCLIP_OUT_BF16, s.mean1, s.rstd1, M, D, st));
         CK(gemm(s.h1, D, W + bw.qkv, D, s.qkv, 3 * D, M, 3 * D, D, bq, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
         CK(attn_forward(w.path, p, s, wl, ww, B, N, st));
+        // before the next execution reuses the inference set's qkv
+        if (mapped[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, wl, map_s[ei], map_p[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
         CK(gemm(s.ctx, D, W + bw.proj, D, s.x_mid, D, M, D, D, bp, 0, nullptr, nullptr, xin, D, sdt, 0, nullptr, st));
         CK(ln_stream(w.h16, s.x_mid, D, nullptr, n2w, n2b, s.h2, D, DCLIP_OUT_BF16, s.mean2, s.rstd2, M, D, st));
         CK(gemm(s.h2, D, W + bw.fc1, D, s.u, F, M, F, D, b1, p.student ? (s.z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (s.z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU), nullptr, s.z, nullptr, 0, 0, 0, nullptr, st));
@@ -512,25 +542,44 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
     if (training) {
         CK(clear_backward_seeds(p, w, M, st));
         e->seeded.store(workspace, std::memory_order_release);
+        std::lock_guard<std::mutex> lk(e->maps_mu);
+        e->exported_ws = workspace;
+        e->exported = mapped;
     }
     return DCLIP_OK;
+}
+
+extern "C" int dclip_encoder_forward_ex(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
+                                        const void* wcache, void* workspace, size_t ws_bytes, int training,
+                                        float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
+                                        const dclip_attn_maps* maps, void* st) {
+    DCLIP_REQUIRE(input, "dclip_encoder_forward: null argument");
+    return encoder_forward_impl(e, input, nullptr, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out, emb_out,
+                                tokens_eff, maps, st);
 }
 
 extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
                                      const void* wcache, void* workspace, size_t ws_bytes, int training,
                                      float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
                                      void* st) {
-    DCLIP_REQUIRE(input, "dclip_encoder_forward: null argument");
-    return encoder_forward_impl(e, input, nullptr, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out, emb_out,
-                                tokens_eff, st);
+    return dclip_encoder_forward_ex(e, input, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out, emb_out,
+                                    tokens_eff, nullptr, st);
+}
+
+extern "C" int dclip_encoder_forward_patches_ex(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
+                                                const void* wcache, void* workspace, size_t ws_bytes, int training,
+                                                float* last_representation, float* const* rep_out, float* emb_out,
+                                                const dclip_attn_maps* maps, void* st) {
+    DCLIP_REQUIRE(patches, "dclip_encoder_forward_patches: null argument");
+    return encoder_forward_impl(e, nullptr, (const bf16_t*)patches, B, params, wcache, workspace, ws_bytes, training, last_representation,
+                                rep_out, emb_out, 0, maps, st);
 }
 
 extern "C" int dclip_encoder_forward_patches(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
                                              const void* wcache, void* workspace, size_t ws_bytes, int training,
                                              float* last_representation, float* const* rep_out, float* emb_out, void* st) {
-    DCLIP_REQUIRE(patches, "dclip_encoder_forward_patches: null argument");
-    return encoder_forward_impl(e, nullptr, (const bf16_t*)patches, B, params, wcache, workspace, ws_bytes, training, last_representation,
-                                rep_out, emb_out, 0, st);
+    return dclip_encoder_forward_patches_ex(e, patches, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out,
+                                            emb_out, nullptr, st);
 }
 
 // All-token output of the final norm + projection (reference _common.py:210-215, text_encoder.py:69-72,
@@ -557,11 +606,38 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
 static int encoder_backward_impl(const dclip_encoder* e, const void* input, const bf16_t* ext_patches, int64_t B, const void* const* params,
                                  void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
                                  const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                 dclip_bucket_cb on_bucket, void* cb_user, void* st) {
+                                 const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
     DCLIP_REQUIRE(e && (input || ext_patches) && params && grads && wcache && workspace && d_last_representation, "dclip_encoder_backward: null argument");
     const Plan& p = e->p;
     DCLIP_REQUIRE(!ext_patches || p.image, "dclip_encoder_backward_patches: image towers only");
     DCLIP_REQUIRE(p.train, "dclip_encoder_backward: the frozen teacher tower (kind 0) has no backward");
+    // gradients of exported head-mean maps, per block execution
+    std::vector<MapGrad> mgrad(p.L * p.R, MapGrad{nullptr, nullptr, nullptr, 0});
+    std::vector<uint8_t> has_mg(p.L * p.R, 0);
+    if (maps && maps->n) {
+        DCLIP_REQUIRE(maps->n > 0 && maps->exec, "dclip_encoder_backward: maps need n > 0 execution indices");
+        std::lock_guard<std::mutex> lk(e->maps_mu);
+        for (int k = 0; k < maps->n; ++k) {
+            const int ei = maps->exec[k];
+            DCLIP_REQUIRE(ei >= 0 && ei < p.L * p.R, "dclip_encoder_backward: map %d: block execution %d out of range 0..%d", k, ei, p.L * p.R - 1);
+            const float* gs = maps->d_score ? maps->d_score[k] : nullptr;
+            const float* gp = maps->d_prob ? maps->d_prob[k] : nullptr;
+            const uint8_t had = e->exported_ws == workspace && (size_t)ei < e->exported.size() ? e->exported[ei] : 0;
+            DCLIP_REQUIRE((!gs || (had & 1)) && (!gp || (had & 2)),
+                          "dclip_encoder_backward: a gradient for the %s map of block execution %d, which the forward did not export",
+                          gs && !(had & 1) ? "score" : "probability", ei);
+            if (gs) mgrad[ei].d_score = gs;
+            if (gp) mgrad[ei].d_prob = gp;
+            if (gs || gp) has_mg[ei] = 1;
+        }
+        if (p.mixing) {
+            const size_t need = dclip_attn_maps_bwd_workspace_bytes(B, p.H, p.N);
+            for (int ei = 0; ei < p.L * p.R; ++ei)
+                DCLIP_REQUIRE(!mgrad[ei].d_prob || (maps->scratch && maps->scratch_bytes >= need),
+                              "dclip_encoder_backward: probability-map gradients of a head-mixing tower need %zu bytes of maps scratch", need);
+        }
+        for (auto& g : mgrad) { g.scratch = maps->scratch; g.scratch_bytes = maps->scratch_bytes; }
+    }
     Work w;
     layout(p, B, true, workspace, w);
     DCLIP_REQUIRE(ws_bytes >= w.bytes, "dclip_encoder_backward: workspace too small");
@@ -626,7 +702,7 @@ static int encoder_backward_impl(const dclip_encoder* e, const void* input, cons
         if (r == 0 && GR(bx.prw)) CK(dclip_gemm_tn_acc(w.gb_pr, D, s0.ctx, D, GR(bx.prw), D, MR, D, D, wsplits(MR, D, D), w.tn_ws, w.tn_ws_bytes, st));
         bf16_t* dctx = w.dh;
         CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx, D, M, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
-        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, st));
+        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, has_mg[ei] ? &mgrad[ei] : nullptr, st));
         if (r == 0 && GR(bx.qkvw)) CK(dclip_gemm_tn_acc(w.dqkv, 3 * D, s0.h1, D, GR(bx.qkvw), D, MR, 3 * D, D, wsplits(MR, 3 * D, D), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && params[bx.qkvb] && GR(bx.qkvb)) CK(dclip_colsum_acc(w.dqkv, 3 * D, GR(bx.qkvb), MR, 3 * D, st));
         CK(gemm(dqkv, 3 * D, W + bw.qkv_t, 3 * D, w.dh, D, M, D, 3 * D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
@@ -681,22 +757,38 @@ static int encoder_backward_impl(const dclip_encoder* e, const void* input, cons
     return DCLIP_OK;
 }
 
+extern "C" int dclip_encoder_backward_ex(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
+                                         void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                                         const float* d_last_representation, const float* const* d_rep, const float* d_emb,
+                                         const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
+    DCLIP_REQUIRE(input, "dclip_encoder_backward: null argument");
+    return encoder_backward_impl(e, input, nullptr, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb,
+                                 maps, on_bucket, cb_user, st);
+}
+
 extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
                                       void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
                                       const float* d_last_representation, const float* const* d_rep, const float* d_emb,
                                       dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    DCLIP_REQUIRE(input, "dclip_encoder_backward: null argument");
-    return encoder_backward_impl(e, input, nullptr, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb,
-                                 on_bucket, cb_user, st);
+    return dclip_encoder_backward_ex(e, input, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb, nullptr,
+                                     on_bucket, cb_user, st);
+}
+
+extern "C" int dclip_encoder_backward_patches_ex(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
+                                                 void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                                                 const float* d_last_representation, const float* const* d_rep, const float* d_emb,
+                                                 const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
+    DCLIP_REQUIRE(patches, "dclip_encoder_backward_patches: null argument");
+    return encoder_backward_impl(e, nullptr, (const bf16_t*)patches, B, params, grads, wcache, workspace, ws_bytes, d_last_representation,
+                                 d_rep, d_emb, maps, on_bucket, cb_user, st);
 }
 
 extern "C" int dclip_encoder_backward_patches(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
                                               void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
                                               const float* d_last_representation, const float* const* d_rep, const float* d_emb,
                                               dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    DCLIP_REQUIRE(patches, "dclip_encoder_backward_patches: null argument");
-    return encoder_backward_impl(e, nullptr, (const bf16_t*)patches, B, params, grads, wcache, workspace, ws_bytes, d_last_representation,
-                                 d_rep, d_emb, on_bucket, cb_user, st);
+    return dclip_encoder_backward_patches_ex(e, patches, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb,
+                                             nullptr, on_bucket, cb_user, st);
 }
 
 // Gradient buckets in the order the backward completes them (data-parallel exchange, SURVEY.md section 8e Collective 1):

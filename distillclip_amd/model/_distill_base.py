@@ -44,6 +44,17 @@ def freeze_image_embedding(enc, teacher_state, prefix):
             p.requires_grad = False
 
 
+def pair_attention_maps(student, teacher):
+    """The attention losses pair student and teacher maps with zip() (attention_score_mse.py, attention_probs_mse.py): tell each tower how
+    many maps the other exports, so that neither computes maps zip would drop.  The student still reports its full execution count
+    (ExportedMaps.executions), the losses' divisor."""
+    cfg = student._tower.cfg
+    need = teacher.need_layers
+    t_maps = teacher.layers if need is None else len({int(i) for i in need if 0 <= int(i) < teacher.layers})
+    student.attn_map_pairs = t_maps
+    teacher.attn_map_pairs = cfg.layers * cfg.repeats
+
+
 class DistillBase(nn.Module):
     def towers(self):
         """the student towers (HipTower), in the order the optimizer and the gradient exchange see them"""

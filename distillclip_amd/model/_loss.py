@@ -15,9 +15,8 @@ from .. import ops
 IMAGE_TEXT_LOSS = ['hard_label', 'soft_label', 'logits_mse', 'fine_grain', 'cos_diff']     # reference _loss.py:14
 _TOWER_FUSED = ('out_l1', 'out_cos', 'out_kl', 'out_ce')
 _CROSS_FUSED = ('cos_diff', 'hard_label', 'soft_label', 'logits_mse')
-_FEATURE = ('hidden_rep_mse', 'embedding_mse')
-_KNOWN_UNSUPPORTED = ('attention_score_mse', 'attention_probs_mse', 'attention_probs_kl', 'last_value_map_kl', 'vit_kd',
-                      'fine_grain', 'smd')
+_FEATURE = ('hidden_rep_mse', 'embedding_mse', 'attention_score_mse', 'attention_probs_mse')
+_KNOWN_UNSUPPORTED = ('attention_probs_kl', 'last_value_map_kl', 'vit_kd', 'fine_grain', 'smd')
 _SLOT_TOWER = {'out_l1': 1, 'out_cos': 2, 'out_kl': 3, 'out_ce': 4}
 _SLOT_CROSS = {'cos_diff': 9, 'hard_label': 10, 'soft_label': 11, 'logits_mse': 12}
 
@@ -97,6 +96,20 @@ class _FeatureMSEFn(torch.autograd.Function):
         return ds * g, None
 
 
+def _map_mse(s, t):
+    """_FeatureMSEFn on one pair of head-mean maps [B, 1, N, N]: dclip_feature_mse reads 4 elements at a time, so an element count that is
+    not a multiple of 4 (odd N at odd B) is zero-padded and the mean rescaled to the true count"""
+    if s.shape != t.shape:
+        raise RuntimeError(f'The size of tensor a {tuple(s.shape)} must match the size of tensor b {tuple(t.shape)}')
+    n = s.numel()
+    pad = -n % 4
+    if not pad:
+        return _FeatureMSEFn.apply(s, t)
+    s = torch.nn.functional.pad(s.reshape(-1), (0, pad))
+    t = torch.nn.functional.pad(t.detach().reshape(-1), (0, pad))
+    return _FeatureMSEFn.apply(s, t) * ((n + pad) / n)
+
+
 class LossCalculator(nn.Module):
     def __init__(self, loss_name: List, loss_scale: dict = None, temperature=None, percent=None, smd_tau: float = 0.04,
                  vit_kd_para: Dict = None):
@@ -132,7 +145,9 @@ class LossCalculator(nn.Module):
 
     def get_control_output(self):
         # reference :100-116
-        return ControlOutput(need_emb='embedding_mse' in self.loss_name, need_rep='hidden_rep_mse' in self.loss_name)
+        return ControlOutput(need_emb='embedding_mse' in self.loss_name, need_rep='hidden_rep_mse' in self.loss_name,
+                             need_attn_score='attention_score_mse' in self.loss_name,
+                             need_attn_prob='attention_probs_mse' in self.loss_name)
 
     def _feature_terms(self, stu, tea):
         """-> (weighted sum, {name: scaled value}) of the hidden-state / embedding MSE terms of one tower"""
@@ -144,6 +159,13 @@ class LossCalculator(nn.Module):
                 val = val / max(len(stu.representations), 1)
             elif n == 'embedding_mse':
                 val = _FeatureMSEFn.apply(stu.embedding, tea.embedding)
+            elif n in ('attention_score_mse', 'attention_probs_mse'):
+                # attention_score_mse.py / attention_probs_mse.py: MSE of the head means per zip() pair, divided by the number of STUDENT
+                # maps; the towers export the head means themselves ([B, 1, N, N]) and, inside a distillation model, only the paired
+                # student maps — ExportedMaps.executions keeps the full count
+                sm, tm = (stu.attention_scores, tea.attention_scores) if n == 'attention_score_mse' else (stu.attention_probs, tea.attention_probs)
+                val = sum(_map_mse(s, t) for s, t in zip(sm, tm))
+                val = val / max(getattr(sm, 'executions', len(sm)), 1)
             else:
                 continue
             res[n] = val * self.loss_scale[n]

@@ -21,6 +21,32 @@ class EncoderCfg(ctypes.Structure):
 _BUCKET_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int32)      # include/dclip.h: dclip_bucket_cb
 
 
+class AttnMapsDesc(ctypes.Structure):
+    # include/dclip.h: dclip_attn_maps (host arrays of n entries)
+    _fields_ = [('n', ctypes.c_int32), ('exec', ctypes.c_void_p), ('score', ctypes.c_void_p), ('prob', ctypes.c_void_p),
+                ('d_score', ctypes.c_void_p), ('d_prob', ctypes.c_void_p), ('scratch', ctypes.c_void_p), ('scratch_bytes', ctypes.c_size_t)]
+
+
+class ExportedMaps(list):
+    """head-mean attention maps, [B, 1, N, N] f32 each, of the first block executions a tower exported; `executions` = how many the
+    tower has (layers x repeats).  The reference's attention losses divide by the length of the STUDENT's list, which holds one map per
+    execution (attention_score_mse.py, attention_probs_mse.py): inside a distillation model only the executions `zip` pairs with the
+    teacher are exported, and `executions` keeps that divisor."""
+
+    def __init__(self, maps=(), executions=None):
+        super().__init__(maps)
+        self.executions = len(self) if executions is None else int(executions)
+
+
+def _maps_desc(execs, score=None, prob=None, d_score=None, d_prob=None, scratch=None):
+    """-> (dclip_attn_maps, objects that must stay alive while the call runs)"""
+    ex = (ctypes.c_int32 * len(execs))(*execs)
+    arrs = [None if t is None else _ptr_array(t) for t in (score, prob, d_score, d_prob)]
+    d = AttnMapsDesc(len(execs), ctypes.cast(ex, ctypes.c_void_p), *[None if a is None else ctypes.cast(a, ctypes.c_void_p) for a in arrs],
+                     None if scratch is None else scratch.data_ptr(), 0 if scratch is None else scratch.numel())
+    return d, (ex, arrs, scratch)
+
+
 _SHARE = threading.local()
 
 
@@ -264,8 +290,10 @@ class HipTower:
         self._handle, self.cfg = handle, cfg
 
     # ---- execution -----------------------------------------------------------------------------------------------
-    def forward(self, x, training, need_rep=False, need_emb=False, rep_layers=None, tokens_eff=0):
-        """-> (last_representation [B,E], input as passed to C, hidden states list, embedding or None)"""
+    def forward(self, x, training, need_rep=False, need_emb=False, rep_layers=None, tokens_eff=0, maps=None):
+        """-> (last_representation [B,E], input as passed to C, hidden states list, embedding or None)
+        maps: None, or (need_score, need_prob, block executions): their head-mean attention maps, [B, 1, N, N] f32 each, are a fifth
+        result (scores, probs) — empty lists for the kind not asked for (include/dclip.h: dclip_attn_maps)"""
         if not x.is_cuda:
             raise RuntimeError('distillclip_amd towers need CUDA(HIP) inputs; there is no CPU fallback')
         expect = torch.float32 if self.cfg.modality == 0 else torch.int64
@@ -297,9 +325,29 @@ class HipTower:
             reps = [slots[i] for i in want]
             rep_arr = _ptr_array(slots)
         emb = torch.empty((B, N, D), dtype=torch.float32, device=x.device) if need_emb else None
+        scores, probs, desc = [], [], None
+        if maps is not None:
+            need_s, need_p, execs = maps
+            execs = [int(i) for i in execs]
+            mk = lambda: [torch.empty((B, 1, N, N), dtype=torch.float32, device=x.device) for _ in execs]
+            scores, probs = (mk() if need_s else []), (mk() if need_p else [])
+            if execs and (need_s or need_p):
+                desc = _maps_desc(execs, scores or None, probs or None)
         rows = _shared_rows_for(x, self.cfg) if not tokens_eff else None
         self._patch_rows = rows if training else None      # (kept until the backward: operand of the patch-embedding wgrad)
-        if rows is not None:
+        if desc is not None:
+            st = torch.cuda.current_stream().cuda_stream
+            if rows is not None:
+                lib().dclip_encoder_forward_patches_ex(self._handle, rows.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
+                                                       self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
+                                                       out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(),
+                                                       ctypes.byref(desc[0]), st)
+            else:
+                lib().dclip_encoder_forward_ex(self._handle, x.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
+                                               self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
+                                               out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(), int(tokens_eff),
+                                               ctypes.byref(desc[0]), st)
+        elif rows is not None:
             lib().dclip_encoder_forward_patches(self._handle, rows.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
                                                 self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
                                                 out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(),
@@ -311,6 +359,8 @@ class HipTower:
                                         torch.cuda.current_stream().cuda_stream)
         self._saved_batch = B if training else None
         self._last_fwd = (B, bool(training), int(tokens_eff))
+        if maps is not None:
+            return out, x, reps, emb, (scores, probs)
         return out, x, reps, emb
 
     @torch.no_grad()
@@ -333,8 +383,9 @@ class HipTower:
                                               scratch.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         return out
 
-    def backward(self, x, d_out, d_reps=None, d_emb=None, grad_flat=None):
-        """grad_flat: None = accumulate into p.grad (views of the tower's flat gradient buffer: the product path); a zeroed flat
+    def backward(self, x, d_out, d_reps=None, d_emb=None, grad_flat=None, d_maps=None):
+        """d_maps: None, or (block executions, [d score map] or None, [d probability map] or None) of maps the forward exported.
+        grad_flat: None = accumulate into p.grad (views of the tower's flat gradient buffer: the product path); a zeroed flat
         buffer = write this backward's gradients there and leave p.grad to autograd (_TowerFn hands the views back as the
         gradients of its parameter inputs, so AccumulateGrad hooks — a DistributedDataParallel reducer — see them)."""
         B = x.shape[0]
@@ -374,13 +425,28 @@ class HipTower:
         rows = getattr(self, '_patch_rows', None)
         if rows is not None:
             rows.record_stream(torch.cuda.current_stream())
-        call = lib().dclip_encoder_backward if rows is None else lib().dclip_encoder_backward_patches
-        call(self._handle, x.data_ptr() if rows is None else rows.data_ptr(), B, _ptr_array(ps), _ptr_array(gs), self.wcache.data_ptr(),
-             self.workspace.data_ptr(), self.workspace.numel(), d_out.data_ptr(),
-             _ptr_array(keep) if any(g is not None for g in keep) else None,
-             None if d_emb is None else d_emb.data_ptr(),
-             ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None,
-             torch.cuda.current_stream().cuda_stream)
+        desc = None
+        if d_maps is not None:
+            execs, d_sc, d_pr = d_maps
+            prep = lambda ts: None if not ts or all(t is None for t in ts) else [None if t is None else t.contiguous().float() for t in ts]
+            d_sc, d_pr = prep(d_sc), prep(d_pr)
+            if execs and (d_sc or d_pr):
+                scratch = None
+                if d_pr and self.cfg.head_mix:
+                    nb = lib().dclip_attn_maps_bwd_workspace_bytes(B, self.cfg.heads, self.cfg.tokens)
+                    scratch = torch.empty(nb, dtype=torch.uint8, device=x.device)
+                desc = _maps_desc([int(i) for i in execs], d_score=d_sc, d_prob=d_pr, scratch=scratch)
+        args = (self._handle, x.data_ptr() if rows is None else rows.data_ptr(), B, _ptr_array(ps), _ptr_array(gs), self.wcache.data_ptr(),
+                self.workspace.data_ptr(), self.workspace.numel(), d_out.data_ptr(),
+                _ptr_array(keep) if any(g is not None for g in keep) else None,
+                None if d_emb is None else d_emb.data_ptr())
+        tail = (ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None, torch.cuda.current_stream().cuda_stream)
+        if desc is None:
+            call = lib().dclip_encoder_backward if rows is None else lib().dclip_encoder_backward_patches
+            call(*args, *tail)
+        else:
+            call = lib().dclip_encoder_backward_ex if rows is None else lib().dclip_encoder_backward_patches_ex
+            call(*args, ctypes.byref(desc[0]), *tail)
         if failed:
             raise failed[0]
         self._saved_batch = None
@@ -415,40 +481,59 @@ class _TowerFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, anchor, x, tower, need_rep, need_emb, *params):
-        out, xin, reps, emb = tower.forward(x, training=True, need_rep=need_rep, need_emb=need_emb)
+    def forward(ctx, anchor, x, tower, need_rep, need_emb, maps, *params):
+        res = tower.forward(x, training=True, need_rep=need_rep, need_emb=need_emb, maps=maps)
+        out, xin, reps, emb = res[:4]
+        scores, probs = res[4] if maps is not None else ([], [])
         ctx.tower = tower
         ctx.x = xin
         ctx.n_rep = len(reps)
         ctx.has_emb = emb is not None
+        ctx.maps = maps
+        ctx.n_sc, ctx.n_pr = len(scores), len(probs)
         ctx.n_params = len(params)
-        return (out,) + tuple(reps) + ((emb,) if emb is not None else ())
+        return (out,) + tuple(reps) + ((emb,) if emb is not None else ()) + tuple(scores) + tuple(probs)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, d_out, *rest):
         d_reps = list(rest[:ctx.n_rep])
         d_emb = rest[ctx.n_rep] if ctx.has_emb else None
+        k = ctx.n_rep + (1 if ctx.has_emb else 0)
+        d_maps = None
+        if ctx.maps is not None:
+            d_maps = (ctx.maps[2], list(rest[k:k + ctx.n_sc]), list(rest[k + ctx.n_sc:k + ctx.n_sc + ctx.n_pr]))
         tower = ctx.tower
         if not ctx.n_params:
-            tower.backward(ctx.x, d_out, d_reps, d_emb)
-            return None, None, None, None, None
+            tower.backward(ctx.x, d_out, d_reps, d_emb, d_maps=d_maps)
+            return None, None, None, None, None, None
         # a buffer of its own per backward: autograd may keep the returned views as p.grad (no copy), and the next backward must not
         # write into them
         grad_flat = torch.zeros_like(tower.flat)
-        gs = tower.backward(ctx.x, d_out, d_reps, d_emb, grad_flat=grad_flat)
-        return (None, None, None, None, None) + tuple(g for p, g in zip(tower._params(), gs) if p is not None)
+        gs = tower.backward(ctx.x, d_out, d_reps, d_emb, grad_flat=grad_flat, d_maps=d_maps)
+        return (None, None, None, None, None, None) + tuple(g for p, g in zip(tower._params(), gs) if p is not None)
 
 
 def refuse_attention_maps(co):
-    """the HIP towers keep attention scores / probabilities / value maps on chip: a ControlOutput asking for them is refused"""
-    if co.need_attn_score or co.need_attn_prob or co.need_value_map:
-        raise NotImplementedError('the HIP towers keep attention scores / probabilities / value maps on chip; the loss terms '
-                                  'that need them (attention_*, last_value_map_kl) are outside the hot path (SURVEY.md §2.1)')
+    """the HIP towers export head-mean attention maps only (attention_score_mse / attention_probs_mse read nothing else); per-head value
+    maps stay on chip: a ControlOutput asking for them is refused"""
+    if co.need_value_map:
+        raise NotImplementedError('the HIP towers keep per-head value maps on chip; last_value_map_kl, the loss term that needs them, '
+                                  'is outside the hot path (SURVEY.md §2.1)')
 
 
-def run_tower(tower, x, need_rep=False, need_emb=False):
-    """-> (last_representation, [hidden state per block execution], embedding or None)"""
+def map_request(co, executions, limit=None):
+    """-> the `maps` argument of HipTower.forward for a ControlOutput: None unless it asks for attention scores / probabilities; else the
+    first `limit` (None = all) of `executions`, the block executions whose maps the reference would export"""
+    if not (co.need_attn_score or co.need_attn_prob):
+        return None
+    execs = list(executions)
+    return bool(co.need_attn_score), bool(co.need_attn_prob), execs if limit is None else execs[:max(int(limit), 0)]
+
+
+def run_tower(tower, x, need_rep=False, need_emb=False, maps=None):
+    """-> (last_representation, [hidden state per block execution], embedding or None, score maps, probability maps); the maps are
+    ExportedMaps of the executions `maps` (see map_request) names, empty when maps is None"""
     # a requires-grad scalar that makes the tower's autograd Function part of the graph whatever its other inputs are
     anchor = tower._anchor
     if anchor is None or anchor.device != x.device:
@@ -458,8 +543,16 @@ def run_tower(tower, x, need_rep=False, need_emb=False):
         if autograd_params_mode(tower):
             tower.materialize(x.device)            # the parameters must already be the views of the flat buffer they will stay
             params = tuple(p for p in tower._params() if p is not None)
-        res = _TowerFn.apply(anchor, x, tower, need_rep, need_emb, *params)
+        res = _TowerFn.apply(anchor, x, tower, need_rep, need_emb, maps, *params)
         nex = tower.cfg.layers * tower.cfg.repeats if need_rep else 0
-        return res[0], list(res[1:1 + nex]), (res[1 + nex] if need_emb else None)
-    out, _, reps, emb = tower.forward(x, training=False, need_rep=need_rep, need_emb=need_emb)
-    return out, reps, emb
+        k = 1 + nex + (1 if need_emb else 0)
+        n_sc = len(maps[2]) if maps is not None and maps[0] else 0
+        n_pr = len(maps[2]) if maps is not None and maps[1] else 0
+        scores, probs = list(res[k:k + n_sc]), list(res[k + n_sc:k + n_sc + n_pr])
+        out, reps, emb = res[0], list(res[1:1 + nex]), (res[1 + nex] if need_emb else None)
+    else:
+        res = tower.forward(x, training=False, need_rep=need_rep, need_emb=need_emb, maps=maps)
+        out, reps, emb = res[0], res[2], res[3]
+        scores, probs = res[4] if maps is not None else ([], [])
+    total = tower.cfg.layers * tower.cfg.repeats
+    return out, reps, emb, ExportedMaps(scores, total), ExportedMaps(probs, total)

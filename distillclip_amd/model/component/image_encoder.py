@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from .output import ControlOutput, VisionTransformerOutput
-from ._tower import EncoderCfg, HipTower, refuse_attention_maps, run_tower
+from ._tower import EncoderCfg, HipTower, ExportedMaps, map_request, refuse_attention_maps, run_tower
 from ._proj import HipLinear
 
 
@@ -123,23 +123,32 @@ def encode_clip(enc, x, control_output, output_cls, max_tokens=None):
     if enc.is_student:
         if enc.need_layers is not None and list(enc.need_layers) != list(range(enc.layers)):
             raise NotImplementedError('a trainable CLIP tower exports every layer\'s hidden state (need_layers = all)')
-        out, reps, emb = run_tower(enc._tower, x, co.need_rep, co.need_emb)
+        maps = map_request(co, range(enc.layers), getattr(enc, 'attn_map_pairs', None))
+        out, reps, emb, scores, probs = run_tower(enc._tower, x, co.need_rep, co.need_emb, maps)
         if not enc.no_trans:
             if co.need_rep:
                 reps = [enc.hidden_projection(r) for r in reps]
             if co.need_emb:
                 emb = enc.embedding_projection(emb)
     else:
-        hint = max_tokens if (max_tokens and not co.need_rep and not co.need_emb and not want_all) else 0
+        # attention maps of the need_layers entries (_common.py:158), at most as many as the student's maps pair with
+        layers = sorted({int(i) for i in enc.need_layers if 0 <= int(i) < enc.layers}) if enc.need_layers is not None else range(enc.layers)
+        maps = map_request(co, layers, getattr(enc, 'attn_map_pairs', None))
+        hint = max_tokens if (max_tokens and not co.need_rep and not co.need_emb and not want_all and maps is None) else 0
         with torch.no_grad():
-            out, _, reps, emb = enc._tower.forward(x, training=False, need_rep=co.need_rep, need_emb=co.need_emb,
-                                                   rep_layers=list(enc.need_layers) if enc.need_layers is not None else None,
-                                                   tokens_eff=min(int(hint), enc._tower.cfg.tokens))
+            res = enc._tower.forward(x, training=False, need_rep=co.need_rep, need_emb=co.need_emb,
+                                     rep_layers=list(enc.need_layers) if enc.need_layers is not None else None,
+                                     tokens_eff=min(int(hint), enc._tower.cfg.tokens), maps=maps)
+        out, reps, emb = res[0], res[2], res[3]
+        scores, probs = (ExportedMaps(m, len(layers)) for m in (res[4] if maps is not None else ([], [])))
     llo = enc._tower.last_layer_output() if want_all else None
-    return output_cls(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb)
+    return output_cls(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb,
+                      attention_scores=scores, attention_probs=probs)
 
 
 class ImageEncoder(nn.Module):
+    attn_map_pairs = None       # set by DistillModel / DualDistillModel: how many attention maps `zip` pairs (None = all)
+
     def __init__(self, is_student, vit_paras, tea_transformer_width=None):
         super().__init__()
         vit_paras = dict(vit_paras)

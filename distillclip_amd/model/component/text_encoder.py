@@ -15,6 +15,8 @@ from .image_encoder import ImageEncoder, TeacherTransformer, _LN, teacher_block_
 
 
 class TextEncoder(nn.Module):
+    attn_map_pairs = None       # set by DistillModel / DualDistillModel: how many attention maps `zip` pairs (None = all)
+
     def __init__(self, transformer_width, transformer_layers, transformer_heads, context_length, need_layers, vocab_size,
                  embed_dim, tea_transformer_width=None, is_student=True, drop_out=0., compression_embedding=False,
                  embedding_compression_dim=256):

@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from .output import ControlOutput, VisionTransformerOutput, TextTransformerOutput
-from ._tower import EncoderCfg, HipTower, refuse_attention_maps, run_tower
+from ._tower import EncoderCfg, HipTower, map_request, refuse_attention_maps, run_tower
 
 
 def _trunc_normal_(t, std=.02):
@@ -132,6 +132,8 @@ def _block_param_names(n_blocks, repeats, qkv_bias, use_transform):
 
 class _StudentBase(nn.Module):
     _tower: Optional[HipTower] = None
+    # set by DistillModel / DualDistillModel: how many attention maps the teacher exports, i.e. how many `zip` pairs (None = all)
+    attn_map_pairs: Optional[int] = None
 
     @property
     def output_layer(self):
@@ -147,10 +149,13 @@ class _StudentBase(nn.Module):
     def _features(self, x, control_output: Optional[ControlOutput], output_cls):
         co = control_output or ControlOutput()
         refuse_attention_maps(co)
-        rep, hidden, emb = run_tower(self._tower, x, co.need_rep, co.need_emb)
-        # like the reference, EVERY block execution contributes a hidden state (weight_share_model.py:211, :356-357)
+        # like the reference, EVERY block execution contributes a hidden state (weight_share_model.py:211, :356-357) and, when asked,
+        # head-mean attention maps (:97-121; inside a distillation model only the executions the teacher's maps pair with)
+        maps = map_request(co, range(self._tower.cfg.layers * self._tower.cfg.repeats), self.attn_map_pairs)
+        rep, hidden, emb, scores, probs = run_tower(self._tower, x, co.need_rep, co.need_emb, maps)
         llo = self._tower.last_layer_output() if getattr(co, 'need_last_layer_output', False) else None
-        return output_cls(last_representation=rep, last_layer_output=llo, representations=hidden, embedding=emb)
+        return output_cls(last_representation=rep, last_layer_output=llo, representations=hidden, embedding=emb,
+                          attention_scores=scores, attention_probs=probs)
 
 
 class RepeatVisionTransformer(_StudentBase):

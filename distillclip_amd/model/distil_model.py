@@ -9,7 +9,7 @@ from typing import Dict, List
 
 import torch
 
-from ._distill_base import DistillBase, _HParams, freeze_image_embedding
+from ._distill_base import DistillBase, _HParams, freeze_image_embedding, pair_attention_maps
 from ._loss import LossCalculator
 from .utils import teacher_load
 from .component._tower import shared_image_patches
@@ -36,6 +36,7 @@ class DistillModel(DistillBase):
         self.need_return_para = self.loss_control.get_control_output()
         for p in self.teacher.parameters():
             p.requires_grad = False                                                       # reference :59-60
+        pair_attention_maps(self.student, self.teacher)
         if model_type == 'image' and freeze_embed:
             self.freeze_image_embedding()
         self.k_list = [1, 3, 5, 10, 20, 50]

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from ._distill_base import DistillBase, _HParams, freeze_image_embedding
+from ._distill_base import DistillBase, _HParams, freeze_image_embedding, pair_attention_maps
 from ._loss import LossCalculator
 from .utils import teacher_load
 from .component.clip_model import CLIPModel
@@ -51,6 +51,8 @@ class DualDistillModel(DistillBase):
                                     state_dict=teacher_state_dict)
         for p in self.teacher.parameters():
             p.requires_grad = False                                                       # reference :76-77
+        pair_attention_maps(self.student.image_encoder, self.teacher.image_encoder)
+        pair_attention_maps(self.student.text_encoder, self.teacher.text_encoder)
         self.loss_control = LossCalculator(**loss_control_para)
         self.need_return_para = self.loss_control.get_control_output()
         if freeze_embed:
@@ -135,7 +137,8 @@ class DualDistillModel(DistillBase):
                     main.wait_event(ev)
                 outs = [teacher_outs.visual_output, teacher_outs.text_output] + outs
             for o in outs:
-                for t_ in [o.last_representation, o.embedding] + list(o.representations or []):
+                for t_ in [o.last_representation, o.embedding] + list(o.representations or []) + list(o.attention_scores or []) \
+                        + list(o.attention_probs or []):
                     if t_ is not None:
                         t_.record_stream(main)
             teacher_outs = CLIPOutput(visual_output=outs[0], text_output=outs[1])

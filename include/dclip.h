@@ -176,6 +176,26 @@ int dclip_attn_mix_fwd(const void* qkv, int64_t ld, const float* Wl, const float
 int dclip_attn_mix_bwd(const void* qkv, int64_t ld, const void* dO, int64_t ldo, const float* Wl, const float* Ww,
                        const float* stats, void* dS, float* dWl, float* dWw, void* workspace, size_t ws_bytes, int64_t B, int64_t H,
                        int64_t N, int64_t Np, int64_t hd, float scale, void* stream);
+/*
+ * Head-mean attention maps (attn_maps.hip; the attention_score_mse / attention_probs_mse terms, reference
+ * model/loss_component/attention_score_mse.py, attention_probs_mse.py, which only ever read sum(dim=1) / H of a map).
+ * maps_fwd : score_map = mean_h S_h, prob_map = mean_h softmax(conv_l(S))_h, f32 [B, N, N] each (nullable), from the packed qkv rows
+ *            (ld elements, 16-byte aligned) the score stage read; S = scale q k^T.  Wl = the [H, H] conv_l weight (students,
+ *            weight_share_model.py:101-121) or NULL (CLIP towers, _common.py:73-94).  causal: masked scores read 0 (text_encoder.py:81-85),
+ *            masked probabilities are 0.  One workgroup per (sample, 4 query rows) with every head's S of the tile in LDS; per exported
+ *            map it reads the q and k columns of qkv (2 B * N * H * hd bytes) and writes B * N * N * 4 bytes.  hd in {32, 64}, N <= 128.
+ * maps_bwd : dS[h] += g_S / H + (Wl^T dA)[h],  dA[g] = P[g] o (g_P / H - rowsum(P[g] o g_P / H)), P recomputed from qkv; d_score_map /
+ *            d_prob_map f32 [B, N, N] (nullable).  dS = the score stage's gradient of the scaled pre-mix scores, bf16 [B, H, N, Np], in the
+ *            quad-blocked layout of dclip_attn_mix_bwd (ds_blocked = 1) or row-major (0).  dWl (nullable) += sum dA_g S_h^T, built from
+ *            per-workgroup [H, H] partials in `workspace` (dclip_attn_maps_bwd_workspace_bytes(B, H, N) bytes, needed when Wl, dWl and
+ *            d_prob_map are all given) and a fixed-order reduce: no atomics, run-to-run identical.  Masked entries get no gradient.
+ */
+int dclip_attn_maps_fwd(const void* qkv, int64_t ld, const float* Wl, float* score_map, float* prob_map, int64_t B, int64_t H, int64_t N,
+                        int64_t hd, float scale, int causal, void* stream);
+size_t dclip_attn_maps_bwd_workspace_bytes(int64_t B, int64_t H, int64_t N);
+int dclip_attn_maps_bwd(const void* qkv, int64_t ld, const float* Wl, const float* d_score_map, const float* d_prob_map, void* dS,
+                        int ds_blocked, float* dWl, void* workspace, size_t ws_bytes, int64_t B, int64_t H, int64_t N, int64_t Np,
+                        int64_t hd, float scale, int causal, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Embedding-side helpers (HBM-bound).
@@ -411,6 +431,39 @@ int dclip_encoder_backward_patches(const dclip_encoder* enc, const void* patches
                                    void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
                                    const float* d_last_representation, const float* const* d_rep, const float* d_emb,
                                    dclip_bucket_cb on_bucket, void* cb_user, void* stream);
+/* Head-mean attention maps of chosen block executions (ControlOutput.need_attn_score / need_attn_prob of the reference, exported as
+ * dclip_attn_maps_fwd computes them).  All arrays are HOST arrays of n entries; every device buffer is caller-owned.
+ *   exec[k]            : block-execution index (0 .. layers * repeats - 1) of map k
+ *   score[k] / prob[k] : forward, f32 [B, N, N] outputs (array or entries nullable); written right after that execution's score stage
+ *   d_score / d_prob   : backward, their gradients (array or entries nullable); added to that execution's dS before dQ / dK are formed.
+ *                        Only maps the most recent training forward of the workspace exported may receive a gradient.
+ *   scratch            : backward, dclip_attn_maps_bwd_workspace_bytes(B, heads, tokens) bytes (head-mixing students with d_prob)
+ * Refused (DCLIP_EINVAL, nothing launched): an index out of range, maps together with tokens_eff != 0, a gradient for a map the
+ * forward did not export.  The _ex entries with maps = NULL are the plain entries; workspace sizes do not depend on maps. */
+typedef struct dclip_attn_maps {
+    int32_t n;
+    const int32_t* exec;
+    float* const* score;
+    float* const* prob;
+    const float* const* d_score;
+    const float* const* d_prob;
+    void* scratch;
+    size_t scratch_bytes;
+} dclip_attn_maps;
+int dclip_encoder_forward_ex(const dclip_encoder* enc, const void* input, int64_t B, const void* const* params,
+                             const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
+                             float* const* rep_out, float* emb_out, int64_t tokens_eff, const dclip_attn_maps* maps, void* stream);
+int dclip_encoder_forward_patches_ex(const dclip_encoder* enc, const void* patches, int64_t B, const void* const* params,
+                                     const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
+                                     float* const* rep_out, float* emb_out, const dclip_attn_maps* maps, void* stream);
+int dclip_encoder_backward_ex(const dclip_encoder* enc, const void* input, int64_t B, const void* const* params,
+                              void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                              const float* d_last_representation, const float* const* d_rep, const float* d_emb,
+                              const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* stream);
+int dclip_encoder_backward_patches_ex(const dclip_encoder* enc, const void* patches, int64_t B, const void* const* params,
+                                      void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                                      const float* d_last_representation, const float* const* d_rep, const float* d_emb,
+                                      const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* stream);
 /* gradient buckets in completion order: 0 = final norm + head, 1..L = blocks L-1..0, L+1 = embedding parameters; each is the
  * range [first_param, end_param) of the canonical parameter order above. */
 int32_t dclip_encoder_num_grad_buckets(const dclip_encoder* enc);

@@ -614,6 +614,94 @@ def clip_student_real():
     np.savez_compressed(os.path.join(OUT, 'real_b4_clipstu.npz'), **out)
     print('real_b4_clipstu.npz', len(out), 'arrays', 'loss', float(out['loss']))
 
+MAPS_LOSSES = ['out_l1', 'out_cos', 'attention_score_mse', 'attention_probs_mse']
+MAPS_ONE_TOWER = ['out_cos', 'attention_score_mse', 'attention_probs_mse']
+
+
+def _maps_case(out, tag, names, student, teacher, inputs, model_type):
+    """one training step of the reference's own modules with the attention-map terms: loss, every scaled term, and of every student
+    gradient its norm and 128 evenly spread elements (whole tensors would make the file too large to keep in the repository)"""
+    lc = quiet(LossCalculator, loss_name=names)
+    co = lc.get_control_output()
+    so = student(*inputs, co)
+    with torch.no_grad():
+        to = teacher(*inputs, co)
+    loss, res = lc(so, to, model_type)
+    loss.backward()
+    out[f'{tag}.loss'] = np_(loss)
+    for k, v in res.items():
+        out[f'{tag}.term.{k}'] = np_(v)
+    mods = [('s_img', student.image_encoder), ('s_txt', student.text_encoder)] if model_type == 'all' else [('s', student)]
+    for name, m in mods:
+        # packed per tower (one array each, not one per parameter): names, norms, [P, 128] samples (zero-padded for small tensors)
+        names_, norms, spread = [], [], []
+        for n, p in m.named_parameters():
+            if p.grad is None:
+                continue
+            g = p.grad.reshape(-1)
+            sm = g[::max(1, g.numel() // 128)][:128]
+            names_.append(n)
+            norms.append(float(g.norm()))
+            spread.append(np.pad(np_(sm), (0, 128 - sm.numel())))
+        out[f'{tag}.{name}.gnames'] = np.array(names_)
+        out[f'{tag}.{name}.gnorm'] = np.array(norms, dtype=np.float32)
+        out[f'{tag}.{name}.gspread'] = np.stack(spread).astype(np.float32)
+
+
+def attn_maps():
+    """attention_score_mse / attention_probs_mse (reference model/loss_component/attention_score_mse.py, attention_probs_mse.py):
+    (a) the TINY dual pair, (b) one-tower image with teacher need_layers [0, 1] (2 zip pairs over the student's 4 executions), (c)
+    one-tower text against the causal teacher, (d) the plain CLIP encoders as students (clip_student_tiny's pair), (e) B = 4 at the
+    l_clip student shapes under the ViT-B/32 teachers."""
+    c = TINY
+    seed, B = c['seed'], c['B']
+    image = torch.from_numpy(synth.images(seed, B, c['res']))
+    text = torch.from_numpy(synth.captions(seed, B, c['ctx'], c['vocab'], 3, 9))
+    out = {}
+
+    def tiny_teachers(need_layers=None):
+        ti = build_teacher_image(seed, c['t_img']['width'], c['t_img']['layers'], c['patch'], c['res'], c['out_dim'], need_layers)
+        tt = build_teacher_text(seed, c['t_txt']['width'], c['t_txt']['layers'], c['ctx'], c['vocab'], c['out_dim'], need_layers)
+        for p in list(ti.parameters()) + list(tt.parameters()):
+            p.requires_grad = False
+        return ti, tt
+
+    ti, tt = tiny_teachers()
+    _maps_case(out, 'a', MAPS_LOSSES, CLIPModel(True, build_student_image(seed, **c['s_img']), build_student_text(seed, **c['s_txt']), False),
+               CLIPModel(False, ti, tt, False), (text, image), 'all')
+    ti, _ = tiny_teachers([0, 1])
+    _maps_case(out, 'b', MAPS_ONE_TOWER, build_student_image(seed, **c['s_img']), ti, (image,), 'image')
+    _, tt = tiny_teachers()
+    _maps_case(out, 'c', MAPS_ONE_TOWER, build_student_text(seed, **c['s_txt']), tt, (text,), 'text')
+    # (d) clip_student_tiny's pair: 2 x 128 CLIP students (causal text) under 2 x 192 teachers
+    dseed = 31
+    d_image = torch.from_numpy(synth.images(dseed, B, c['res']))
+    d_text = torch.from_numpy(synth.captions(dseed, B, c['ctx'], c['vocab'], 3, 9))
+    d_ti = build_teacher_image(dseed, 192, 2, c['patch'], c['res'], c['out_dim'])
+    d_tt = build_teacher_text(dseed, 192, 2, c['ctx'], c['vocab'], c['out_dim'])
+    ds_i, ds_t = _clip_students(dseed + 1, 128, 2, c['patch'], c['res'], c['ctx'], c['vocab'], c['out_dim'], {'img': 192, 'txt': 192})
+    for p in list(d_ti.parameters()) + list(d_tt.parameters()):
+        p.requires_grad = False
+    _maps_case(out, 'd', MAPS_LOSSES, CLIPModel(True, ds_i, ds_t, False), CLIPModel(False, d_ti, d_tt, False), (d_text, d_image), 'all')
+    out.update({'d.image': np_(d_image), 'd.text': np_(d_text)})
+    # (e) l_clip student shapes (image 24 heads x 32, 50 tokens; text 12 heads x 64, 77 tokens), teachers need_layers [0, 1, 10, 11]
+    eseed, eB = 2027, 4
+    e_image = torch.from_numpy(synth.images(eseed, eB, 224))
+    e_text = torch.from_numpy(synth.captions(eseed, eB))
+    e_ti = build_teacher_image(eseed, 768, 12, 32, 224, 512, need_layers=[0, 1, 10, 11])
+    e_tt = build_teacher_text(eseed, 512, 12, 77, 49408, 512, need_layers=[0, 1, 10, 11])
+    for p in list(e_ti.parameters()) + list(e_tt.parameters()):
+        p.requires_grad = False
+    s_img_cfg = dict(img_size=224, patch_size=32, in_chans=3, out_dim=512, embed_dim=768, depth=6, num_heads=24,
+                     mlp_ratio=4.0, qkv_bias=True, repeated_times=2, use_transform=True)
+    e_student = CLIPModel(True, build_student_image(eseed, **s_img_cfg), build_student_text(eseed, depth=4, repeated_times=2, use_transform=True),
+                          False)
+    _maps_case(out, 'e', MAPS_LOSSES, e_student, CLIPModel(False, e_ti, e_tt, False), (e_text, e_image), 'all')
+    out.update({'seed': np.int64(seed), 'B': np.int64(B), 'd.seed': np.int64(dseed), 'e.seed': np.int64(eseed), 'e.B': np.int64(eB)})
+    np.savez_compressed(os.path.join(OUT, 'attn_maps.npz'), **out)
+    print('attn_maps.npz', len(out), 'arrays', {k: float(v) for k, v in out.items() if k.endswith('.loss')})
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['tiny', 'loss', 'real', 'trajectory']
@@ -633,6 +721,8 @@ if __name__ == '__main__':
         real_textc()
     if 'real_336' in which:
         real_336()
+    if 'attn_maps' in which:
+        attn_maps()
     if 'clip_student' in which:
         clip_student_tiny()
         clip_student_real()
