@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — distill-step throughput on N x MI355X (BASELINE.json metric: image-text pairs/sec of one full distill step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lclip|image|text|lclip336] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config lclip|image|text|lclip336] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes (one per GPU, RCCL over
 xGMI) BEFORE it touches the GPU itself, relays rank 0's JSON line and exits non-zero if any rank fails.  Under
@@ -19,6 +19,10 @@ Prints ONE JSON line on rank 0.  `--dump-outputs DIR` (rank 0) also writes what 
 DIR/<name>.npy (float32): `loss`, the logged loss terms `term.<name>` and the updated student weights `student.<name>`, each
 sampled at fixed positions when larger than its share of a 48 MiB budget (see dump_outputs), so that two builds can be compared
 output for output on identical seeded inputs.
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the dump, the JSON line.  `--full` adds
+what takes work of its own after the timed steps: the single-stream per-kernel roofline probe (`roofline`: 3 further steps, HIP
+events around every launch) and the fp32 oracle timed on the host CPU (`cpu_baseline`: ~40 s or more); `--no-roofline` /
+`--no-cpu-baseline` leave either out of a `--full` run.
 """
 import argparse
 import json
@@ -374,8 +378,11 @@ def main():
     ap.add_argument('--config', choices=sorted(WORKLOADS), default='lclip',
                     help='lclip = BASELINE.json configs[3] (the headline metric); image / text / lclip336 = configs[1] / [2] / [4]')
     ap.add_argument('--batch', type=int, default=0, help='units per GPU (default: the configuration\'s own batch)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the per-kernel roofline probe and the CPU baseline (not needed for the '
+                         'headline figure)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='--full without the roofline probe')
     ap.add_argument('--no-clock-probe', action='store_true')
     ap.add_argument('--dry-launch', action='store_true', help='spawn the ranks, join a gloo group on the CPU, exit (launcher test)')
     ap.add_argument('--launch-timeout', type=float, default=1800.0, help='launcher: seconds every rank has to finish')
@@ -390,6 +397,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    run_roofline = args.full and not args.no_roofline
+    run_cpu_baseline = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # nothing above touched the GPU (torch is not even imported)
@@ -519,7 +528,7 @@ def main():
         log(f'{len(outs)} outputs of the last timed step written to {args.dump_outputs}')
 
     roofline = None
-    if not args.no_roofline:
+    if run_roofline:
         # dominant kernel = gemm_nt (forward linears + dgrad): HIP events around every launch of 2 further steps, recorded on the
         # launch stream by the library's trace hooks (include/dclip.h: dclip_trace_*).  EVERY rank runs these steps (they contain
         # the gradient collectives); only rank 0 traces.
@@ -538,7 +547,7 @@ def main():
         torch.cuda.synchronize()
         if multi is not None:
             model.multi_stream = multi
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and run_roofline:
         kind = (ctypes.c_int32 * cap)()
         ms = (ctypes.c_float * cap)()
         fl = (ctypes.c_double * cap)()
@@ -575,8 +584,8 @@ def main():
                                                       'hbm_frac': round(v[3] / (v[1] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
                                for k, v in agg.items()}}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        log('roofline probe done; CPU baseline')
+    if rank == 0 and world == 1 and run_cpu_baseline:
+        log('CPU baseline')
         cpu = cpu_baseline(wl, seed)
 
     if rank == 0:

@@ -10,7 +10,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 # profiled passes put every tower on one stream (same kernels, same launches; the multi-stream step time is bench.py's number)
 export DCLIP_MULTI_STREAM=0
 OUT=gpurun_out
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 for c in $CONFIGS; do
   if [ $c = default ]; then sfx=""; args=""; else sfx="_$c"; args="--config $c"; fi
   echo "[profiles] stats $c"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}${sfx}_stats -- $B $args --steps 5 --warmup 3 > $OUT/prof_${TAG}${sfx}_stats.log 2>&1 || exit 1
