@@ -299,15 +299,6 @@ __global__ __launch_bounds__(256) void pick_index_kernel(const int64_t* __restri
     if (lane == 0) idx[b] = b * N + best;
 }
 
-// out[r, :] = src[idx[r], :]   (f32 rows)
-__global__ void gather_rows_kernel(const float* __restrict__ src, int64_t lds, const int* __restrict__ idx,
-                                   float* __restrict__ out, int rows, int D) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)rows * D) return;
-    const int r = (int)(i / D), c = (int)(i % D);
-    out[i] = src[(int64_t)idx[r] * lds + c];
-}
-
 // torch.optim.AdamW semantics (decoupled weight decay; bias-corrected), reference distil_model.py:160-162
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2,
@@ -442,13 +433,6 @@ extern "C" int dclip_cast_f16_f32(const void* src, float* dst, int64_t n, void* 
     return dclip_check_launch("dclip_cast_f16_f32");
 }
 
-extern "C" int dclip_cast_transpose_bf16(const float* W, void* Wb, void* Wt, int64_t R, int64_t C, void* stream) {
-    DCLIP_REQUIRE(W && (Wb || Wt) && R > 0 && C > 0, "dclip_cast_transpose_bf16: bad argument");
-    dim3 grid((unsigned)((C + 63) / 64), (unsigned)((R + 63) / 64));
-    hipLaunchKernelGGL(cast_transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, W, (bf16_t*)Wb, (bf16_t*)Wt, (int)R, (int)C);
-    return dclip_check_launch("dclip_cast_transpose_bf16");
-}
-
 extern "C" int dclip_cast_transpose_bf16_multi(const float* const* W, void* const* Wb, void* const* Wt, const int64_t* R,
                                                const int64_t* C, int64_t n, void* stream) {
     DCLIP_REQUIRE(W && Wb && Wt && R && C && n > 0, "dclip_cast_transpose_bf16_multi: bad argument");
@@ -545,13 +529,6 @@ extern "C" int dclip_pick_index(const int64_t* ids, int64_t id_stride, int32_t* 
     DCLIP_REQUIRE(idx && B > 0 && N > 0 && id_stride >= N, "dclip_pick_index: bad argument");
     hipLaunchKernelGGL(pick_index_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ids, (int)id_stride, idx, (int)B, (int)N);
     return dclip_check_launch("dclip_pick_index");
-}
-
-extern "C" int dclip_gather_rows(const float* src, int64_t ld, const int32_t* idx, float* out, int64_t rows, int64_t D,
-                                 void* stream) {
-    DCLIP_REQUIRE(src && idx && out && rows > 0 && D > 0, "dclip_gather_rows: bad argument");
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((rows * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, ld, idx, out, (int)rows, (int)D);
-    return dclip_check_launch("dclip_gather_rows");
 }
 
 // several ranges in one launch (blockIdx.y = range): the sharded data-parallel step updates one owned slice per gradient bucket — 9 launches

@@ -443,16 +443,18 @@ static int clear_backward_seeds(const Plan& p, const Work& w, int64_t M, void* s
     return DCLIP_OK;
 }
 
-// ext_patches: the image tower's [B*N, K] bf16 patch rows made by the caller (dclip_im2row, cls_rows = 1) — two towers that
+// patches: the image tower's [B*N, K] bf16 patch rows made by the caller (dclip_im2row, cls_rows = 1) — two towers that
 // see the same images and cut them the same way share one conversion; null: this call converts `input` itself
-static int encoder_forward_impl(const dclip_encoder* e, const void* input, const bf16_t* ext_patches, int64_t B, const void* const* params,
-                                const void* wcache, void* workspace, size_t ws_bytes, int training,
-                                float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
-                                const dclip_attn_maps* maps, void* st) {
-    DCLIP_REQUIRE(e && (input || ext_patches) && params && wcache && workspace && last_representation, "dclip_encoder_forward: null argument");
+extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, const void* patches, int64_t B, const void* const* params,
+                                     const void* wcache, void* workspace, size_t ws_bytes, int training,
+                                     float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
+                                     const dclip_attn_maps* maps, void* st) {
+    DCLIP_REQUIRE(e && (input || patches) && params && wcache && workspace && last_representation, "dclip_encoder_forward: null argument");
     DCLIP_REQUIRE(B > 0, "dclip_encoder_forward: empty batch");
     const Plan& p = e->p;
-    DCLIP_REQUIRE(!ext_patches || (p.image && ((uintptr_t)ext_patches % 16) == 0), "dclip_encoder_forward_patches: image towers only, 16-byte aligned rows");
+    const bf16_t* ext_patches = (const bf16_t*)patches;
+    DCLIP_REQUIRE(!ext_patches || (p.image && ((uintptr_t)ext_patches % 16) == 0), "dclip_encoder_forward: patches: image towers only, 16-byte aligned rows");
+    DCLIP_REQUIRE(!ext_patches || tokens_eff == 0, "dclip_encoder_forward: patches cannot be combined with tokens_eff");
     DCLIP_REQUIRE(!training || p.train, "dclip_encoder_forward: the frozen teacher tower (kind 0) is inference-only");
     // tokens_eff: causal text teacher only.  Positions after the longest caption's EOT cannot influence any EOT row (causal
     // attention; LN / MLP are per token), so the tower may run on the first tokens_eff positions with identical output.
@@ -483,15 +485,15 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
 
     // ---- embedding -----------------------------------------------------------------------------------------
     if (p.image) {
-        const bf16_t* patches = ext_patches ? ext_patches : w.patches;
+        const bf16_t* rows = ext_patches ? ext_patches : w.patches;
         if (!ext_patches) CK(dclip_im2row((const float*)input, w.patches, B, p.c.in_chans, p.c.resolution, p.c.patch, 1, st));
         if (p.student) {   // params: 0 conv w, 1 conv b, 2 cls_token, 3 pos_embed
             CK(dclip_token_table(PF(params, 3), PF(params, 2), PF(params, 1), w.tok_table, N, D, st));
-            CK(gemm(patches, p.K, W + p.w_embed, p.K, w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, 1, N, w.tok_table, st));
+            CK(gemm(rows, p.K, W + p.w_embed, p.K, w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, 1, N, w.tok_table, st));
         } else {           // params: 0 conv1 w, 1 class_embedding, 2 positional_embedding, 3 ln_pre w, 4 ln_pre b
             CK(dclip_token_table(PF(params, 2), PF(params, 1), nullptr, w.tok_table, N, D, st));
             const int sdt0 = w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;
-            CK(gemm(patches, p.K, W + p.w_embed, p.K, w.x0, D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, sdt0, N, w.tok_table, st));
+            CK(gemm(rows, p.K, W + p.w_embed, p.K, w.x0, D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, sdt0, N, w.tok_table, st));
             CK(ln_stream(w.h16, w.x0, D, nullptr, PF(params, 3), PF(params, 4), w.X[0], D, sdt0, w.mean0, w.rstd0, M, D, st));
         }
     } else if (p.compressed) {   // params: 0 table [V,rank], 1 linear w [D,rank], 2 linear b, 3 pos
@@ -549,39 +551,6 @@ static int encoder_forward_impl(const dclip_encoder* e, const void* input, const
     return DCLIP_OK;
 }
 
-extern "C" int dclip_encoder_forward_ex(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
-                                        const void* wcache, void* workspace, size_t ws_bytes, int training,
-                                        float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
-                                        const dclip_attn_maps* maps, void* st) {
-    DCLIP_REQUIRE(input, "dclip_encoder_forward: null argument");
-    return encoder_forward_impl(e, input, nullptr, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out, emb_out,
-                                tokens_eff, maps, st);
-}
-
-extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
-                                     const void* wcache, void* workspace, size_t ws_bytes, int training,
-                                     float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
-                                     void* st) {
-    return dclip_encoder_forward_ex(e, input, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out, emb_out,
-                                    tokens_eff, nullptr, st);
-}
-
-extern "C" int dclip_encoder_forward_patches_ex(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
-                                                const void* wcache, void* workspace, size_t ws_bytes, int training,
-                                                float* last_representation, float* const* rep_out, float* emb_out,
-                                                const dclip_attn_maps* maps, void* st) {
-    DCLIP_REQUIRE(patches, "dclip_encoder_forward_patches: null argument");
-    return encoder_forward_impl(e, nullptr, (const bf16_t*)patches, B, params, wcache, workspace, ws_bytes, training, last_representation,
-                                rep_out, emb_out, 0, maps, st);
-}
-
-extern "C" int dclip_encoder_forward_patches(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
-                                             const void* wcache, void* workspace, size_t ws_bytes, int training,
-                                             float* last_representation, float* const* rep_out, float* emb_out, void* st) {
-    return dclip_encoder_forward_patches_ex(e, patches, B, params, wcache, workspace, ws_bytes, training, last_representation, rep_out,
-                                            emb_out, nullptr, st);
-}
-
 // All-token output of the final norm + projection (reference _common.py:210-215, text_encoder.py:69-72,
 // weight_share_model.py:363-366 / :503-506: `last_layer_output`, of which `last_representation` is one row per sample).  The
 // training path projects only the picked row; this call produces the whole [B*N, E] tensor on request from the residual
@@ -603,13 +572,15 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
     return DCLIP_OK;
 }
 
-static int encoder_backward_impl(const dclip_encoder* e, const void* input, const bf16_t* ext_patches, int64_t B, const void* const* params,
-                                 void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                 const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                 const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    DCLIP_REQUIRE(e && (input || ext_patches) && params && grads && wcache && workspace && d_last_representation, "dclip_encoder_backward: null argument");
+// patches: the rows the forward ran on, if the caller made them (they are the patch-embedding wgrad's operand)
+extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input, const void* patches, int64_t B, const void* const* params,
+                                      void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                                      const float* d_last_representation, const float* const* d_rep, const float* d_emb,
+                                      const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
+    DCLIP_REQUIRE(e && (input || patches) && params && grads && wcache && workspace && d_last_representation, "dclip_encoder_backward: null argument");
     const Plan& p = e->p;
-    DCLIP_REQUIRE(!ext_patches || p.image, "dclip_encoder_backward_patches: image towers only");
+    const bf16_t* ext_patches = (const bf16_t*)patches;
+    DCLIP_REQUIRE(!ext_patches || p.image, "dclip_encoder_backward: patches: image towers only");
     DCLIP_REQUIRE(p.train, "dclip_encoder_backward: the frozen teacher tower (kind 0) has no backward");
     // gradients of exported head-mean maps, per block execution
     std::vector<MapGrad> mgrad(p.L * p.R, MapGrad{nullptr, nullptr, nullptr, 0});
@@ -755,40 +726,6 @@ static int encoder_backward_impl(const dclip_encoder* e, const void* input, cons
     }
     if (on_bucket) on_bucket(cb_user, p.L + 1);          // embedding parameters: the last bucket
     return DCLIP_OK;
-}
-
-extern "C" int dclip_encoder_backward_ex(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
-                                         void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                         const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                         const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    DCLIP_REQUIRE(input, "dclip_encoder_backward: null argument");
-    return encoder_backward_impl(e, input, nullptr, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb,
-                                 maps, on_bucket, cb_user, st);
-}
-
-extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input, int64_t B, const void* const* params,
-                                      void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                      const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                      dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    return dclip_encoder_backward_ex(e, input, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb, nullptr,
-                                     on_bucket, cb_user, st);
-}
-
-extern "C" int dclip_encoder_backward_patches_ex(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
-                                                 void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                                 const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                                 const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    DCLIP_REQUIRE(patches, "dclip_encoder_backward_patches: null argument");
-    return encoder_backward_impl(e, nullptr, (const bf16_t*)patches, B, params, grads, wcache, workspace, ws_bytes, d_last_representation,
-                                 d_rep, d_emb, maps, on_bucket, cb_user, st);
-}
-
-extern "C" int dclip_encoder_backward_patches(const dclip_encoder* e, const void* patches, int64_t B, const void* const* params,
-                                              void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                              const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                              dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    return dclip_encoder_backward_patches_ex(e, patches, B, params, grads, wcache, workspace, ws_bytes, d_last_representation, d_rep, d_emb,
-                                             nullptr, on_bucket, cb_user, st);
 }
 
 // Gradient buckets in the order the backward completes them (data-parallel exchange, SURVEY.md section 8e Collective 1):

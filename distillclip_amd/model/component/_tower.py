@@ -97,6 +97,16 @@ def _shared_rows_for(x, cfg):
     return rows
 
 
+class TowerResult(tuple):
+    """HipTower.forward's result, the same shape whatever was asked for: unpacks as (last_representation [B,E], input as passed to
+    C, hidden states list, embedding or None); .scores / .probs: the exported head-mean attention maps (empty lists if none)"""
+
+    def __new__(cls, out, x, reps, emb, scores, probs):
+        res = super().__new__(cls, (out, x, reps, emb))
+        res.scores, res.probs = scores, probs
+        return res
+
+
 def _ptr_array(tensors):
     arr = (ctypes.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):
@@ -291,9 +301,9 @@ class HipTower:
 
     # ---- execution -----------------------------------------------------------------------------------------------
     def forward(self, x, training, need_rep=False, need_emb=False, rep_layers=None, tokens_eff=0, maps=None):
-        """-> (last_representation [B,E], input as passed to C, hidden states list, embedding or None)
-        maps: None, or (need_score, need_prob, block executions): their head-mean attention maps, [B, 1, N, N] f32 each, are a fifth
-        result (scores, probs) — empty lists for the kind not asked for (include/dclip.h: dclip_attn_maps)"""
+        """-> TowerResult (last_representation [B,E], input as passed to C, hidden states list, embedding or None; .scores, .probs)
+        maps: None, or (need_score, need_prob, block executions): their head-mean attention maps, [B, 1, N, N] f32 each — empty lists
+        for a kind not asked for (include/dclip.h: dclip_attn_maps)"""
         if not x.is_cuda:
             raise RuntimeError('distillclip_amd towers need CUDA(HIP) inputs; there is no CPU fallback')
         expect = torch.float32 if self.cfg.modality == 0 else torch.int64
@@ -335,33 +345,13 @@ class HipTower:
                 desc = _maps_desc(execs, scores or None, probs or None)
         rows = _shared_rows_for(x, self.cfg) if not tokens_eff else None
         self._patch_rows = rows if training else None      # (kept until the backward: operand of the patch-embedding wgrad)
-        if desc is not None:
-            st = torch.cuda.current_stream().cuda_stream
-            if rows is not None:
-                lib().dclip_encoder_forward_patches_ex(self._handle, rows.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
-                                                       self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
-                                                       out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(),
-                                                       ctypes.byref(desc[0]), st)
-            else:
-                lib().dclip_encoder_forward_ex(self._handle, x.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
-                                               self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
-                                               out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(), int(tokens_eff),
-                                               ctypes.byref(desc[0]), st)
-        elif rows is not None:
-            lib().dclip_encoder_forward_patches(self._handle, rows.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
-                                                self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
-                                                out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(),
-                                                torch.cuda.current_stream().cuda_stream)
-        else:
-            lib().dclip_encoder_forward(self._handle, x.data_ptr(), B, _ptr_array(ps), self.wcache.data_ptr(),
-                                        self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
-                                        out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(), int(tokens_eff),
-                                        torch.cuda.current_stream().cuda_stream)
+        lib().dclip_encoder_forward(self._handle, None if rows is not None else x.data_ptr(), None if rows is None else rows.data_ptr(), B,
+                                    _ptr_array(ps), self.wcache.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+                                    1 if training else 0, out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(), int(tokens_eff),
+                                    None if desc is None else ctypes.byref(desc[0]), torch.cuda.current_stream().cuda_stream)
         self._saved_batch = B if training else None
         self._last_fwd = (B, bool(training), int(tokens_eff))
-        if maps is not None:
-            return out, x, reps, emb, (scores, probs)
-        return out, x, reps, emb
+        return TowerResult(out, x, reps, emb, scores, probs)
 
     @torch.no_grad()
     def last_layer_output(self):
@@ -436,17 +426,12 @@ class HipTower:
                     nb = lib().dclip_attn_maps_bwd_workspace_bytes(B, self.cfg.heads, self.cfg.tokens)
                     scratch = torch.empty(nb, dtype=torch.uint8, device=x.device)
                 desc = _maps_desc([int(i) for i in execs], d_score=d_sc, d_prob=d_pr, scratch=scratch)
-        args = (self._handle, x.data_ptr() if rows is None else rows.data_ptr(), B, _ptr_array(ps), _ptr_array(gs), self.wcache.data_ptr(),
-                self.workspace.data_ptr(), self.workspace.numel(), d_out.data_ptr(),
-                _ptr_array(keep) if any(g is not None for g in keep) else None,
-                None if d_emb is None else d_emb.data_ptr())
-        tail = (ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None, torch.cuda.current_stream().cuda_stream)
-        if desc is None:
-            call = lib().dclip_encoder_backward if rows is None else lib().dclip_encoder_backward_patches
-            call(*args, *tail)
-        else:
-            call = lib().dclip_encoder_backward_ex if rows is None else lib().dclip_encoder_backward_patches_ex
-            call(*args, ctypes.byref(desc[0]), *tail)
+        lib().dclip_encoder_backward(self._handle, None if rows is not None else x.data_ptr(), None if rows is None else rows.data_ptr(), B,
+                                     _ptr_array(ps), _ptr_array(gs), self.wcache.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+                                     d_out.data_ptr(), _ptr_array(keep) if any(g is not None for g in keep) else None,
+                                     None if d_emb is None else d_emb.data_ptr(), None if desc is None else ctypes.byref(desc[0]),
+                                     ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None,
+                                     torch.cuda.current_stream().cuda_stream)
         if failed:
             raise failed[0]
         self._saved_batch = None
@@ -483,8 +468,7 @@ class _TowerFn(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, anchor, x, tower, need_rep, need_emb, maps, *params):
         res = tower.forward(x, training=True, need_rep=need_rep, need_emb=need_emb, maps=maps)
-        out, xin, reps, emb = res[:4]
-        scores, probs = res[4] if maps is not None else ([], [])
+        (out, xin, reps, emb), scores, probs = res, res.scores, res.probs
         ctx.tower = tower
         ctx.x = xin
         ctx.n_rep = len(reps)
@@ -552,7 +536,6 @@ def run_tower(tower, x, need_rep=False, need_emb=False, maps=None):
         out, reps, emb = res[0], list(res[1:1 + nex]), (res[1 + nex] if need_emb else None)
     else:
         res = tower.forward(x, training=False, need_rep=need_rep, need_emb=need_emb, maps=maps)
-        out, reps, emb = res[0], res[2], res[3]
-        scores, probs = res[4] if maps is not None else ([], [])
+        (out, _, reps, emb), scores, probs = res, res.scores, res.probs
     total = tower.cfg.layers * tower.cfg.repeats
     return out, reps, emb, ExportedMaps(scores, total), ExportedMaps(probs, total)

@@ -139,8 +139,8 @@ def encode_clip(enc, x, control_output, output_cls, max_tokens=None):
             res = enc._tower.forward(x, training=False, need_rep=co.need_rep, need_emb=co.need_emb,
                                      rep_layers=list(enc.need_layers) if enc.need_layers is not None else None,
                                      tokens_eff=min(int(hint), enc._tower.cfg.tokens), maps=maps)
-        out, reps, emb = res[0], res[2], res[3]
-        scores, probs = (ExportedMaps(m, len(layers)) for m in (res[4] if maps is not None else ([], [])))
+        out, _, reps, emb = res
+        scores, probs = ExportedMaps(res.scores, len(layers)), ExportedMaps(res.probs, len(layers))
     llo = enc._tower.last_layer_output() if want_all else None
     return output_cls(last_representation=out, last_layer_output=llo, representations=reps, embedding=emb,
                       attention_scores=scores, attention_probs=probs)

@@ -200,7 +200,7 @@ int dclip_attn_maps_bwd(const void* qkv, int64_t ld, const float* Wl, const floa
 /* ---------------------------------------------------------------------------------------------------------------
  * Embedding-side helpers (HBM-bound).
  * cast_bf16            : f32 -> bf16 copy (per-step weight down-cast).
- * cast_transpose_bf16  : W f32 [R,C] -> Wb bf16 [R,C] (nullable) and Wt bf16 [C,R] (nullable; the dgrad operand).
+ * cast_transpose_bf16_multi : per job, W f32 [R,C] -> Wb bf16 [R,C] (nullable) and Wt bf16 [C,R] (nullable; the dgrad operand).
  * im2row               : image f32 [B,C,res,res] -> bf16 rows [B*(G*G+cls_rows), C*p*p], G = res / p; the class-token row
  *                        is zero.  Conv2d(k=p,s=p) of _common.py:176,196 / timm PatchEmbed (weight_share_model.py:250).
  * token_table          : out[0] = pos[0] + cls ; out[n>=1] = pos[n] + bias  (cls NULL: out[n] = pos[n] + bias)
@@ -211,15 +211,13 @@ int dclip_attn_maps_bwd(const void* qkv, int64_t ld, const float* Wl, const floa
  * embed_scatter_add    : dtable[ids[r]] += dx[r] (f32 atomics; rows with the hot ids 0 / vocab-2 / vocab-1 = padding / SOT / EOT
  *                        of the clip.tokenize layout are reduced per block first instead of contending on three table rows).
  * pick_index           : idx[b] = b*N + argmax_n ids[b, 0..id_stride) (text_encoder.py:86, weight_share_model.py:506); ids NULL: b*N.
- * gather_rows          : out[r] = src[idx[r]] (f32).
  * adamw                : torch.optim.AdamW step on flat f32 buffers (distil_model.py:160-162, dual_distill_model.py:194-196).
  */
 int dclip_cast_bf16(const float* src, void* dst, int64_t n, void* stream);
 int dclip_cast_f16_f32(const void* src, float* dst, int64_t n, void* stream);   /* f16 -> f32 (teacher hidden-state export) */
 /* dst += src (f32) ; optional bf16 copy of the updated dst ; optional column sums of src (row length D; then n % D == 0) */
 int dclip_axpy_f32(float* dst, const float* src, void* dst_bf16, int64_t n, float* colsum_acc, int64_t D, void* stream);
-int dclip_cast_transpose_bf16(const float* W, void* Wb, void* Wt, int64_t R, int64_t C, void* stream);
-/* n jobs of the above in one launch (per-step refresh of a student tower's bf16 weight cache): host arrays of device pointers
+/* n cast_transpose jobs in one launch (per-step refresh of a student tower's bf16 weight cache): host arrays of device pointers
  * and shapes; Wb[i] / Wt[i] nullable per job. */
 int dclip_cast_transpose_bf16_multi(const float* const* W, void* const* Wb, void* const* Wt, const int64_t* R, const int64_t* C,
                                     int64_t n, void* stream);
@@ -233,7 +231,6 @@ int dclip_embed_gather(const int64_t* ids, int64_t id_stride, const float* table
 int dclip_embed_scatter_add(const int64_t* ids, const void* dx, int dx_f32, float* dtable, int64_t rows, int64_t D,
                             int64_t vocab, void* stream);
 int dclip_pick_index(const int64_t* ids, int64_t id_stride, int32_t* idx, int64_t B, int64_t N, void* stream);
-int dclip_gather_rows(const float* src, int64_t ld, const int32_t* idx, float* out, int64_t rows, int64_t D, void* stream);
 int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                 float weight_decay, int64_t step, int zero_grad, void* stream);   /* zero_grad: g := 0 once consumed */
 /* the same step on `count` <= DCLIP_ADAMW_MAX_RANGES ranges in ONE launch (HOST arrays of device pointers and lengths; every range a
@@ -387,50 +384,6 @@ size_t dclip_encoder_wcache_bytes(const dclip_encoder* enc);
 size_t dclip_encoder_workspace_bytes(const dclip_encoder* enc, int64_t B, int training);
 /* refresh the bf16 GEMM-weight cache from the f32 parameters (student: every step; teacher: once) */
 int dclip_encoder_prepare(const dclip_encoder* enc, const void* const* params, void* wcache, void* stream);
-/* input: image f32 [B,C,res,res] or token ids i64 [B,N].  last_representation: f32 [B,E] (class token / EOT row).
- * training = 1 keeps every activation backward needs inside `workspace` (kinds 1 and 2).
- * rep_out (nullable array of layers*repeats nullable f32 [B*N, D] pointers) / emb_out (nullable f32 [B*N, D]) receive the hidden
- * state after each block execution and the post-positional-embedding tokens (ControlOutput.need_rep / need_emb of the
- * reference, _loss.py:100-116); d_rep / d_emb are the matching gradients, added to the residual-stream gradient in backward.
- * tokens_eff (0 = all): causal text teacher only — run the tower on the first tokens_eff positions of every caption.  The
- * caller guarantees that every caption's EOT lies inside that prefix; positions after it cannot influence the EOT row
- * (causal mask), so last_representation is unchanged. */
-int dclip_encoder_forward(const dclip_encoder* enc, const void* input, int64_t B, const void* const* params,
-                          const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
-                          float* const* rep_out, float* emb_out, int64_t tokens_eff, void* stream);
-/* The same forward on patch rows the caller has already cut: `patches` = bf16 [B*N, C*patch*patch] from dclip_im2row(..., cls_rows = 1).
- * Teacher and student see the same image batch (reference dual_distill_model.py:107-109, distil_model.py forward) and, when their
- * patch size and resolution agree, the same conv1 / PatchEmbed unfolding (_common.py:196-198, weight_share_model.py:344): one
- * conversion then serves both towers.  Image towers only; the matching backward is dclip_encoder_backward_patches. */
-int dclip_encoder_forward_patches(const dclip_encoder* enc, const void* patches, int64_t B, const void* const* params,
-                                  const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
-                                  float* const* rep_out, float* emb_out, void* stream);
-/* last_layer_output (reference output.py:16-35; _common.py:210-215, text_encoder.py:69-72, weight_share_model.py:363-366,
- * :503-506): final norm + projection of EVERY token, f32 [B*N, E], computed on request from the residual stream the most
- * recent dclip_encoder_forward(enc, ..., B, training) left in `workspace` (tokens_eff must have been 0).  scratch: bf16
- * [B*N, D] caller-owned.  last_representation is the class-token / EOT row of this tensor. */
-int dclip_encoder_last_layer_output(const dclip_encoder* enc, int64_t B, const void* const* params, const void* wcache,
-                                    void* workspace, size_t ws_bytes, int training, void* scratch, float* out, void* stream);
-/* on_bucket (nullable): host callback, invoked on the calling thread as soon as every launch that writes gradient bucket
- * `bucket` has been enqueued on `stream` (an event recorded on `stream` inside the callback marks the bucket complete): the
- * data-parallel exchange of that bucket may start while the rest of the backward runs (reference: Lightning DDP's bucketed
- * all-reduce from autograd hooks, config/final_config/l_clip.yaml:56 strategy ddp_find_unused_parameters_false).
- * Buckets complete in index order; see dclip_encoder_grad_bucket.
- * Seeds: the backward starts from a residual-stream gradient accumulator (and one bf16 operand slot) that must be zero.  The training
- * forward clears them at its end (beside the other towers' work) and the handle remembers the workspace it did that for; a backward that
- * does not find ITS workspace there — a second backward on one forward, a retry, another workspace used in between — clears them itself.
- * Either way one call = the gradients of the most recent training forward of that workspace for the given d_*; gradients ACCUMULATE (+=)
- * into `grads` as everywhere. */
-typedef void (*dclip_bucket_cb)(void* user, int32_t bucket);
-int dclip_encoder_backward(const dclip_encoder* enc, const void* input, int64_t B, const void* const* params,
-                           void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                           const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                           dclip_bucket_cb on_bucket, void* cb_user, void* stream);
-/* backward of a forward that ran on caller-made patch rows (they are the patch-embedding wgrad's operand) */
-int dclip_encoder_backward_patches(const dclip_encoder* enc, const void* patches, int64_t B, const void* const* params,
-                                   void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                   const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                   dclip_bucket_cb on_bucket, void* cb_user, void* stream);
 /* Head-mean attention maps of chosen block executions (ControlOutput.need_attn_score / need_attn_prob of the reference, exported as
  * dclip_attn_maps_fwd computes them).  All arrays are HOST arrays of n entries; every device buffer is caller-owned.
  *   exec[k]            : block-execution index (0 .. layers * repeats - 1) of map k
@@ -439,7 +392,7 @@ int dclip_encoder_backward_patches(const dclip_encoder* enc, const void* patches
  *                        Only maps the most recent training forward of the workspace exported may receive a gradient.
  *   scratch            : backward, dclip_attn_maps_bwd_workspace_bytes(B, heads, tokens) bytes (head-mixing students with d_prob)
  * Refused (DCLIP_EINVAL, nothing launched): an index out of range, maps together with tokens_eff != 0, a gradient for a map the
- * forward did not export.  The _ex entries with maps = NULL are the plain entries; workspace sizes do not depend on maps. */
+ * forward did not export.  maps = NULL or n = 0 exports nothing; workspace sizes do not depend on maps. */
 typedef struct dclip_attn_maps {
     int32_t n;
     const int32_t* exec;
@@ -450,20 +403,46 @@ typedef struct dclip_attn_maps {
     void* scratch;
     size_t scratch_bytes;
 } dclip_attn_maps;
-int dclip_encoder_forward_ex(const dclip_encoder* enc, const void* input, int64_t B, const void* const* params,
-                             const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
-                             float* const* rep_out, float* emb_out, int64_t tokens_eff, const dclip_attn_maps* maps, void* stream);
-int dclip_encoder_forward_patches_ex(const dclip_encoder* enc, const void* patches, int64_t B, const void* const* params,
-                                     const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
-                                     float* const* rep_out, float* emb_out, const dclip_attn_maps* maps, void* stream);
-int dclip_encoder_backward_ex(const dclip_encoder* enc, const void* input, int64_t B, const void* const* params,
-                              void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                              const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                              const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* stream);
-int dclip_encoder_backward_patches_ex(const dclip_encoder* enc, const void* patches, int64_t B, const void* const* params,
-                                      void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
-                                      const float* d_last_representation, const float* const* d_rep, const float* d_emb,
-                                      const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* stream);
+/* input: image f32 [B,C,res,res] or token ids i64 [B,N].  last_representation: f32 [B,E] (class token / EOT row).
+ * patches (image towers only; nullable): replaces `input` with patch rows the caller has already cut, bf16 [B*N, C*patch*patch] from
+ * dclip_im2row(..., cls_rows = 1), 16-byte aligned.  Teacher and student see the same image batch (reference
+ * dual_distill_model.py:107-109, distil_model.py forward) and, when their patch size and resolution agree, the same conv1 /
+ * PatchEmbed unfolding (_common.py:196-198, weight_share_model.py:344): one conversion then serves both towers.  input may then be
+ * NULL (not both); patches are refused on text towers and together with tokens_eff != 0.
+ * training = 1 keeps every activation backward needs inside `workspace` (kinds 1 and 2).
+ * rep_out (nullable array of layers*repeats nullable f32 [B*N, D] pointers) / emb_out (nullable f32 [B*N, D]) receive the hidden
+ * state after each block execution and the post-positional-embedding tokens (ControlOutput.need_rep / need_emb of the
+ * reference, _loss.py:100-116); d_rep / d_emb are the matching gradients, added to the residual-stream gradient in backward.
+ * tokens_eff (0 = all): causal text teacher only — run the tower on the first tokens_eff positions of every caption.  The
+ * caller guarantees that every caption's EOT lies inside that prefix; positions after it cannot influence the EOT row
+ * (causal mask), so last_representation is unchanged.
+ * maps (nullable): head-mean attention maps to export, see dclip_attn_maps. */
+int dclip_encoder_forward(const dclip_encoder* enc, const void* input, const void* patches, int64_t B, const void* const* params,
+                          const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
+                          float* const* rep_out, float* emb_out, int64_t tokens_eff, const dclip_attn_maps* maps, void* stream);
+/* last_layer_output (reference output.py:16-35; _common.py:210-215, text_encoder.py:69-72, weight_share_model.py:363-366,
+ * :503-506): final norm + projection of EVERY token, f32 [B*N, E], computed on request from the residual stream the most
+ * recent dclip_encoder_forward(enc, ..., B, training) left in `workspace` (tokens_eff must have been 0).  scratch: bf16
+ * [B*N, D] caller-owned.  last_representation is the class-token / EOT row of this tensor. */
+int dclip_encoder_last_layer_output(const dclip_encoder* enc, int64_t B, const void* const* params, const void* wcache,
+                                    void* workspace, size_t ws_bytes, int training, void* scratch, float* out, void* stream);
+/* input / patches: what the forward ran on (caller-made patch rows are the patch-embedding wgrad's operand).
+ * maps (nullable): gradients of the maps the forward exported, see dclip_attn_maps.
+ * on_bucket (nullable): host callback, invoked on the calling thread as soon as every launch that writes gradient bucket
+ * `bucket` has been enqueued on `stream` (an event recorded on `stream` inside the callback marks the bucket complete): the
+ * data-parallel exchange of that bucket may start while the rest of the backward runs (reference: Lightning DDP's bucketed
+ * all-reduce from autograd hooks, config/final_config/l_clip.yaml:56 strategy ddp_find_unused_parameters_false).
+ * Buckets complete in index order; see dclip_encoder_grad_bucket.
+ * Seeds: the backward starts from a residual-stream gradient accumulator (and one bf16 operand slot) that must be zero.  The training
+ * forward clears them at its end (beside the other towers' work) and the handle remembers the workspace it did that for; a backward that
+ * does not find ITS workspace there — a second backward on one forward, a retry, another workspace used in between — clears them itself.
+ * Either way one call = the gradients of the most recent training forward of that workspace for the given d_*; gradients ACCUMULATE (+=)
+ * into `grads` as everywhere. */
+typedef void (*dclip_bucket_cb)(void* user, int32_t bucket);
+int dclip_encoder_backward(const dclip_encoder* enc, const void* input, const void* patches, int64_t B, const void* const* params,
+                           void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                           const float* d_last_representation, const float* const* d_rep, const float* d_emb,
+                           const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* stream);
 /* gradient buckets in completion order: 0 = final norm + head, 1..L = blocks L-1..0, L+1 = embedding parameters; each is the
  * range [first_param, end_param) of the canonical parameter order above. */
 int32_t dclip_encoder_num_grad_buckets(const dclip_encoder* enc);

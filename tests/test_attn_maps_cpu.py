@@ -32,12 +32,17 @@ def test_value_maps_are_still_refused():
 def test_header_declares_and_library_exports_the_map_entries():
     from distillclip_amd._lib import lib, _HEADER
     src = open(_HEADER).read()
-    names = ['dclip_attn_maps_fwd', 'dclip_attn_maps_bwd', 'dclip_attn_maps_bwd_workspace_bytes', 'dclip_encoder_forward_ex',
-             'dclip_encoder_forward_patches_ex', 'dclip_encoder_backward_ex', 'dclip_encoder_backward_patches_ex']
+    names = ['dclip_attn_maps_fwd', 'dclip_attn_maps_bwd', 'dclip_attn_maps_bwd_workspace_bytes', 'dclip_encoder_forward',
+             'dclip_encoder_backward']
     for n in names:
         assert re.search(r'\b' + n + r'\s*\(', src), n
         assert hasattr(lib()._dll, n), n
     assert 'typedef struct dclip_attn_maps' in src
+    # one forward and one backward entry per tower, each taking input / patches and the nullable maps descriptor
+    protos = lib().protos
+    assert len(protos['dclip_encoder_forward'][1]) == 15 and len(protos['dclip_encoder_backward'][1]) == 16
+    assert re.search(r'dclip_encoder_forward\([^)]*const void\* patches[^)]*const dclip_attn_maps\* maps', src)
+    assert re.search(r'dclip_encoder_backward\([^)]*const void\* patches[^)]*const dclip_attn_maps\* maps', src)
 
 
 def test_maps_workspace_size():
@@ -84,36 +89,63 @@ def test_encoder_refuses_bad_map_requests_on_host():
         def data_ptr(self):
             return fake
     buf = Buf()
+    params = (ctypes.c_void_p * 64)(*([fake] * 64))
     h = _handle()
     try:
-        params = (ctypes.c_void_p * 64)(*([fake] * 64))
         ws = l.dclip_encoder_workspace_bytes(h, 2, 1)
         bad, keep = _maps_desc([4], score=[buf])     # 2 layers x 2 repeats: executions 0..3
-        with pytest.raises(ValueError, match='out of range'):
-            l.dclip_encoder_forward_ex(h, fake, 2, params, fake, fake, ws, 1, fake, None, None, 0, ctypes.byref(bad), None)
         neg, keep2 = _maps_desc([-1], prob=[buf])
-        with pytest.raises(ValueError, match='out of range'):
-            l.dclip_encoder_forward_patches_ex(h, fake, 2, params, fake, fake, ws, 1, fake, None, None, ctypes.byref(neg), None)
-        # a gradient for a map no forward of this workspace exported
-        d, keep3 = _maps_desc([1], d_prob=[buf])
-        with pytest.raises(ValueError, match='did not export'):
-            l.dclip_encoder_backward_ex(h, fake, 2, params, params, fake, fake, ws, fake, None, None, ctypes.byref(d), None, None, None)
-        with pytest.raises(ValueError, match='did not export'):
-            l.dclip_encoder_backward_patches_ex(h, fake, 2, params, params, fake, fake, ws, fake, None, None, ctypes.byref(d), None, None,
-                                                None)
+        d, keep3 = _maps_desc([1], d_prob=[buf])     # a gradient for a map no forward of this workspace exported
+        # the same refusals whether the image tower converts `input` itself or takes caller-cut patch rows
+        for inp, rows in ((fake, None), (None, fake)):
+            for m in (bad, neg):
+                with pytest.raises(ValueError, match='out of range'):
+                    l.dclip_encoder_forward(h, inp, rows, 2, params, fake, fake, ws, 1, fake, None, None, 0, ctypes.byref(m), None)
+            with pytest.raises(ValueError, match='did not export'):
+                l.dclip_encoder_backward(h, inp, rows, 2, params, params, fake, fake, ws, fake, None, None, ctypes.byref(d), None, None,
+                                         None)
+        # neither input nor patch rows
+        with pytest.raises(ValueError, match='null argument'):
+            l.dclip_encoder_forward(h, None, None, 2, params, fake, fake, ws, 1, fake, None, None, 0, None, None)
+        with pytest.raises(ValueError, match='null argument'):
+            l.dclip_encoder_backward(h, None, None, 2, params, params, fake, fake, ws, fake, None, None, None, None, None, None)
     finally:
         l.dclip_encoder_destroy(h)
-    # the causal text teacher's caption-prefix shortcut cannot export maps
+    # the causal text teacher's caption-prefix shortcut cannot export maps, and a text tower takes no patch rows
     t = _handle(kind=0, modality=1, tokens=13, heads=2, layers=2, repeats=1, patch=0, resolution=0, in_chans=0, vocab=97, head_mix=0,
                 causal=1)
     try:
-        params = (ctypes.c_void_p * 64)(*([fake] * 64))
         ws = l.dclip_encoder_workspace_bytes(t, 2, 0)
         m, keep4 = _maps_desc([0], score=[buf])
-        with pytest.raises(ValueError, match='tokens_eff'):
-            l.dclip_encoder_forward_ex(t, fake, 2, params, fake, fake, ws, 0, fake, None, None, 5, ctypes.byref(m), None)
+        with pytest.raises(ValueError, match='caption prefix'):
+            l.dclip_encoder_forward(t, fake, None, 2, params, fake, fake, ws, 0, fake, None, None, 5, ctypes.byref(m), None)
+        with pytest.raises(ValueError, match='image towers only'):
+            l.dclip_encoder_forward(t, None, fake, 2, params, fake, fake, ws, 0, fake, None, None, 0, None, None)
+        with pytest.raises(ValueError, match='null argument'):
+            l.dclip_encoder_forward(t, None, None, 2, params, fake, fake, ws, 0, fake, None, None, 0, None, None)
     finally:
         l.dclip_encoder_destroy(t)
+    # a trainable text tower: its backward refuses patch rows too
+    s = _handle(modality=1, tokens=13, heads=2, patch=0, resolution=0, in_chans=0, vocab=97, head_mix=0, causal=1)
+    try:
+        ws = l.dclip_encoder_workspace_bytes(s, 2, 1)
+        with pytest.raises(ValueError, match='image towers only'):
+            l.dclip_encoder_forward(s, None, fake, 2, params, fake, fake, ws, 1, fake, None, None, 0, None, None)
+        with pytest.raises(ValueError, match='image towers only'):
+            l.dclip_encoder_backward(s, None, fake, 2, params, params, fake, fake, ws, fake, None, None, None, None, None, None)
+    finally:
+        l.dclip_encoder_destroy(s)
+    # maps together with tokens_eff on patch rows (image towers): patch rows never combine with tokens_eff
+    h = _handle(kind=0, repeats=1, head_mix=0)
+    try:
+        ws = l.dclip_encoder_workspace_bytes(h, 2, 0)
+        m, keep5 = _maps_desc([0], score=[buf])
+        with pytest.raises(ValueError, match='patches cannot be combined with tokens_eff'):
+            l.dclip_encoder_forward(h, None, fake, 2, params, fake, fake, ws, 0, fake, None, None, 5, ctypes.byref(m), None)
+        with pytest.raises(ValueError, match='patches cannot be combined with tokens_eff'):
+            l.dclip_encoder_forward(h, None, fake, 2, params, fake, fake, ws, 0, fake, None, None, 5, None, None)
+    finally:
+        l.dclip_encoder_destroy(h)
 
 
 def test_workspace_sizes_do_not_depend_on_maps():

@@ -1,6 +1,6 @@
 """Head-mean attention maps on the MI355X: the kernels against a float64 restatement built from the same operands, the towers' exported
 maps against the reference's per-head maps (tiny.npz), training steps with attention_score_mse / attention_probs_mse against the
-reference's own runs (attn_maps.npz: tools/golden/gen_golden.py attn_maps), the plain entries against the _ex entries, determinism.
+reference's own runs (attn_maps.npz: tools/golden/gen_golden.py attn_maps), a step with unread maps against a map-free one, determinism.
 
 Kernel tolerances follow from the arithmetic, not from measurement.  S = scale sum_d q_d k_d over hd f32 products of exact bf16 operands:
 |dS| <= (hd + 2) u scale sum_d |q_d k_d| with u = 2^-24.  The mixed scores add H terms: |dA| <= |Wl| |dS| + (H + 1) u |Wl| |S|.  A
@@ -345,43 +345,60 @@ def test_training_step_parity_on_the_unfused_score_stage():
 
 
 # ---- 4. no regression ---------------------------------------------------------------------------------------------------------------
-def test_plain_entries_equal_ex_entries_with_null_descriptor(monkeypatch):
-    """terms off: a tiny dual step through the plain entries and through the _ex entries with maps = NULL are bit-identical"""
-    from distillclip_amd._lib import lib
+def test_map_plumbing_leaves_a_map_free_step_unchanged(monkeypatch):
+    """terms off: a tiny dual step is bit-identical whether the towers export no maps or export maps of executions 0 and 1 that no loss
+    term reads (their gradients reach the backward as zeros), with the image towers on their own input and on shared patch rows"""
     from distillclip_amd.model._loss import LossCalculator
+    from distillclip_amd.model.component._tower import HipTower, TowerResult, shared_image_patches
     from distillclip_amd.model.component.output import CLIPOutput
 
-    def run():
+    def run(share):
         (si, st), (ti, tt) = _students(11, TINY['s_img'], TINY['s_txt']), _teachers(11, 128, 2, 8, 32, 13, 97, 64)
         image = torch.from_numpy(synth.images(11, 3, 32)).cuda()
         text = torch.from_numpy(synth.captions(11, 3, 13, 97, 3, 9)).cuda()
         lc = LossCalculator(['out_cos', 'hidden_rep_mse'])
         co = lc.get_control_output()
-        so = CLIPOutput(visual_output=si(image, co), text_output=st(text, co))
+        with shared_image_patches(image, [si._tower, ti._tower] if share else []):
+            vo = si(image, co)
+            with torch.no_grad():
+                tvo = ti(image, co)
+        so = CLIPOutput(visual_output=vo, text_output=st(text, co))
         with torch.no_grad():
-            to = CLIPOutput(visual_output=ti(image, co), text_output=tt(text, co))
+            to = CLIPOutput(visual_output=tvo, text_output=tt(text, co))
         loss, _ = lc(so, to, 'all')
         loss.backward()
         torch.cuda.synchronize()
         return [loss.detach().clone(), so.visual_output.last_representation.detach().clone(), to.text_output.last_representation.clone()] + \
             [m._tower.flat_grad.clone() for m in (si, st)]
 
-    plain, again = run(), run()
-    l = lib()
-    fwd, fwdp = l.dclip_encoder_forward_ex, l.dclip_encoder_forward_patches_ex
-    bwd, bwdp = l.dclip_encoder_backward_ex, l.dclip_encoder_backward_patches_ex
-    monkeypatch.setattr(l, 'dclip_encoder_forward', lambda *a: fwd(*a[:-1], None, a[-1]))
-    monkeypatch.setattr(l, 'dclip_encoder_forward_patches', lambda *a: fwdp(*a[:-1], None, a[-1]))
-    monkeypatch.setattr(l, 'dclip_encoder_backward', lambda *a: bwd(*a[:-3], None, *a[-3:]))
-    monkeypatch.setattr(l, 'dclip_encoder_backward_patches', lambda *a: bwdp(*a[:-3], None, *a[-3:]))
-    ex = run()
+    plain = {share: run(share) for share in (False, True)}
+    again = run(False)
+    fwd, bwd, calls = HipTower.forward, HipTower.backward, []
+
+    def fwd_exporting(self, x, training, *a, tokens_eff=0, maps=None, **kw):
+        assert maps is None and not tokens_eff
+        res = fwd(self, x, training, *a, tokens_eff=tokens_eff, maps=(True, True, [0, 1]), **kw)
+        assert len(res.scores) == len(res.probs) == 2
+        calls.append(training)
+        return TowerResult(*res, [], [])
+
+    def bwd_with_zero_map_grads(self, x, d_out, *a, d_maps=None, **kw):
+        assert d_maps is None
+        z = [torch.zeros((x.shape[0], 1, self.cfg.tokens, self.cfg.tokens), device=x.device) for _ in range(2)]
+        return bwd(self, x, d_out, *a, d_maps=([0, 1], z, z), **kw)
+
+    monkeypatch.setattr(HipTower, 'forward', fwd_exporting)
+    monkeypatch.setattr(HipTower, 'backward', bwd_with_zero_map_grads)
+    mapped = {share: run(share) for share in (False, True)}
+    assert calls.count(True) == 4 and calls.count(False) == 4         # both students trained, both teachers ran, in each run
     # loss and outputs: bit-identical.  Gradients: several step kernels (token-table scatter, LayerNorm and bias column sums) accumulate
     # with f32 atomics, so two plain runs already differ in the order of those additions; the bound is that of f32 reordering
-    for k, (a, a2, b) in enumerate(zip(plain, again, ex)):
-        if k < 3:
-            assert torch.equal(a, b) and torch.equal(a, a2), k
-        else:
-            assert rel_l2(b, a.cpu()) <= 1e-5 and rel_l2(a2, a.cpu()) <= 1e-5, k
+    for share in (False, True):
+        for k, (a, a2, b) in enumerate(zip(plain[share], again, mapped[share])):
+            if k < 3:
+                assert torch.equal(a, b) and torch.equal(plain[False][k], a2), (share, k)
+            else:
+                assert rel_l2(b, a.cpu()) <= 1e-5 and rel_l2(a2, plain[False][k].cpu()) <= 1e-5, (share, k)
 
 
 # ---- 5. determinism at the l_clip shapes ---------------------------------------------------------------------------------------------

@@ -42,7 +42,7 @@ def test_trainable_clip_tower_plan_is_host_side():
     l.dclip_encoder_grad_bucket(h2, 1, ctypes.byref(first), ctypes.byref(end))
     assert (first.value, end.value) == (5 + 12 * 3, 5 + 12 * 4)                                  # the last layer completes first
     with pytest.raises(ValueError, match='inference-only'):                                       # the frozen kind still refuses to train
-        l.dclip_encoder_forward(h0, 256, 1, (ctypes.c_void_p * 56)(), 256, 256, 1 << 40, 1, 256, None, None, 0, None)
+        l.dclip_encoder_forward(h0, 256, None, 1, (ctypes.c_void_p * 56)(), 256, 256, 1 << 40, 1, 256, None, None, 0, None, None)
     for h in (h2, h0):
         l.dclip_encoder_destroy(h)
     assert not l.dclip_encoder_create(ctypes.byref(mk(kind=3)))

@@ -150,7 +150,7 @@ def test_tiny_dual_training_step_vs_reference_golden(tiny, case):
 
 def test_shared_image_patches_between_teacher_and_student(tiny):
     """teacher and student image towers take their patch rows from ONE im2row when they cut the same images the same way
-    (dclip_encoder_forward_patches / _backward_patches; reference dual_distill_model.py:107-109: both see `image`): embeddings and every
+    (the `patches` argument of dclip_encoder_forward / _backward; reference dual_distill_model.py:107-109: both see `image`): embeddings and every
     student gradient — the patch-embedding wgrad reads those rows — equal the separately converted run (embeddings bit for bit)"""
     from distillclip_amd.model.component import _tower
     image = torch.from_numpy(tiny['image']).cuda()
