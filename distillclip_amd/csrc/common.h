@@ -27,6 +27,13 @@ void dclip_set_error(const char* fmt, ...);
         }                                         \
     } while (0)
 
+// row moves of the last block execution run on the picked class / EOT rows only (elementwise.hip; used by encoder.cpp, not C ABI):
+//   rows_pick   : dst[b] = src[idx[b]]                                       (compact [B, .] from [B*N, .])
+//   rows_expand : dst[r] = r == idx[r / N] ? src[r / N] : 0 for every r < B*N (full [B*N, .] from compact [B, .])
+// idx[b] lies in sample b's rows (dclip_pick_index); row_bytes a multiple of 16, buffers 16-byte aligned.
+extern "C" int dclip_rows_pick(const void* src, void* dst, const int32_t* idx, int64_t B, int64_t row_bytes, void* stream);
+extern "C" int dclip_rows_expand(const void* src, void* dst, const int32_t* idx, int64_t B, int64_t N, int64_t row_bytes, void* stream);
+
 // launch trace (capi.cpp): open() returns false unless dclip_trace_begin() enabled tracing
 bool dclip_trace_open(int kind, double flops, double bytes, void* stream, int* slot, int d0 = 0, int d1 = 0, int d2 = 0, int d3 = 0);
 void dclip_trace_close(int slot, void* stream);

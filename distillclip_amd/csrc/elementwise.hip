@@ -412,6 +412,27 @@ __global__ __launch_bounds__(256) void axpy_colsum_kernel(float* __restrict__ ds
     if (c < D) unsafeAtomicAdd(colsum + c, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
 }
 
+// dst[b] = src[idx[b]]: the picked class / EOT rows of a [B*N, .] tensor as a compact [B, .] one (16-byte chunks; q = chunks per row)
+__global__ __launch_bounds__(256) void rows_pick_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, const int* __restrict__ idx,
+                                                        int B, int q) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int64_t s = (int64_t)idx[b] * q, d = (int64_t)b * q;
+    for (int i = threadIdx.x; i < q; i += 256) dst[d + i] = src[s + i];
+}
+
+// its adjoint's shape: dst [B*N, .] = compact row b at row idx[b] of sample b, zeros everywhere else (every row written)
+__global__ __launch_bounds__(256) void rows_expand_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, const int* __restrict__ idx,
+                                                          int N, int q, int64_t total) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < total; c += stride) {
+        const int64_t row = c / q;
+        const int64_t b = row / N;
+        const int j = (int)(c - row * q);
+        dst[c] = row == idx[b] ? src[b * q + j] : u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
 inline int grid_for(int64_t work, int per_block = 256, int cap = 2048 * 4) {
     int64_t g = (work + per_block - 1) / per_block;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -614,3 +635,20 @@ extern "C" int dclip_axpy_f32(float* dst, const float* src, void* dst_bf16, int6
     return dclip_check_launch("dclip_axpy_f32");
 }
 
+
+extern "C" int dclip_rows_pick(const void* src, void* dst, const int32_t* idx, int64_t B, int64_t row_bytes, void* stream) {
+    DCLIP_REQUIRE(src && dst && idx && B > 0 && row_bytes > 0 && row_bytes % 16 == 0 && B < (1LL << 31), "dclip_rows_pick: bad argument");
+    DCLIP_REQUIRE(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0, "dclip_rows_pick: misaligned buffer");
+    hipLaunchKernelGGL(rows_pick_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, (u32x4*)dst, idx, (int)B,
+                       (int)(row_bytes / 16));
+    return dclip_check_launch("dclip_rows_pick");
+}
+
+extern "C" int dclip_rows_expand(const void* src, void* dst, const int32_t* idx, int64_t B, int64_t N, int64_t row_bytes, void* stream) {
+    DCLIP_REQUIRE(src && dst && idx && B > 0 && N > 0 && row_bytes > 0 && row_bytes % 16 == 0, "dclip_rows_expand: bad argument");
+    DCLIP_REQUIRE(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0, "dclip_rows_expand: misaligned buffer");
+    const int64_t q = row_bytes / 16, total = B * N * q;
+    hipLaunchKernelGGL(rows_expand_kernel, dim3(grid_for(total, 1024)), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, (u32x4*)dst, idx,
+                       (int)N, (int)q, total);
+    return dclip_check_launch("dclip_rows_expand");
+}

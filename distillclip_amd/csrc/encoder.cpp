@@ -176,6 +176,15 @@ struct Work {
     float* wg_dummy;                       // Mix: [2, H, H] sink for conv_l / conv_w gradients when those parameters are frozen
     float* mix_ws; size_t mix_ws_bytes;    // Mix: per-workgroup weight-gradient partials of dclip_attn_mix_bwd
     void* tn_ws; size_t tn_ws_bytes;       // partial tiles of the 256 x 256 wgrad launches (dclip_gemm_tn_acc)
+    // the last block execution run on the B picked rows only (prune_last): compact [B, .] operands.  Training: the first B rows of
+    // that execution's own saved buffers (the block's [R][M, .] wgrad operands then hold them at the start of slot R - 1) and of
+    // X[nex]; inference: buffers of their own, so that the shared residual stream keeps X[nex - 1] for last_layer_output.
+    bf16_t* ctx_full;                      // the execution's attention output, all M rows, before its picked rows are gathered
+    void *xr, *xmc, *xoc;                  // gathered residual in, residual after the attention branch, output (stream dtype)
+    bf16_t *cctx, *ch2, *cu;               // out_proj / fc1 / fc2 operands
+    uint8_t* cz;                           // saved gelu' (training)
+    float *cmean2, *crstd2;                // LN2 statistics (training)
+    float* Gc;                             // training: [B, D] residual-stream gradient of the compact rows
     AttnPath path;                         // the score stage every buffer above was sized for
     size_t bytes;
 };
@@ -228,6 +237,22 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
                 t.h1 = h1 + r * M * D; t.ctx = ctx + r * M * D; t.h2 = h2 + r * M * D; t.u = u + r * M * F;
             }
         }
+    }
+    // compact operands of the last execution (prune_last)
+    {
+        ExecSave& s = w.ex[nex - 1];
+        if (save) {
+            w.ctx_full = s.h2;                                       // rows B.. of the h2 slot are unused by a pruned execution
+            w.cctx = s.ctx; w.ch2 = s.h2; w.cu = s.u; w.cz = s.z; w.cmean2 = s.mean2; w.crstd2 = s.rstd2;
+            w.xmc = s.x_mid;
+            w.xr = w.xoc = w.X[nex];                                 // the gathered input is consumed (out_proj) before fc2 writes the output
+        } else {
+            w.ctx_full = shared.ctx;
+            w.cctx = b.take<bf16_t>(B * D); w.ch2 = shared.h1; w.cu = shared.u; w.cz = nullptr; w.cmean2 = w.crstd2 = nullptr;
+            const size_t es = w.h16 ? 2 : 4;
+            w.xr = b.take<char>(B * D * es); w.xmc = b.take<char>(B * D * es); w.xoc = b.take<char>(B * D * es);
+        }
+        w.Gc = save ? b.take<float>(B * D) : nullptr;
     }
     w.patches = p.image ? b.take<bf16_t>(M * p.K) : (p.compressed ? b.take<bf16_t>(M * p.c.embed_rank) : nullptr);
     w.tok_table = b.take<float>((int64_t)N * D);
@@ -344,13 +369,33 @@ int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w
 // another workspace in between) clears the seeds itself, so the call is self-contained whatever the caller does.
 // exported: which head-mean maps (bit 0 score, bit 1 probabilities, per block execution) the most recent training forward of the workspace
 // `exported_ws` wrote; the backward accepts map gradients for those only.
+// pruned: per workspace, whether its most recent forward ran the last block execution on the picked rows only (prune_last):
+// last_layer_output then re-runs that execution on all rows, and the backward takes the compact path and refuses a gradient
+// for that execution's hidden state.
 struct dclip_encoder {
     Plan p;
     mutable std::atomic<void*> seeded{nullptr};
     mutable std::mutex maps_mu;
     mutable void* exported_ws = nullptr;
     mutable std::vector<uint8_t> exported;
+    mutable std::vector<std::pair<void*, bool>> pruned;    // (workspace, pruned), guarded by maps_mu
 };
+
+namespace {
+void note_pruned(const dclip_encoder* e, void* ws, bool pruned) {
+    std::lock_guard<std::mutex> lk(e->maps_mu);
+    for (auto& q : e->pruned)
+        if (q.first == ws) { q.second = pruned; return; }
+    if (e->pruned.size() >= 16) e->pruned.erase(e->pruned.begin());
+    e->pruned.emplace_back(ws, pruned);
+}
+bool was_pruned(const dclip_encoder* e, const void* ws) {
+    std::lock_guard<std::mutex> lk(e->maps_mu);
+    for (const auto& q : e->pruned)
+        if (q.first == ws) return q.second;
+    return false;
+}
+}  // namespace
 
 extern "C" dclip_encoder* dclip_encoder_create(const dclip_encoder_cfg* cfg) {
     if (!cfg) { dclip_set_error("dclip_encoder_create: null cfg"); return nullptr; }
@@ -398,6 +443,66 @@ inline BX bexec(const Plan& p, int l, int r) {
     const TB t = tblock(p, l);
     return BX{t.ln1w, t.ln1b, t.ln2w, t.ln2b, t.inw, t.inb, t.outw, t.outb, t.fcw, t.fcb, t.prw, t.prb, -1, -1};
 }
+
+// the parameters one block execution's forward reads
+struct EP { const float *n1w, *n1b, *n2w, *n2b, *bq, *bp, *b1, *b2, *wl, *ww; };
+inline EP exec_params(const Plan& p, const void* const* params, int l, int r) {
+    const BX bx = bexec(p, l, r);
+    EP e{PF(params, bx.n1w), PF(params, bx.n1b), PF(params, bx.n2w), PF(params, bx.n2b), PF(params, bx.qkvb), PF(params, bx.prb),
+         PF(params, bx.f1b), PF(params, bx.f2b), nullptr, nullptr};
+    if (p.mixing) { e.wl = PF(params, bx.cl); e.ww = PF(params, bx.cw); }
+    return e;
+}
+
+// first half of a block execution, on all M rows: LN1 -> QKV -> score stage (s.qkv, s.ctx and the path's saved score tensors)
+int exec_attn(const Plan& p, AttnPath path, const ExecSave& s, const bf16_t* W, int l, const EP& e, bool h16, const void* xin, int64_t B,
+              int64_t N, void* st) {
+    const int64_t D = p.D, M = B * N;
+    CK(ln_stream(h16, xin, D, nullptr, e.n1w, e.n1b, s.h1, D, DCLIP_OUT_BF16, s.mean1, s.rstd1, M, D, st));
+    CK(gemm(s.h1, D, W + p.bw[l].qkv, D, s.qkv, 3 * D, M, 3 * D, D, e.bq, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+    return attn_forward(path, p, s, e.wl, e.ww, B, N, st);
+}
+
+// second half, row-local, on `rows` rows: x_mid = xin + proj(ctx), xout = x_mid + fc2(act(fc1(LN2(x_mid)))).  z (nullable) receives
+// the saved activation derivative, mean2 / rstd2 (nullable) the LN2 statistics.
+int exec_mlp(const Plan& p, const bf16_t* W, int l, const EP& e, bool h16, const bf16_t* ctx, const void* xin, void* x_mid, bf16_t* h2,
+             float* mean2, float* rstd2, bf16_t* u, uint8_t* z, void* xout, int64_t rows, void* st) {
+    const int64_t D = p.D, F = p.F;
+    const auto& bw = p.bw[l];
+    const int sdt = h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;            // dtype of the residual stream
+    const int act = p.student ? (z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU);
+    CK(gemm(ctx, D, W + bw.proj, D, x_mid, D, rows, D, D, e.bp, 0, nullptr, nullptr, xin, D, sdt, 0, nullptr, st));
+    CK(ln_stream(h16, x_mid, D, nullptr, e.n2w, e.n2b, h2, D, DCLIP_OUT_BF16, mean2, rstd2, rows, D, st));
+    CK(gemm(h2, D, W + bw.fc1, D, u, F, rows, F, D, e.b1, act, nullptr, z, nullptr, 0, 0, 0, nullptr, st));
+    return gemm(u, F, W + bw.fc2, F, xout, D, rows, D, F, e.b2, 0, nullptr, nullptr, x_mid, D, sdt, 0, nullptr, st);
+}
+
+// Scratch of dclip_encoder_last_layer_output: after a pruned forward it re-runs the last execution on all rows into buffers of its
+// own (a pending backward's saved activations stay untouched).  h1 comes first: it is also the bf16 final-LN output, the whole
+// scratch an unpruned forward needs.
+size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base, ExecSave& t, void*& xout) {
+    Bump b(base);
+    const int64_t N = p.N, M = B * N, D = p.D, F = p.F, SN = B * p.H * N * p.Np;
+    const size_t es = h16 ? 2 : 4;
+    t = ExecSave{};
+    t.h1 = b.take<bf16_t>(M * D); t.h2 = t.h1;
+    t.qkv = b.take<bf16_t>(M * 3 * D);
+    t.S = path == AttnPath::Unfused ? b.take<float>(SN) : nullptr;
+    t.P = path == AttnPath::Unfused ? b.take<bf16_t>(SN) : nullptr;
+    t.Rm = p.mixing ? b.take<bf16_t>(SN) : t.P;
+    t.stats = path == AttnPath::Mix ? b.take<float>(B * p.H * N) : nullptr;
+    t.ctx = b.take<bf16_t>(M * D);
+    t.x_mid = b.take<char>(M * D * es);
+    t.u = b.take<bf16_t>(M * F);
+    xout = b.take<char>(M * D * es);
+    return b.off;
+}
+
+// DCLIP_PRUNE_LAST=0 (read once): every forward runs its last block execution on all rows
+inline bool prune_last_enabled() {
+    static const int v = [] { const char* e = getenv("DCLIP_PRUNE_LAST"); return e ? atoi(e) : 1; }();
+    return v != 0;
+}
 }  // namespace
 
 extern "C" int dclip_encoder_prepare(const dclip_encoder* e, const void* const* params, void* wcache, void* st) {
@@ -428,13 +533,22 @@ extern "C" int dclip_encoder_prepare(const dclip_encoder* e, const void* const* 
 }
 
 // The backward starts from a residual-stream gradient that is non-zero in B of the M rows (the picked class / EOT rows): its f32
-// accumulator and the fc2 operand slot of the last execution start as zeros.  Those fills used to open dclip_encoder_backward, i.e. sat
+// accumulator and the fc2 operand slot of the last execution start as zeros.  After a pruned forward only the compact [B, D]
+// accumulator w.Gc does: the full one is written whole from it (dclip_rows_expand) and the fc2 operand rows are the B compact ones,
+// every one of which the final LayerNorm backward writes.  Those fills used to open dclip_encoder_backward, i.e. sat
 // on the critical path right after the loss; issued at the end of the training forward, they run on the tower's stream while the other
 // towers finish and the loss is evaluated (the buffers are not touched by the forward).  (Round 5: the bf16 copy w.Gb is no longer
 // cleared — every row of it is written by the first execution's LayerNorm backward before anything reads it.)
-static int clear_backward_seeds(const Plan& p, const Work& w, int64_t M, void* st) {
+static int clear_backward_seeds(const Plan& p, const Work& w, int64_t M, int64_t B, bool pruned, void* st) {
     const int64_t D = p.D;
     hipStream_t hs = (hipStream_t)st;
+    if (pruned) {
+        if (hipMemsetAsync(w.Gc, 0, (size_t)B * D * 4, hs) != hipSuccess) {
+            dclip_set_error("dclip_encoder: clearing the backward seeds failed");
+            return DCLIP_ELAUNCH;
+        }
+        return DCLIP_OK;
+    }
     bf16_t* gb_last = w.gb_f2 + (int64_t)(p.R - 1) * M * D;
     if (hipMemsetAsync(w.G, 0, (size_t)M * D * 4, hs) != hipSuccess || hipMemsetAsync(gb_last, 0, (size_t)M * D * 2, hs) != hipSuccess) {
         dclip_set_error("dclip_encoder: clearing the backward seeds failed");
@@ -509,40 +623,40 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     if (emb_out) CK(export_stream(w.h16, (!p.student && p.image) ? w.x0 : w.X[0], emb_out, M * D, st));
 
     // ---- blocks --------------------------------------------------------------------------------------------
+    // Only the picked token of each sample (class token / EOT = argmax of the ids) leaves the tower, and after the last execution's
+    // attention everything is row-local: unless its hidden state or maps are exported, that execution's out_proj, LN2 and MLP run on
+    // the B picked rows only (its attention still runs on all M rows: the picked queries attend to every key).
+    CK(dclip_pick_index(p.image ? nullptr : (const int64_t*)input, p.N, w.pick, B, N, st));
+    const bool prune = prune_last_enabled() && !(rep_out && rep_out[nex - 1]) && !mapped[nex - 1];
     for (int ei = 0; ei < nex; ++ei) {
         const int l = ei / p.R, r = ei % p.R;
-        const auto& bw = p.bw[l];
-        ExecSave& s = w.ex[ei];
-        const float *n1w, *n1b, *n2w, *n2b, *bq, *bp, *b1, *b2, *wl = nullptr, *ww = nullptr;
-        {
-            const BX bx = bexec(p, l, r);
-            n1w = PF(params, bx.n1w); n1b = PF(params, bx.n1b); n2w = PF(params, bx.n2w); n2b = PF(params, bx.n2b);
-            bq = PF(params, bx.qkvb); bp = PF(params, bx.prb); b1 = PF(params, bx.f1b); b2 = PF(params, bx.f2b);
-            if (p.mixing) { wl = PF(params, bx.cl); ww = PF(params, bx.cw); }
-        }
-        void* xin = w.X[ei];
-        void* xout = w.X[ei + 1];
-        const int sdt = w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;        // dtype of the residual stream
-        CK(ln_stream(w.h16, xin, D, nullptr, n1w, n1b, s.h1, D, DCLIP_OUT_BF16, s.mean1, s.rstd1, M, D, st));
-        CK(gemm(s.h1, D, W + bw.qkv, D, s.qkv, 3 * D, M, 3 * D, D, bq, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
-        CK(attn_forward(w.path, p, s, wl, ww, B, N, st));
+        const ExecSave& s = w.ex[ei];
+        const EP ep = exec_params(p, params, l, r);
+        const bool compact = prune && ei == nex - 1;
+        ExecSave sa = s;
+        if (compact) sa.ctx = w.ctx_full;
+        CK(exec_attn(p, w.path, sa, W, l, ep, w.h16, w.X[ei], B, N, st));
         // before the next execution reuses the inference set's qkv
-        if (mapped[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, wl, map_s[ei], map_p[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
-        CK(gemm(s.ctx, D, W + bw.proj, D, s.x_mid, D, M, D, D, bp, 0, nullptr, nullptr, xin, D, sdt, 0, nullptr, st));
-        CK(ln_stream(w.h16, s.x_mid, D, nullptr, n2w, n2b, s.h2, D, DCLIP_OUT_BF16, s.mean2, s.rstd2, M, D, st));
-        CK(gemm(s.h2, D, W + bw.fc1, D, s.u, F, M, F, D, b1, p.student ? (s.z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (s.z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU), nullptr, s.z, nullptr, 0, 0, 0, nullptr, st));
-        CK(gemm(s.u, F, W + bw.fc2, F, xout, D, M, D, F, b2, 0, nullptr, nullptr, s.x_mid, D, sdt, 0, nullptr, st));
+        if (mapped[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, ep.wl, map_s[ei], map_p[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
+        if (!compact) {
+            CK(exec_mlp(p, W, l, ep, w.h16, s.ctx, w.X[ei], s.x_mid, s.h2, s.mean2, s.rstd2, s.u, s.z, w.X[ei + 1], M, st));
+        } else {
+            CK(dclip_rows_pick(w.ctx_full, w.cctx, w.pick, B, D * 2, st));
+            CK(dclip_rows_pick(w.X[ei], w.xr, w.pick, B, D * (w.h16 ? 2 : 4), st));
+            CK(exec_mlp(p, W, l, ep, w.h16, w.cctx, w.xr, w.xmc, w.ch2, w.cmean2, w.crstd2, w.cu, w.cz, w.xoc, B, st));
+        }
         // optional export of this execution's hidden state (ControlOutput.need_rep: _common.py:156-158, weight_share_model.py:211)
-        if (rep_out && rep_out[ei]) CK(export_stream(w.h16, xout, rep_out[ei], M * D, st));
+        if (rep_out && rep_out[ei]) CK(export_stream(w.h16, w.X[ei + 1], rep_out[ei], M * D, st));
     }
 
-    // ---- final norm + projection on the picked token only (class token / EOT = argmax of the ids) ----------------
-    CK(dclip_pick_index(p.image ? nullptr : (const int64_t*)input, p.N, w.pick, B, N, st));
+    // ---- final norm + projection on the picked token only ------------------------------------------------------
     const int f = p.p_final;
-    CK(ln_stream(w.h16, w.X[nex], D, w.pick, PF(params, f), PF(params, f + 1), w.hf, D, DCLIP_OUT_BF16, w.meanf, w.rstdf, B, D, st));
+    CK(ln_stream(w.h16, prune ? w.xoc : w.X[nex], D, prune ? nullptr : w.pick, PF(params, f), PF(params, f + 1), w.hf, D, DCLIP_OUT_BF16,
+                 w.meanf, w.rstdf, B, D, st));
     CK(gemm(w.hf, D, W + p.w_head, D, last_representation, E, B, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, 1, 0, nullptr, st));
+    note_pruned(e, workspace, prune);
     if (training) {
-        CK(clear_backward_seeds(p, w, M, st));
+        CK(clear_backward_seeds(p, w, M, B, prune, st));
         e->seeded.store(workspace, std::memory_order_release);
         std::lock_guard<std::mutex> lk(e->maps_mu);
         e->exported_ws = workspace;
@@ -554,7 +668,18 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
 // All-token output of the final norm + projection (reference _common.py:210-215, text_encoder.py:69-72,
 // weight_share_model.py:363-366 / :503-506: `last_layer_output`, of which `last_representation` is one row per sample).  The
 // training path projects only the picked row; this call produces the whole [B*N, E] tensor on request from the residual
-// stream the most recent forward of this tower left in `workspace`.
+// stream the most recent forward of this tower left in `workspace`.  If that forward ran its last block execution on the picked rows
+// only, the execution is run again on all rows from X[nex - 1], in `scratch`, on the same kernels: the result is the one an
+// unpruned forward leaves, and nothing a pending backward reads is touched.
+extern "C" size_t dclip_encoder_last_layer_output_scratch_bytes(const dclip_encoder* e, int64_t B, int training) {
+    if (!e || B <= 0) return 0;
+    Work w;
+    layout(e->p, B, training != 0, nullptr, w);
+    ExecSave t;
+    void* xout;
+    return llo_scratch(e->p, w.path, w.h16, B, nullptr, t, xout);
+}
+
 extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B, const void* const* params, const void* wcache,
                                                void* workspace, size_t ws_bytes, int training, void* scratch, float* out, void* st) {
     DCLIP_REQUIRE(e && params && wcache && workspace && scratch && out, "dclip_encoder_last_layer_output: null argument");
@@ -567,7 +692,18 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
     const bf16_t* W = (const bf16_t*)wcache;
     const int64_t M = B * p.N, D = p.D, E = p.E;
     const int nex = p.L * p.R, f = p.p_final;
-    CK(ln_stream(w.h16, w.X[nex], D, nullptr, PF(params, f), PF(params, f + 1), scratch, D, DCLIP_OUT_BF16, nullptr, nullptr, M, D, st));
+    const void* xlast = w.X[nex];
+    if (was_pruned(e, workspace)) {
+        ExecSave t;
+        void* xout;
+        llo_scratch(p, w.path, w.h16, B, scratch, t, xout);
+        const int ei = nex - 1, l = ei / p.R;
+        const EP ep = exec_params(p, params, l, ei % p.R);
+        CK(exec_attn(p, w.path, t, W, l, ep, w.h16, w.X[ei], B, p.N, st));
+        CK(exec_mlp(p, W, l, ep, w.h16, t.ctx, w.X[ei], t.x_mid, t.h2, nullptr, nullptr, t.u, nullptr, xout, M, st));
+        xlast = xout;
+    }
+    CK(ln_stream(w.h16, xlast, D, nullptr, PF(params, f), PF(params, f + 1), scratch, D, DCLIP_OUT_BF16, nullptr, nullptr, M, D, st));
     CK(gemm(scratch, D, W + p.w_head, D, out, E, M, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, 1, 0, nullptr, st));
     return DCLIP_OK;
 }
@@ -615,6 +751,13 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     const bf16_t* W = (const bf16_t*)wcache;
     const int64_t N = p.N, D = p.D, F = p.F, E = p.E, M = B * N;
     const int nex = p.L * p.R;
+    // a pruned forward (its last execution on the picked rows only) keeps no hidden state of that execution and exports no map of it
+    const bool pruned = was_pruned(e, workspace);
+    DCLIP_REQUIRE(!pruned || !(d_rep && d_rep[nex - 1]),
+                  "dclip_encoder_backward: a gradient for the hidden state of block execution %d, which the forward ran on the class / EOT "
+                  "rows only (request that hidden state in the forward, or set DCLIP_PRUNE_LAST=0)", nex - 1);
+    DCLIP_REQUIRE(!pruned || !has_mg[nex - 1],
+                  "dclip_encoder_backward: a map gradient for block execution %d, which the forward ran on the class / EOT rows only", nex - 1);
     auto GR = [&](int i) -> float* { return (float*)grads[i]; };
     hipStream_t hs = (hipStream_t)st;
 
@@ -622,7 +765,7 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     // (clear_backward_seeds) unless a backward has consumed them since: then they are cleared here
     {
         void* expect = workspace;
-        if (!e->seeded.compare_exchange_strong(expect, nullptr, std::memory_order_acq_rel)) CK(clear_backward_seeds(p, w, M, st));
+        if (!e->seeded.compare_exchange_strong(expect, nullptr, std::memory_order_acq_rel)) CK(clear_backward_seeds(p, w, M, B, pruned, st));
     }
     // ---- head + final norm -----------------------------------------------------------------------------------
     const int f = p.p_final;
@@ -638,8 +781,9 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     // linear that wrote into that residual stream (fc2 of the previous execution / attn.proj of this one)
     const int R = p.R;
     bf16_t* gb_last = w.gb_f2 + (int64_t)(R - 1) * M * D;            // fc2 of the last execution reads slot R - 1
-    CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)w.X[nex], D, w.pick, PF(params, f), w.meanf, w.rstdf, w.G, D, gb_last, D, GR(f), GR(f + 1),
-                           GR(bexec(p, (nex - 1) / p.R, 0).f2b), B, D, st));
+    // (pruned: the compact rows of the last execution's output and of its gradient, identity pick)
+    CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)(pruned ? w.xoc : w.X[nex]), D, pruned ? nullptr : w.pick, PF(params, f), w.meanf, w.rstdf,
+                           pruned ? w.Gc : w.G, D, gb_last, D, GR(f), GR(f + 1), GR(bexec(p, (nex - 1) / p.R, 0).f2b), B, D, st));
     // gradient bucket 0 (final norm + head) is complete: every launch that writes it is enqueued on `st`
     if (on_bucket) on_bucket(cb_user, 0);
 
@@ -659,20 +803,34 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
         bf16_t* dqkv = w.dqkv + (int64_t)r * M * 3 * D;
         const int64_t MR = (int64_t)R * M;
         const ExecSave& s0 = w.ex[ei - r];                               // execution r = 0 of this block: base of the [R][M, .] operands
+        // pruned last execution: its out_proj / MLP backward runs on its B compact rows, which sit at the start of its slots, so the
+        // last block's fc1 / fc2 / out_proj wgrads contract over (R - 1) M + B rows
+        const bool compact = pruned && ei == nex - 1;
+        const int64_t Mx = compact ? B : M;
+        const int64_t MRw = pruned && l == p.L - 1 ? (int64_t)(R - 1) * M + B : MR;
         // gradient arriving directly at this execution's output (feature-MSE terms): G += d_rep[ei], refresh the bf16 copy
         if (d_rep && d_rep[ei]) CK(dclip_axpy_f32(w.G, d_rep[ei], gb_f2, M * D, GR(bx.f2b), D, st));
         // MLP: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
-        CK(dclip_gemm_nt(gb_f2, D, W + bw.fc2_t, D, dbig, F, M, F, D, 1.f, nullptr, DCLIP_ACT_MULAUX, s.z, nullptr, nullptr, 0, 0, 0, nullptr,
+        CK(dclip_gemm_nt(gb_f2, D, W + bw.fc2_t, D, dbig, F, Mx, F, D, 1.f, nullptr, DCLIP_ACT_MULAUX, s.z, nullptr, nullptr, 0, 0, 0, nullptr,
                          GR(bx.f1b), st));                                        // dz = (G W2) o gelu'(z) ; db1 += colsum(dz)
-        if (r == 0 && GR(bx.f2w)) CK(dclip_gemm_tn_acc(w.gb_f2, D, s0.u, F, GR(bx.f2w), F, MR, D, F, wsplits(MR, D, F), w.tn_ws, w.tn_ws_bytes, st));
-        if (r == 0 && GR(bx.f1w)) CK(dclip_gemm_tn_acc(w.dbig, F, s0.h2, D, GR(bx.f1w), D, MR, F, D, wsplits(MR, F, D), w.tn_ws, w.tn_ws_bytes, st));
-        CK(gemm(dbig, F, W + bw.fc1_t, F, w.dh, D, M, D, F, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
-        CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)s.x_mid, D, nullptr, PF(params, bx.n2w), s.mean2, s.rstd2, w.G, D, gb_pr, D, GR(bx.n2w), GR(bx.n2b),
-                               GR(bx.prb), M, D, st));
+        if (r == 0 && GR(bx.f2w)) CK(dclip_gemm_tn_acc(w.gb_f2, D, s0.u, F, GR(bx.f2w), F, MRw, D, F, wsplits(MRw, D, F), w.tn_ws, w.tn_ws_bytes, st));
+        if (r == 0 && GR(bx.f1w)) CK(dclip_gemm_tn_acc(w.dbig, F, s0.h2, D, GR(bx.f1w), D, MRw, F, D, wsplits(MRw, F, D), w.tn_ws, w.tn_ws_bytes, st));
+        CK(gemm(dbig, F, W + bw.fc1_t, F, w.dh, D, Mx, D, F, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+        CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)s.x_mid, D, nullptr, PF(params, bx.n2w), s.mean2, s.rstd2, compact ? w.Gc : w.G, D, gb_pr, D,
+                               GR(bx.n2w), GR(bx.n2b), GR(bx.prb), Mx, D, st));
         // attention: x_mid = x_in + proj(attn(LN1(x_in)))
-        if (r == 0 && GR(bx.prw)) CK(dclip_gemm_tn_acc(w.gb_pr, D, s0.ctx, D, GR(bx.prw), D, MR, D, D, wsplits(MR, D, D), w.tn_ws, w.tn_ws_bytes, st));
+        if (r == 0 && GR(bx.prw)) CK(dclip_gemm_tn_acc(w.gb_pr, D, s0.ctx, D, GR(bx.prw), D, MRw, D, D, wsplits(MRw, D, D), w.tn_ws, w.tn_ws_bytes, st));
         bf16_t* dctx = w.dh;
-        CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx, D, M, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+        if (!compact) {
+            CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx, D, M, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+        } else {
+            // the compact dctx goes through this execution's dqkv slot (written by the attention backward only after it is read);
+            // dctx and the residual-stream gradient are then the full-M tensors, zero outside the picked rows
+            bf16_t* dctx_c = dqkv;
+            CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx_c, D, B, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+            CK(dclip_rows_expand(dctx_c, dctx, w.pick, B, N, D * 2, st));
+            CK(dclip_rows_expand(w.Gc, w.G, w.pick, B, N, D * 4, st));
+        }
         CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, has_mg[ei] ? &mgrad[ei] : nullptr, st));
         if (r == 0 && GR(bx.qkvw)) CK(dclip_gemm_tn_acc(w.dqkv, 3 * D, s0.h1, D, GR(bx.qkvw), D, MR, 3 * D, D, wsplits(MR, 3 * D, D), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && params[bx.qkvb] && GR(bx.qkvb)) CK(dclip_colsum_acc(w.dqkv, 3 * D, GR(bx.qkvb), MR, 3 * D, st));

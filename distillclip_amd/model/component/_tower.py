@@ -364,9 +364,10 @@ class HipTower:
         B, training, tokens_eff = last
         if tokens_eff:
             raise RuntimeError('last_layer_output is not available when the text teacher ran on a caption prefix (max_tokens hint)')
-        N, D, E = self.cfg.tokens, self.cfg.width, self.cfg.out_dim
+        N, E = self.cfg.tokens, self.cfg.out_dim
         dev = self.workspace.device
-        scratch = torch.empty((B * N, D), dtype=torch.bfloat16, device=dev)
+        scratch = torch.empty(lib().dclip_encoder_last_layer_output_scratch_bytes(self._handle, B, 1 if training else 0), dtype=torch.uint8,
+                              device=dev)
         out = torch.empty((B, N, E), dtype=torch.float32, device=dev)
         lib().dclip_encoder_last_layer_output(self._handle, B, _ptr_array(self._params()), self.wcache.data_ptr(),
                                               self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,

@@ -422,8 +422,12 @@ int dclip_encoder_forward(const dclip_encoder* enc, const void* input, const voi
                           float* const* rep_out, float* emb_out, int64_t tokens_eff, const dclip_attn_maps* maps, void* stream);
 /* last_layer_output (reference output.py:16-35; _common.py:210-215, text_encoder.py:69-72, weight_share_model.py:363-366,
  * :503-506): final norm + projection of EVERY token, f32 [B*N, E], computed on request from the residual stream the most
- * recent dclip_encoder_forward(enc, ..., B, training) left in `workspace` (tokens_eff must have been 0).  scratch: bf16
- * [B*N, D] caller-owned.  last_representation is the class-token / EOT row of this tensor. */
+ * recent dclip_encoder_forward(enc, ..., B, training) left in `workspace` (tokens_eff must have been 0).  scratch: caller-owned,
+ * dclip_encoder_last_layer_output_scratch_bytes(enc, B, training) bytes, 256-byte aligned.  A forward that exported neither the
+ * hidden state nor a map of the last block execution runs that execution's out_proj / LN2 / MLP on the class / EOT rows only
+ * (DCLIP_PRUNE_LAST=0: on all rows); this call then runs it again on all rows in `scratch`, leaving `workspace` untouched.
+ * last_representation is the class-token / EOT row of this tensor. */
+size_t dclip_encoder_last_layer_output_scratch_bytes(const dclip_encoder* enc, int64_t B, int training);
 int dclip_encoder_last_layer_output(const dclip_encoder* enc, int64_t B, const void* const* params, const void* wcache,
                                     void* workspace, size_t ws_bytes, int training, void* scratch, float* out, void* stream);
 /* input / patches: what the forward ran on (caller-made patch rows are the patch-embedding wgrad's operand).
@@ -437,7 +441,8 @@ int dclip_encoder_last_layer_output(const dclip_encoder* enc, int64_t B, const v
  * forward clears them at its end (beside the other towers' work) and the handle remembers the workspace it did that for; a backward that
  * does not find ITS workspace there — a second backward on one forward, a retry, another workspace used in between — clears them itself.
  * Either way one call = the gradients of the most recent training forward of that workspace for the given d_*; gradients ACCUMULATE (+=)
- * into `grads` as everywhere. */
+ * into `grads` as everywhere.  After a forward that ran its last block execution on the class / EOT rows only (see last_layer_output),
+ * d_rep[layers * repeats - 1] and map gradients of that execution are refused (DCLIP_EINVAL). */
 typedef void (*dclip_bucket_cb)(void* user, int32_t bucket);
 int dclip_encoder_backward(const dclip_encoder* enc, const void* input, const void* patches, int64_t B, const void* const* params,
                            void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
