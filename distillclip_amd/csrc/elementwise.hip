@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void pick_index_kernel(const int64_t* __restri
         int pos = INT_MAX;
         for (int n = lane; n < id_stride; n += 64) {
             const long long v = ids[(int64_t)b * id_stride + n];
-            if (v > m) { m = v; pos = n; }
+            if (v > m || n == lane) { m = v; pos = n; }     // the lane's first id counts even at LLONG_MIN (all-minimum rows pick 0)
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
