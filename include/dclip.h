@@ -80,7 +80,8 @@ int dclip_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* 
 /*
  * dW[P,Q] (f32, ld = ldo) += sum_m A[m,P] * B[m,Q]         (weight gradient of nn.Linear: dY^T · X)
  *   autograd of the reference linears listed above (student only: weight_share_model.py:90,132,177,364).
- *   A bf16 [M,P] (lda), B bf16 [M,Q] (ldb).  P % 16 == 0, Q % 16 == 0.  Accumulates with f32 atomics
+ *   A bf16 [M,P] (lda), B bf16 [M,Q] (ldb).  P % 8 == 0, Q % 8 == 0, lda % 8 == 0, ldb % 8 == 0 (16-byte operand chunks; P, Q = 8 mod 16
+ *   are exact on every kernel: tests/test_gemm_exact_gpu.py).  Accumulates with f32 atomics
  *   (weight-shared layers add R uses per step, weight_share_model.py:199-218); `splits` >= 1 partitions M.
  */
 /* workspace (nullable; dclip_gemm_tn_workspace_bytes() bytes, 16-byte aligned): with it the 256 x 256 wgrad pipeline writes each

@@ -1,6 +1,9 @@
-"""GPU parity of the MFMA GEMM kernels against torch fp32 on the SAME bf16-rounded operands.
+"""GPU parity of the MFMA GEMM kernels against torch fp32 on the SAME bf16-rounded operands, over many shapes.
 
-bf16 products are exact in fp32, so the only difference is fp32 summation order: tolerance 2e-3 * sqrt(K)-ish."""
+Every comparison here is max |got - ref| over max |ref|: 1e-5 sqrt(K) for f32 outputs (bf16 products are exact in fp32, the difference is
+the fp32 summation order), 6e-3 to 8e-3 -- several bf16 roundings -- for bf16 / f16 outputs, 2e-3 to 3e-3 for column sums.  That resolves
+neither a single rounding nor a single row or operand: the per-element checks (float64 reference, bit equality on integer operands,
+derived bounds on real ones, ownership of the output buffers, every tile height) are in tests/test_gemm_exact_gpu.py."""
 import pytest
 import torch
 
