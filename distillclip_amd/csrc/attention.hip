@@ -107,6 +107,13 @@ __global__ __launch_bounds__(256) void attn_nt_kernel(AttnMM p) {
             }
         }
     }
+    // pad columns behind the last 16-key tile (Np > 16 ceil(N / 16), e.g. N = 16, Np = 24: never with Np = round_up(N, 8)) are zero too
+    const int wpad = p.Np - nt * 16;
+    for (int idx = lane; idx < p.N * wpad; idx += 64) {
+        const int64_t o = (((int64_t)b * p.H + h) * p.N + idx / wpad) * p.ldc + nt * 16 + idx % wpad;
+        if (OUT_F32) ((float*)p.C)[o] = 0.f;
+        else ((bf16_t*)p.C)[o] = f2bf(0.f);
+    }
 }
 
 // k-major LDS tile fragment (16 columns from x0, 32 rows from r0): two ds_read_b64_tr_b16
@@ -267,9 +274,13 @@ struct AttnFused {
 // NTM = 16-key tiles the instance holds registers for (4: N <= 64, 5: N <= 80, 7: N <= 112, 8: N <= 128); the K fragments and score tiles
 // scale with it, and at NTM = 4 / 5 three waves per SIMD fit where the N = 128 sizing allowed two.
 // LDS (round 5): the V and P tiles hold 16 x ceil(N / 16) key rows, not the sequence padded to 32 — an odd number of key tiles ends in
-// ONE v_mfma_f32_16x16x16_bf16 step instead of a half-empty 32-key step —, and the launch picks the workgroup size (4, 2 or 1 waves) that
-// puts the most waves on a CU: at N = 101 (l_clip at 336 px) a wave needs 21.8 KB instead of 24.8 and runs in one-wave workgroups, 7 per
-// CU where the four-wave workgroup of 99 KB left ONE per CU (151 us for the ViT-B/32 teacher against 38.7 at N = 50: 3.9 x for 2 x tokens).
+// ONE v_mfma_f32_16x16x16_bf16 step instead of a half-empty 32-key step —, and the launch (dclip_attn_fused_fwd) picks the workgroup
+// shape that puts the most waves on a CU.  Evaluated for every N <= 128 and both head sizes it picks one of two shapes only: four
+// problems of one wave each for N <= 16 (a single query tile cannot be split), and for every other N four waves as two problems of two
+// waves, which share the problem's V tile and take alternate query tiles -- the first candidate already reaches the register cap of
+// 12 / 8 waves per CU, and ties go to the split form.  At N = 101 (l_clip at 336 px), hd = 64, that workgroup needs 50 KB (two V tiles
+// of 17.5 KB, four P tiles of 3.75 KB: three workgroups per CU) where four one-wave problems at the N = 128 sizing needed 99 KB and left
+// ONE workgroup per CU.
 template <int HD, int NTM>
 __global__ __launch_bounds__(256, NTM <= 7 ? 3 : 2) void attn_fused_fwd_kernel(AttnFused p) {
     constexpr int VROWB = HD * 2 + 32;
@@ -1068,7 +1079,8 @@ int check_mm(const AttnMM& p, const char* who) {
     DCLIP_REQUIRE(p.A && p.Bm && p.C, "%s: null operand", who);
     DCLIP_REQUIRE(p.B > 0 && p.H > 0 && p.N > 0 && p.N <= NMAX, "%s: need 0 < N <= %d (N=%d)", who, NMAX, p.N);
     DCLIP_REQUIRE(p.hd == 32 || p.hd == 64, "%s: head dim must be 32 or 64 (got %d)", who, p.hd);
-    DCLIP_REQUIRE(p.Np % 8 == 0 && p.Np >= p.N, "%s: Np must be a multiple of 8 and >= N", who);
+    // Np <= NMAX: attn_tn_kernel stages 16 MAXJ <= 128 columns of A per chunk (Np = 136 would leave rows of the chunk unstaged)
+    DCLIP_REQUIRE(p.Np % 8 == 0 && p.Np >= p.N && p.Np <= NMAX, "%s: Np must be a multiple of 8, >= N and <= %d (Np=%d)", who, NMAX, p.Np);
     return DCLIP_OK;
 }
 

@@ -122,7 +122,9 @@ int dclip_layernorm_bwd(const void* dy, int64_t lddy, int dy_f32, const float* x
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Attention building blocks.  q/k/v/ctx are token-major bf16 (row = b*N + n, column = head*hd + d, row stride ld*);
- * score-like tensors are [B,H,N,Np], Np = round_up(N, 8), pad columns zero.  hd in {32, 64}, N <= 128.
+ * score-like tensors are [B,H,N,Np], Np = round_up(N, 8) in the towers (the product entries take any multiple of 8 with
+ * N <= Np <= 128 and refuse others), pad columns [N, Np) zero: nt writes them as +0, nn / tn require them of A.
+ * hd in {32, 64}, N <= 128.
  *   reference teacher: _common.py:73-89 ; student: weight_share_model.py:101-125 (scale, QK^T, conv_l, softmax,
  *   conv_w, PV) ; causal mask: text_encoder.py:54-60.
  * nt : C[b,h,i,j] = alpha * sum_d A[(b,i),h*hd+d] * Bm[(b,j),h*hd+d]          (S = QK^T ; dR = dO V^T)
