@@ -12,7 +12,7 @@ void dclip_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-extern "C" int dclip_version(void) { return 5; }
+extern "C" int dclip_version(void) { return 6; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Which HIP runtime is this library bound to, and is it the only one in the process?  (include/dclip.h, "Load order".)  PyTorch-ROCm

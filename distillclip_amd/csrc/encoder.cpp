@@ -7,16 +7,15 @@
 //   student (weight-shared MiniViT blocks): reference model/component/weight_share_model.py:336-372, :482-512
 //                           (forward_features), :199-218 (RepeatedMiniBlock), :179-185 (MiniBlock), :88-140 (MiniAttention)
 //
-// The handle is an immutable plan (shapes + workspace/weight-cache offsets).  All device memory is owned by the caller:
+// The handle is a read-only plan (shapes + workspace/weight-cache offsets).  Everything else is owned by the caller:
 //   params / grads : arrays of f32 device pointers in the canonical order documented in include/dclip.h
 //   wcache         : bf16 copies of the GEMM weights (W and, for the student, W^T for dgrad), refreshed by _prepare
 //   workspace      : activations; in training mode everything backward needs stays resident between the two calls
+//   run            : host record of what the last forward left in that workspace (dclip_encoder_run)
 // No allocation, no synchronisation, no global state: safe to call from the autograd thread and capturable in a hipGraph.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
-#include <mutex>
 #include <new>
 #include <vector>
 #include "common.h"
@@ -150,6 +149,16 @@ struct ExecSave {          // one block execution: its own set per execution in 
     float* stats;          // Mix: [B, H, N] log-sum-exp rows
 };
 
+// score buffers are reserved only on the paths that read them; the others stay null (see ExecSave)
+void take_scores(Bump& b, const Plan& p, AttnPath path, int64_t B, int64_t N, int64_t Np, ExecSave& s) {
+    const int64_t SN = B * p.H * N * Np;
+    const bool unfused = path == AttnPath::Unfused;
+    s.S = unfused ? b.take<float>(SN) : nullptr;
+    s.P = unfused ? b.take<bf16_t>(SN) : nullptr;
+    s.Rm = p.mixing ? b.take<bf16_t>(SN) : s.P;
+    s.stats = path == AttnPath::Mix ? b.take<float>(B * p.H * N) : nullptr;
+}
+
 struct Work {
     // persistent
     std::vector<void*> X;                  // residual stream: X[0] embedding output .. X[LR]; f32 for students, f16 for the frozen
@@ -198,13 +207,6 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
     const bool save = p.train && training;
     w.path = attn_path(p, save);
     const bool mix = w.path == AttnPath::Mix, unfused = w.path == AttnPath::Unfused;
-    // score buffers are reserved only on the paths that read them; the others stay null (see ExecSave)
-    auto take_scores = [&](ExecSave& s) {
-        s.S = unfused ? b.take<float>(SN) : nullptr;
-        s.P = unfused ? b.take<bf16_t>(SN) : nullptr;
-        s.Rm = p.mixing ? b.take<bf16_t>(SN) : s.P;
-        s.stats = mix ? b.take<float>(B * p.H * N) : nullptr;
-    };
     w.X.assign(nex + 1, nullptr);
     w.ex.assign(nex, ExecSave{});
     // teacher / inference: a single ping-pong set reused by every block
@@ -215,7 +217,7 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         xs = w.h16 ? (void*)b.take<_Float16>(M * D) : (void*)b.take<float>(M * D);
         shared.x_mid = xs;   // in-place residual stream
         shared.h1 = b.take<bf16_t>(M * D); shared.qkv = b.take<bf16_t>(M * 3 * D);
-        take_scores(shared);
+        take_scores(b, p, w.path, B, N, Npad, shared);
         shared.ctx = b.take<bf16_t>(M * D); shared.h2 = shared.h1; shared.z = nullptr; shared.u = b.take<bf16_t>(M * F);
         shared.mean1 = shared.rstd1 = shared.mean2 = shared.rstd2 = nullptr;
     }
@@ -226,7 +228,7 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         s.x_mid = b.take<float>(M * D);
         s.mean1 = b.take<float>(M); s.rstd1 = b.take<float>(M); s.mean2 = b.take<float>(M); s.rstd2 = b.take<float>(M);
         s.qkv = b.take<bf16_t>(M * 3 * D);
-        take_scores(s);
+        take_scores(b, p, w.path, B, N, Npad, s);
         s.z = b.take<uint8_t>(M * F);
         if (e % p.R == 0) {
             // the wgrad operands (inputs of the four linears) of a block's R executions lie back to back: [R][M, .]
@@ -363,39 +365,11 @@ int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w
 
 }  // namespace
 
-// seeded: the workspace whose backward seeds (residual-gradient accumulator, its bf16 copy, the last execution's fc2 operand slot)
-// the most recent training forward of this handle left cleared — the only mutable word of the handle.  dclip_encoder_backward
-// consumes it; a backward that does not find its workspace there (a second backward on one forward, a retry after a failed one,
-// another workspace in between) clears the seeds itself, so the call is self-contained whatever the caller does.
-// exported: which head-mean maps (bit 0 score, bit 1 probabilities, per block execution) the most recent training forward of the workspace
-// `exported_ws` wrote; the backward accepts map gradients for those only.
-// pruned: per workspace, whether its most recent forward ran the last block execution on the picked rows only (prune_last):
-// last_layer_output then re-runs that execution on all rows, and the backward takes the compact path and refuses a gradient
-// for that execution's hidden state.
-struct dclip_encoder {
-    Plan p;
-    mutable std::atomic<void*> seeded{nullptr};
-    mutable std::mutex maps_mu;
-    mutable void* exported_ws = nullptr;
-    mutable std::vector<uint8_t> exported;
-    mutable std::vector<std::pair<void*, bool>> pruned;    // (workspace, pruned), guarded by maps_mu
-};
+// dclip_encoder_run::flags.  The seeds are the residual-gradient accumulator and the last execution's fc2 operand slot (or, after a
+// pruned forward, the compact accumulator) that a backward starts from: clear_backward_seeds.
+enum : uint32_t { RUN_SEEDS_CLEAR = 1u, RUN_PRUNED = 2u };
 
-namespace {
-void note_pruned(const dclip_encoder* e, void* ws, bool pruned) {
-    std::lock_guard<std::mutex> lk(e->maps_mu);
-    for (auto& q : e->pruned)
-        if (q.first == ws) { q.second = pruned; return; }
-    if (e->pruned.size() >= 16) e->pruned.erase(e->pruned.begin());
-    e->pruned.emplace_back(ws, pruned);
-}
-bool was_pruned(const dclip_encoder* e, const void* ws) {
-    std::lock_guard<std::mutex> lk(e->maps_mu);
-    for (const auto& q : e->pruned)
-        if (q.first == ws) return q.second;
-    return false;
-}
-}  // namespace
+struct dclip_encoder { Plan p; };
 
 extern "C" dclip_encoder* dclip_encoder_create(const dclip_encoder_cfg* cfg) {
     if (!cfg) { dclip_set_error("dclip_encoder_create: null cfg"); return nullptr; }
@@ -459,7 +433,7 @@ int exec_attn(const Plan& p, AttnPath path, const ExecSave& s, const bf16_t* W, 
               int64_t N, void* st) {
     const int64_t D = p.D, M = B * N;
     CK(ln_stream(h16, xin, D, nullptr, e.n1w, e.n1b, s.h1, D, DCLIP_OUT_BF16, s.mean1, s.rstd1, M, D, st));
-    CK(gemm(s.h1, D, W + p.bw[l].qkv, D, s.qkv, 3 * D, M, 3 * D, D, e.bq, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+    CK(gemm(s.h1, D, W + p.bw[l].qkv, D, s.qkv, 3 * D, M, 3 * D, D, e.bq, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
     return attn_forward(path, p, s, e.wl, e.ww, B, N, st);
 }
 
@@ -473,7 +447,7 @@ int exec_mlp(const Plan& p, const bf16_t* W, int l, const EP& e, bool h16, const
     const int act = p.student ? (z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU);
     CK(gemm(ctx, D, W + bw.proj, D, x_mid, D, rows, D, D, e.bp, 0, nullptr, nullptr, xin, D, sdt, 0, nullptr, st));
     CK(ln_stream(h16, x_mid, D, nullptr, e.n2w, e.n2b, h2, D, DCLIP_OUT_BF16, mean2, rstd2, rows, D, st));
-    CK(gemm(h2, D, W + bw.fc1, D, u, F, rows, F, D, e.b1, act, nullptr, z, nullptr, 0, 0, 0, nullptr, st));
+    CK(gemm(h2, D, W + bw.fc1, D, u, F, rows, F, D, e.b1, act, nullptr, z, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
     return gemm(u, F, W + bw.fc2, F, xout, D, rows, D, F, e.b2, 0, nullptr, nullptr, x_mid, D, sdt, 0, nullptr, st);
 }
 
@@ -482,15 +456,12 @@ int exec_mlp(const Plan& p, const bf16_t* W, int l, const EP& e, bool h16, const
 // scratch an unpruned forward needs.
 size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base, ExecSave& t, void*& xout) {
     Bump b(base);
-    const int64_t N = p.N, M = B * N, D = p.D, F = p.F, SN = B * p.H * N * p.Np;
+    const int64_t N = p.N, M = B * N, D = p.D, F = p.F;
     const size_t es = h16 ? 2 : 4;
     t = ExecSave{};
     t.h1 = b.take<bf16_t>(M * D); t.h2 = t.h1;
     t.qkv = b.take<bf16_t>(M * 3 * D);
-    t.S = path == AttnPath::Unfused ? b.take<float>(SN) : nullptr;
-    t.P = path == AttnPath::Unfused ? b.take<bf16_t>(SN) : nullptr;
-    t.Rm = p.mixing ? b.take<bf16_t>(SN) : t.P;
-    t.stats = path == AttnPath::Mix ? b.take<float>(B * p.H * N) : nullptr;
+    take_scores(b, p, path, B, N, p.Np, t);
     t.ctx = b.take<bf16_t>(M * D);
     t.x_mid = b.take<char>(M * D * es);
     t.u = b.take<bf16_t>(M * F);
@@ -560,10 +531,10 @@ static int clear_backward_seeds(const Plan& p, const Work& w, int64_t M, int64_t
 // patches: the image tower's [B*N, K] bf16 patch rows made by the caller (dclip_im2row, cls_rows = 1) — two towers that
 // see the same images and cut them the same way share one conversion; null: this call converts `input` itself
 extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, const void* patches, int64_t B, const void* const* params,
-                                     const void* wcache, void* workspace, size_t ws_bytes, int training,
+                                     const void* wcache, void* workspace, size_t ws_bytes, dclip_encoder_run* run, int training,
                                      float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
                                      const dclip_attn_maps* maps, void* st) {
-    DCLIP_REQUIRE(e && (input || patches) && params && wcache && workspace && last_representation, "dclip_encoder_forward: null argument");
+    DCLIP_REQUIRE(e && (input || patches) && params && wcache && workspace && run && last_representation, "dclip_encoder_forward: null argument");
     DCLIP_REQUIRE(B > 0, "dclip_encoder_forward: empty batch");
     const Plan& p = e->p;
     const bf16_t* ext_patches = (const bf16_t*)patches;
@@ -574,19 +545,20 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     // attention; LN / MLP are per token), so the tower may run on the first tokens_eff positions with identical output.
     DCLIP_REQUIRE(tokens_eff == 0 || (!p.train && !p.image && p.c.causal && tokens_eff > 0 && tokens_eff <= p.N && !rep_out && !emb_out),
                   "dclip_encoder_forward: tokens_eff is only valid for the causal text teacher without hidden-state export");
-    // head-mean attention maps per block execution (bit 0 score, bit 1 probabilities)
+    // head-mean attention maps per block execution, and which were asked for as the record notes them (one bit per execution)
     std::vector<float*> map_s(p.L * p.R, nullptr), map_p(p.L * p.R, nullptr);
-    std::vector<uint8_t> mapped(p.L * p.R, 0);
+    uint64_t score_maps = 0, prob_maps = 0;
     if (maps && maps->n) {
         DCLIP_REQUIRE(maps->n > 0 && maps->exec, "dclip_encoder_forward: maps need n > 0 execution indices");
         DCLIP_REQUIRE(tokens_eff == 0, "dclip_encoder_forward: attention maps cannot be exported from a caption prefix (tokens_eff)");
         for (int k = 0; k < maps->n; ++k) {
             const int ei = maps->exec[k];
             DCLIP_REQUIRE(ei >= 0 && ei < p.L * p.R, "dclip_encoder_forward: map %d: block execution %d out of range 0..%d", k, ei, p.L * p.R - 1);
+            DCLIP_REQUIRE(ei < 64, "dclip_encoder_forward: map %d: block execution %d: maps are exported for executions 0..63 only", k, ei);
             float* sm = maps->score ? maps->score[k] : nullptr;
             float* pm = maps->prob ? maps->prob[k] : nullptr;
-            if (sm) { map_s[ei] = sm; mapped[ei] |= 1; }
-            if (pm) { map_p[ei] = pm; mapped[ei] |= 2; }
+            if (sm) { map_s[ei] = sm; score_maps |= (uint64_t)1 << ei; }
+            if (pm) { map_p[ei] = pm; prob_maps |= (uint64_t)1 << ei; }
         }
     }
     Work w;
@@ -603,7 +575,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
         if (!ext_patches) CK(dclip_im2row((const float*)input, w.patches, B, p.c.in_chans, p.c.resolution, p.c.patch, 1, st));
         if (p.student) {   // params: 0 conv w, 1 conv b, 2 cls_token, 3 pos_embed
             CK(dclip_token_table(PF(params, 3), PF(params, 2), PF(params, 1), w.tok_table, N, D, st));
-            CK(gemm(rows, p.K, W + p.w_embed, p.K, w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, 1, N, w.tok_table, st));
+            CK(gemm(rows, p.K, W + p.w_embed, p.K, w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, N, w.tok_table, st));
         } else {           // params: 0 conv1 w, 1 class_embedding, 2 positional_embedding, 3 ln_pre w, 4 ln_pre b
             CK(dclip_token_table(PF(params, 2), PF(params, 1), nullptr, w.tok_table, N, D, st));
             const int sdt0 = w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;
@@ -613,7 +585,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     } else if (p.compressed) {   // params: 0 table [V,rank], 1 linear w [D,rank], 2 linear b, 3 pos
         CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, 0), nullptr, w.patches, 0, M, N, p.c.embed_rank, st));
         CK(dclip_token_table(PF(params, 3), nullptr, PF(params, 2), w.tok_table, N, D, st));
-        CK(gemm(w.patches, p.c.embed_rank, W + p.w_embed, p.c.embed_rank, w.X[0], D, M, D, p.c.embed_rank, nullptr, 0, nullptr, nullptr, nullptr, 0, 1, N, w.tok_table, st));
+        CK(gemm(w.patches, p.c.embed_rank, W + p.w_embed, p.c.embed_rank, w.X[0], D, M, D, p.c.embed_rank, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, N, w.tok_table, st));
     } else {                     // params: 0 table [V,D], 1 pos [N,D]
         CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, 0), PF(params, 1), w.X[0], w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32, M, N, D, st));
     }
@@ -627,7 +599,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     // attention everything is row-local: unless its hidden state or maps are exported, that execution's out_proj, LN2 and MLP run on
     // the B picked rows only (its attention still runs on all M rows: the picked queries attend to every key).
     CK(dclip_pick_index(p.image ? nullptr : (const int64_t*)input, p.N, w.pick, B, N, st));
-    const bool prune = prune_last_enabled() && !(rep_out && rep_out[nex - 1]) && !mapped[nex - 1];
+    const bool prune = prune_last_enabled() && !(rep_out && rep_out[nex - 1]) && !map_s[nex - 1] && !map_p[nex - 1];
     for (int ei = 0; ei < nex; ++ei) {
         const int l = ei / p.R, r = ei % p.R;
         const ExecSave& s = w.ex[ei];
@@ -637,7 +609,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
         if (compact) sa.ctx = w.ctx_full;
         CK(exec_attn(p, w.path, sa, W, l, ep, w.h16, w.X[ei], B, N, st));
         // before the next execution reuses the inference set's qkv
-        if (mapped[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, ep.wl, map_s[ei], map_p[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
+        if (map_s[ei] || map_p[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, ep.wl, map_s[ei], map_p[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
         if (!compact) {
             CK(exec_mlp(p, W, l, ep, w.h16, s.ctx, w.X[ei], s.x_mid, s.h2, s.mean2, s.rstd2, s.u, s.z, w.X[ei + 1], M, st));
         } else {
@@ -653,14 +625,13 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     const int f = p.p_final;
     CK(ln_stream(w.h16, prune ? w.xoc : w.X[nex], D, prune ? nullptr : w.pick, PF(params, f), PF(params, f + 1), w.hf, D, DCLIP_OUT_BF16,
                  w.meanf, w.rstdf, B, D, st));
-    CK(gemm(w.hf, D, W + p.w_head, D, last_representation, E, B, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, 1, 0, nullptr, st));
-    note_pruned(e, workspace, prune);
+    CK(gemm(w.hf, D, W + p.w_head, D, last_representation, E, B, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
+    *run = dclip_encoder_run{prune ? RUN_PRUNED : 0u, 0, 0, 0};
     if (training) {
         CK(clear_backward_seeds(p, w, M, B, prune, st));
-        e->seeded.store(workspace, std::memory_order_release);
-        std::lock_guard<std::mutex> lk(e->maps_mu);
-        e->exported_ws = workspace;
-        e->exported = mapped;
+        run->flags |= RUN_SEEDS_CLEAR;
+        run->score_maps = score_maps;
+        run->prob_maps = prob_maps;
     }
     return DCLIP_OK;
 }
@@ -681,8 +652,9 @@ extern "C" size_t dclip_encoder_last_layer_output_scratch_bytes(const dclip_enco
 }
 
 extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B, const void* const* params, const void* wcache,
-                                               void* workspace, size_t ws_bytes, int training, void* scratch, float* out, void* st) {
-    DCLIP_REQUIRE(e && params && wcache && workspace && scratch && out, "dclip_encoder_last_layer_output: null argument");
+                                               void* workspace, size_t ws_bytes, const dclip_encoder_run* run, int training, void* scratch,
+                                               float* out, void* st) {
+    DCLIP_REQUIRE(e && params && wcache && workspace && run && scratch && out, "dclip_encoder_last_layer_output: null argument");
     DCLIP_REQUIRE(B > 0, "dclip_encoder_last_layer_output: empty batch");
     const Plan& p = e->p;
     DCLIP_REQUIRE(!training || p.train, "dclip_encoder_last_layer_output: the frozen teacher tower (kind 0) is inference-only");
@@ -693,7 +665,7 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
     const int64_t M = B * p.N, D = p.D, E = p.E;
     const int nex = p.L * p.R, f = p.p_final;
     const void* xlast = w.X[nex];
-    if (was_pruned(e, workspace)) {
+    if (run->flags & RUN_PRUNED) {
         ExecSave t;
         void* xout;
         llo_scratch(p, w.path, w.h16, B, scratch, t, xout);
@@ -704,16 +676,16 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
         xlast = xout;
     }
     CK(ln_stream(w.h16, xlast, D, nullptr, PF(params, f), PF(params, f + 1), scratch, D, DCLIP_OUT_BF16, nullptr, nullptr, M, D, st));
-    CK(gemm(scratch, D, W + p.w_head, D, out, E, M, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, 1, 0, nullptr, st));
+    CK(gemm(scratch, D, W + p.w_head, D, out, E, M, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
     return DCLIP_OK;
 }
 
 // patches: the rows the forward ran on, if the caller made them (they are the patch-embedding wgrad's operand)
 extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input, const void* patches, int64_t B, const void* const* params,
-                                      void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                                      void* const* grads, const void* wcache, void* workspace, size_t ws_bytes, dclip_encoder_run* run,
                                       const float* d_last_representation, const float* const* d_rep, const float* d_emb,
                                       const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* st) {
-    DCLIP_REQUIRE(e && (input || patches) && params && grads && wcache && workspace && d_last_representation, "dclip_encoder_backward: null argument");
+    DCLIP_REQUIRE(e && (input || patches) && params && grads && wcache && workspace && run && d_last_representation, "dclip_encoder_backward: null argument");
     const Plan& p = e->p;
     const bf16_t* ext_patches = (const bf16_t*)patches;
     DCLIP_REQUIRE(!ext_patches || p.image, "dclip_encoder_backward: patches: image towers only");
@@ -723,16 +695,15 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     std::vector<uint8_t> has_mg(p.L * p.R, 0);
     if (maps && maps->n) {
         DCLIP_REQUIRE(maps->n > 0 && maps->exec, "dclip_encoder_backward: maps need n > 0 execution indices");
-        std::lock_guard<std::mutex> lk(e->maps_mu);
         for (int k = 0; k < maps->n; ++k) {
             const int ei = maps->exec[k];
             DCLIP_REQUIRE(ei >= 0 && ei < p.L * p.R, "dclip_encoder_backward: map %d: block execution %d out of range 0..%d", k, ei, p.L * p.R - 1);
             const float* gs = maps->d_score ? maps->d_score[k] : nullptr;
             const float* gp = maps->d_prob ? maps->d_prob[k] : nullptr;
-            const uint8_t had = e->exported_ws == workspace && (size_t)ei < e->exported.size() ? e->exported[ei] : 0;
-            DCLIP_REQUIRE((!gs || (had & 1)) && (!gp || (had & 2)),
+            const bool had_s = ei < 64 && (run->score_maps >> ei & 1), had_p = ei < 64 && (run->prob_maps >> ei & 1);
+            DCLIP_REQUIRE((!gs || had_s) && (!gp || had_p),
                           "dclip_encoder_backward: a gradient for the %s map of block execution %d, which the forward did not export",
-                          gs && !(had & 1) ? "score" : "probability", ei);
+                          gs && !had_s ? "score" : "probability", ei);
             if (gs) mgrad[ei].d_score = gs;
             if (gp) mgrad[ei].d_prob = gp;
             if (gs || gp) has_mg[ei] = 1;
@@ -752,7 +723,7 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     const int64_t N = p.N, D = p.D, F = p.F, E = p.E, M = B * N;
     const int nex = p.L * p.R;
     // a pruned forward (its last execution on the picked rows only) keeps no hidden state of that execution and exports no map of it
-    const bool pruned = was_pruned(e, workspace);
+    const bool pruned = (run->flags & RUN_PRUNED) != 0;
     DCLIP_REQUIRE(!pruned || !(d_rep && d_rep[nex - 1]),
                   "dclip_encoder_backward: a gradient for the hidden state of block execution %d, which the forward ran on the class / EOT "
                   "rows only (request that hidden state in the forward, or set DCLIP_PRUNE_LAST=0)", nex - 1);
@@ -761,12 +732,10 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     auto GR = [&](int i) -> float* { return (float*)grads[i]; };
     hipStream_t hs = (hipStream_t)st;
 
-    // w.G, w.Gb and the last execution's fc2 operand slot were cleared at the end of the training forward of THIS workspace
-    // (clear_backward_seeds) unless a backward has consumed them since: then they are cleared here
-    {
-        void* expect = workspace;
-        if (!e->seeded.compare_exchange_strong(expect, nullptr, std::memory_order_acq_rel)) CK(clear_backward_seeds(p, w, M, B, pruned, st));
-    }
+    // the seeds were cleared at the end of the training forward of this workspace (clear_backward_seeds) unless a backward has consumed
+    // them since: then they are cleared here
+    if (run->flags & RUN_SEEDS_CLEAR) run->flags &= ~RUN_SEEDS_CLEAR;
+    else CK(clear_backward_seeds(p, w, M, B, pruned, st));
     // ---- head + final norm -----------------------------------------------------------------------------------
     const int f = p.p_final;
     CK(dclip_cast_bf16(d_last_representation, w.dout, B * E, st));
@@ -776,7 +745,7 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     } else if (GR(f + 2)) {  // x @ proj: proj [D, E], no bias (reference _common.py:213, text_encoder.py:72)
         CK(dclip_gemm_tn_acc(w.hf, D, w.dout, E, GR(f + 2), E, B, D, E, 1, w.tn_ws, w.tn_ws_bytes, st));
     }
-    CK(gemm(w.dout, E, W + p.w_head_t, E, w.dh, D, B, D, E, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+    CK(gemm(w.dout, E, W + p.w_head_t, E, w.dh, D, B, D, E, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
     // every LayerNorm backward also emits the column sums of the updated residual gradient = the bias gradient of the
     // linear that wrote into that residual stream (fc2 of the previous execution / attn.proj of this one)
     const int R = p.R;
@@ -811,30 +780,30 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
         // gradient arriving directly at this execution's output (feature-MSE terms): G += d_rep[ei], refresh the bf16 copy
         if (d_rep && d_rep[ei]) CK(dclip_axpy_f32(w.G, d_rep[ei], gb_f2, M * D, GR(bx.f2b), D, st));
         // MLP: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
-        CK(dclip_gemm_nt(gb_f2, D, W + bw.fc2_t, D, dbig, F, Mx, F, D, 1.f, nullptr, DCLIP_ACT_MULAUX, s.z, nullptr, nullptr, 0, 0, 0, nullptr,
+        CK(dclip_gemm_nt(gb_f2, D, W + bw.fc2_t, D, dbig, F, Mx, F, D, 1.f, nullptr, DCLIP_ACT_MULAUX, s.z, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr,
                          GR(bx.f1b), st));                                        // dz = (G W2) o gelu'(z) ; db1 += colsum(dz)
         if (r == 0 && GR(bx.f2w)) CK(dclip_gemm_tn_acc(w.gb_f2, D, s0.u, F, GR(bx.f2w), F, MRw, D, F, wsplits(MRw, D, F), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && GR(bx.f1w)) CK(dclip_gemm_tn_acc(w.dbig, F, s0.h2, D, GR(bx.f1w), D, MRw, F, D, wsplits(MRw, F, D), w.tn_ws, w.tn_ws_bytes, st));
-        CK(gemm(dbig, F, W + bw.fc1_t, F, w.dh, D, Mx, D, F, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+        CK(gemm(dbig, F, W + bw.fc1_t, F, w.dh, D, Mx, D, F, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
         CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)s.x_mid, D, nullptr, PF(params, bx.n2w), s.mean2, s.rstd2, compact ? w.Gc : w.G, D, gb_pr, D,
                                GR(bx.n2w), GR(bx.n2b), GR(bx.prb), Mx, D, st));
         // attention: x_mid = x_in + proj(attn(LN1(x_in)))
         if (r == 0 && GR(bx.prw)) CK(dclip_gemm_tn_acc(w.gb_pr, D, s0.ctx, D, GR(bx.prw), D, MRw, D, D, wsplits(MRw, D, D), w.tn_ws, w.tn_ws_bytes, st));
         bf16_t* dctx = w.dh;
         if (!compact) {
-            CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx, D, M, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+            CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx, D, M, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
         } else {
             // the compact dctx goes through this execution's dqkv slot (written by the attention backward only after it is read);
             // dctx and the residual-stream gradient are then the full-M tensors, zero outside the picked rows
             bf16_t* dctx_c = dqkv;
-            CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx_c, D, B, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+            CK(gemm(gb_pr, D, W + bw.proj_t, D, dctx_c, D, B, D, D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
             CK(dclip_rows_expand(dctx_c, dctx, w.pick, B, N, D * 2, st));
             CK(dclip_rows_expand(w.Gc, w.G, w.pick, B, N, D * 4, st));
         }
         CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, has_mg[ei] ? &mgrad[ei] : nullptr, st));
         if (r == 0 && GR(bx.qkvw)) CK(dclip_gemm_tn_acc(w.dqkv, 3 * D, s0.h1, D, GR(bx.qkvw), D, MR, 3 * D, D, wsplits(MR, 3 * D, D), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && params[bx.qkvb] && GR(bx.qkvb)) CK(dclip_colsum_acc(w.dqkv, 3 * D, GR(bx.qkvb), MR, 3 * D, st));
-        CK(gemm(dqkv, 3 * D, W + bw.qkv_t, 3 * D, w.dh, D, M, D, 3 * D, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, st));
+        CK(gemm(dqkv, 3 * D, W + bw.qkv_t, 3 * D, w.dh, D, M, D, 3 * D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
         // the bf16 residual gradient leaving this execution is the fc2 operand of the previous one (slot of its repeat index)
         bf16_t* gb_next = ei > 0 ? w.gb_f2 + (int64_t)((ei - 1) % R) * M * D : w.Gb;
         CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)w.X[ei], D, nullptr, PF(params, bx.n1w), s.mean1, s.rstd1, w.G, D, gb_next, D, GR(bx.n1w), GR(bx.n1b),
@@ -872,7 +841,7 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
             CK(dclip_token_table_bwd(w.tok_sum, GR(3), nullptr, GR(2), N, D, 0, st));
         }
         if (GR(0)) {
-            CK(gemm(w.Gb, D, W + p.w_embed_t, D, w.demb, rk, M, rk, D, nullptr, 0, nullptr, nullptr, nullptr, 0, 1, 0, nullptr, st));
+            CK(gemm(w.Gb, D, W + p.w_embed_t, D, w.demb, rk, M, rk, D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
             CK(dclip_embed_scatter_add((const int64_t*)input, w.demb, 1, GR(0), M, rk, p.c.vocab, st));
         }
     } else {                     // grads: 0 table, 1 pos

@@ -27,6 +27,11 @@ class AttnMapsDesc(ctypes.Structure):
                 ('d_score', ctypes.c_void_p), ('d_prob', ctypes.c_void_p), ('scratch', ctypes.c_void_p), ('scratch_bytes', ctypes.c_size_t)]
 
 
+class EncoderRun(ctypes.Structure):
+    # include/dclip.h: dclip_encoder_run (what the last forward left in one workspace; zeroed = no forward yet)
+    _fields_ = [('flags', ctypes.c_uint32), ('reserved', ctypes.c_uint32), ('score_maps', ctypes.c_uint64), ('prob_maps', ctypes.c_uint64)]
+
+
 class ExportedMaps(list):
     """head-mean attention maps, [B, 1, N, N] f32 each, of the first block executions a tower exported; `executions` = how many the
     tower has (layers x repeats).  The reference's attention losses divide by the length of the STUDENT's list, which holds one map per
@@ -131,6 +136,7 @@ class HipTower:
         self.wcache = None
         self.wcache_dirty = True
         self.workspace = None
+        self._run = EncoderRun()                  # the workspace's record: replaced together with it
         self._ws_key = None
         self._saved_batch = None
         self.bwd_done = None
@@ -269,6 +275,7 @@ class HipTower:
         need = lib().dclip_encoder_workspace_bytes(self._handle, batch, 1 if training else 0)
         if self.workspace is None or self.workspace.numel() < need or self.workspace.device != device:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=device)
+            self._run = EncoderRun()
         self._ws_key = key
 
     def prepare(self):
@@ -347,7 +354,7 @@ class HipTower:
         self._patch_rows = rows if training else None      # (kept until the backward: operand of the patch-embedding wgrad)
         lib().dclip_encoder_forward(self._handle, None if rows is not None else x.data_ptr(), None if rows is None else rows.data_ptr(), B,
                                     _ptr_array(ps), self.wcache.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
-                                    1 if training else 0, out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(), int(tokens_eff),
+                                    ctypes.byref(self._run), 1 if training else 0, out.data_ptr(), rep_arr, None if emb is None else emb.data_ptr(), int(tokens_eff),
                                     None if desc is None else ctypes.byref(desc[0]), torch.cuda.current_stream().cuda_stream)
         self._saved_batch = B if training else None
         self._last_fwd = (B, bool(training), int(tokens_eff))
@@ -370,7 +377,7 @@ class HipTower:
                               device=dev)
         out = torch.empty((B, N, E), dtype=torch.float32, device=dev)
         lib().dclip_encoder_last_layer_output(self._handle, B, _ptr_array(self._params()), self.wcache.data_ptr(),
-                                              self.workspace.data_ptr(), self.workspace.numel(), 1 if training else 0,
+                                              self.workspace.data_ptr(), self.workspace.numel(), ctypes.byref(self._run), 1 if training else 0,
                                               scratch.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         return out
 
@@ -429,7 +436,7 @@ class HipTower:
                 desc = _maps_desc([int(i) for i in execs], d_score=d_sc, d_prob=d_pr, scratch=scratch)
         lib().dclip_encoder_backward(self._handle, None if rows is not None else x.data_ptr(), None if rows is None else rows.data_ptr(), B,
                                      _ptr_array(ps), _ptr_array(gs), self.wcache.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
-                                     d_out.data_ptr(), _ptr_array(keep) if any(g is not None for g in keep) else None,
+                                     ctypes.byref(self._run), d_out.data_ptr(), _ptr_array(keep) if any(g is not None for g in keep) else None,
                                      None if d_emb is None else d_emb.data_ptr(), None if desc is None else ctypes.byref(desc[0]),
                                      ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None,
                                      torch.cuda.current_stream().cuda_stream)

@@ -8,8 +8,7 @@
  * No synchronisation inside any entry point, no allocation, no global mutable state on the compute path: the process-global state is
  * the opt-in profiling hooks (dclip_trace_*: launch trace, GEMM stamps / clock stamps; the wgrad fallback counter) and a handful of
  * tuning knobs read from DCLIP_* environment variables, latched once on first use and constant
- * afterwards.  A dclip_encoder handle additionally remembers which workspace its last training forward
- * prepared for a backward (dclip_encoder_backward below).  Every function returns
+ * afterwards.  Every function returns
  * 0 on success, DCLIP_EINVAL (-1) for a bad argument, DCLIP_ELAUNCH (-2) for a HIP launch failure, and
  * dclip_last_error_string() (thread-local) explains the last failure.
  *
@@ -340,7 +339,10 @@ int dclip_feature_mse(const float* s, const float* t, int64_t n, float coef, flo
  *            student role (reference image_encoder.py:16-25,54-59, text_encoder.py:41-47,75-80; their embedding_projection /
  *            hidden_projection linears act on the exported hidden states and stay with the caller) — f32 residual stream, autograd of it;
  *   student: reference model/component/weight_share_model.py:336-372 / :482-512 (forward_features) and autograd of it.
- * The handle is an immutable host-side plan; params / grads / wcache / workspace are caller-owned device buffers.
+ * The handle is an immutable host-side plan; params / grads / wcache / workspace are caller-owned device buffers, and what a forward
+ * left in a workspace is noted in a caller-owned host record that travels with it (dclip_encoder_run below).
+ * Threads: the handle is read-only after create, so any number of threads may use one handle at once.  Calls that share a workspace
+ * share its record and are the caller's to serialise (they share device buffers, so they already are).
  *
  * Canonical parameter order (arrays of f32 device pointers; names are the reference's state_dict keys):
  *  teacher image : visual.conv1.weight, visual.class_embedding, visual.positional_embedding, visual.ln_pre.{weight,bias},
@@ -392,10 +394,12 @@ int dclip_encoder_prepare(const dclip_encoder* enc, const void* const* params, v
  *   exec[k]            : block-execution index (0 .. layers * repeats - 1) of map k
  *   score[k] / prob[k] : forward, f32 [B, N, N] outputs (array or entries nullable); written right after that execution's score stage
  *   d_score / d_prob   : backward, their gradients (array or entries nullable); added to that execution's dS before dQ / dK are formed.
- *                        Only maps the most recent training forward of the workspace exported may receive a gradient.
+ *                        Only maps the most recent training forward of the workspace exported (its dclip_encoder_run says which)
+ *                        may receive a gradient.
  *   scratch            : backward, dclip_attn_maps_bwd_workspace_bytes(B, heads, tokens) bytes (head-mixing students with d_prob)
- * Refused (DCLIP_EINVAL, nothing launched): an index out of range, maps together with tokens_eff != 0, a gradient for a map the
- * forward did not export.  maps = NULL or n = 0 exports nothing; workspace sizes do not depend on maps. */
+ * Refused (DCLIP_EINVAL, nothing launched): an index out of range or, in the forward, above 63 (one bit per execution in the record),
+ * maps together with tokens_eff != 0, a gradient for a map the forward did not export.  maps = NULL or n = 0 exports nothing;
+ * workspace sizes do not depend on maps. */
 typedef struct dclip_attn_maps {
     int32_t n;
     const int32_t* exec;
@@ -406,7 +410,16 @@ typedef struct dclip_attn_maps {
     void* scratch;
     size_t scratch_bytes;
 } dclip_attn_maps;
+/* What the most recent dclip_encoder_forward left in one workspace.  Host memory, caller-owned, one per workspace;
+ * all-zero = "no forward yet".  Opaque: written by the forward, consumed by the backward, read by last_layer_output. */
+typedef struct dclip_encoder_run {
+    uint32_t flags;        /* bit 0: backward seeds are clear; bit 1: last block execution ran on the picked rows only */
+    uint32_t reserved;
+    uint64_t score_maps;   /* bit e: the training forward exported the score map of block execution e */
+    uint64_t prob_maps;    /* the same for the probability maps */
+} dclip_encoder_run;
 /* input: image f32 [B,C,res,res] or token ids i64 [B,N].  last_representation: f32 [B,E] (class token / EOT row).
+ * run: the workspace's record, written whole when the call has issued everything (an inference forward notes the pruned bit only).
  * patches (image towers only; nullable): replaces `input` with patch rows the caller has already cut, bf16 [B*N, C*patch*patch] from
  * dclip_im2row(..., cls_rows = 1), 16-byte aligned.  Teacher and student see the same image batch (reference
  * dual_distill_model.py:107-109, distil_model.py forward) and, when their patch size and resolution agree, the same conv1 /
@@ -421,18 +434,20 @@ typedef struct dclip_attn_maps {
  * (causal mask), so last_representation is unchanged.
  * maps (nullable): head-mean attention maps to export, see dclip_attn_maps. */
 int dclip_encoder_forward(const dclip_encoder* enc, const void* input, const void* patches, int64_t B, const void* const* params,
-                          const void* wcache, void* workspace, size_t ws_bytes, int training, float* last_representation,
-                          float* const* rep_out, float* emb_out, int64_t tokens_eff, const dclip_attn_maps* maps, void* stream);
+                          const void* wcache, void* workspace, size_t ws_bytes, dclip_encoder_run* run, int training,
+                          float* last_representation, float* const* rep_out, float* emb_out, int64_t tokens_eff,
+                          const dclip_attn_maps* maps, void* stream);
 /* last_layer_output (reference output.py:16-35; _common.py:210-215, text_encoder.py:69-72, weight_share_model.py:363-366,
  * :503-506): final norm + projection of EVERY token, f32 [B*N, E], computed on request from the residual stream the most
- * recent dclip_encoder_forward(enc, ..., B, training) left in `workspace` (tokens_eff must have been 0).  scratch: caller-owned,
+ * recent dclip_encoder_forward(enc, ..., B, training) left in `workspace` and noted in `run` (tokens_eff must have been 0).  scratch: caller-owned,
  * dclip_encoder_last_layer_output_scratch_bytes(enc, B, training) bytes, 256-byte aligned.  A forward that exported neither the
  * hidden state nor a map of the last block execution runs that execution's out_proj / LN2 / MLP on the class / EOT rows only
  * (DCLIP_PRUNE_LAST=0: on all rows); this call then runs it again on all rows in `scratch`, leaving `workspace` untouched.
  * last_representation is the class-token / EOT row of this tensor. */
 size_t dclip_encoder_last_layer_output_scratch_bytes(const dclip_encoder* enc, int64_t B, int training);
 int dclip_encoder_last_layer_output(const dclip_encoder* enc, int64_t B, const void* const* params, const void* wcache,
-                                    void* workspace, size_t ws_bytes, int training, void* scratch, float* out, void* stream);
+                                    void* workspace, size_t ws_bytes, const dclip_encoder_run* run, int training, void* scratch,
+                                    float* out, void* stream);
 /* input / patches: what the forward ran on (caller-made patch rows are the patch-embedding wgrad's operand).
  * maps (nullable): gradients of the maps the forward exported, see dclip_attn_maps.
  * on_bucket (nullable): host callback, invoked on the calling thread as soon as every launch that writes gradient bucket
@@ -441,14 +456,14 @@ int dclip_encoder_last_layer_output(const dclip_encoder* enc, int64_t B, const v
  * all-reduce from autograd hooks, config/final_config/l_clip.yaml:56 strategy ddp_find_unused_parameters_false).
  * Buckets complete in index order; see dclip_encoder_grad_bucket.
  * Seeds: the backward starts from a residual-stream gradient accumulator (and one bf16 operand slot) that must be zero.  The training
- * forward clears them at its end (beside the other towers' work) and the handle remembers the workspace it did that for; a backward that
- * does not find ITS workspace there — a second backward on one forward, a retry, another workspace used in between — clears them itself.
+ * forward clears them at its end (beside the other towers' work) and says so in `run`; the backward consumes that note, and one that does
+ * not find it — a second backward on one forward, a retry, a record no forward has written — clears them itself.
  * Either way one call = the gradients of the most recent training forward of that workspace for the given d_*; gradients ACCUMULATE (+=)
  * into `grads` as everywhere.  After a forward that ran its last block execution on the class / EOT rows only (see last_layer_output),
  * d_rep[layers * repeats - 1] and map gradients of that execution are refused (DCLIP_EINVAL). */
 typedef void (*dclip_bucket_cb)(void* user, int32_t bucket);
 int dclip_encoder_backward(const dclip_encoder* enc, const void* input, const void* patches, int64_t B, const void* const* params,
-                           void* const* grads, const void* wcache, void* workspace, size_t ws_bytes,
+                           void* const* grads, const void* wcache, void* workspace, size_t ws_bytes, dclip_encoder_run* run,
                            const float* d_last_representation, const float* const* d_rep, const float* d_emb,
                            const dclip_attn_maps* maps, dclip_bucket_cb on_bucket, void* cb_user, void* stream);
 /* gradient buckets in completion order: 0 = final norm + head, 1..L = blocks L-1..0, L+1 = embedding parameters; each is the

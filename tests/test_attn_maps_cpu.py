@@ -40,7 +40,8 @@ def test_header_declares_and_library_exports_the_map_entries():
     assert 'typedef struct dclip_attn_maps' in src
     # one forward and one backward entry per tower, each taking input / patches and the nullable maps descriptor
     protos = lib().protos
-    assert len(protos['dclip_encoder_forward'][1]) == 15 and len(protos['dclip_encoder_backward'][1]) == 16
+    assert len(protos['dclip_encoder_forward'][1]) == 16 and len(protos['dclip_encoder_backward'][1]) == 17
+    assert len(protos['dclip_encoder_last_layer_output'][1]) == 11
     assert re.search(r'dclip_encoder_forward\([^)]*const void\* patches[^)]*const dclip_attn_maps\* maps', src)
     assert re.search(r'dclip_encoder_backward\([^)]*const void\* patches[^)]*const dclip_attn_maps\* maps', src)
 
@@ -81,9 +82,10 @@ def _handle(**kw):
 
 def test_encoder_refuses_bad_map_requests_on_host():
     from distillclip_amd._lib import lib
-    from distillclip_amd.model.component._tower import _maps_desc
+    from distillclip_amd.model.component._tower import _maps_desc, EncoderRun
     l = lib()
     fake = 1 << 20                                    # never dereferenced: every refusal below happens before a launch
+    run = ctypes.byref(EncoderRun())                  # a record no forward has written
 
     class Buf:                                        # stands for a device tensor in the descriptor's pointer arrays
         def data_ptr(self):
@@ -95,20 +97,21 @@ def test_encoder_refuses_bad_map_requests_on_host():
         ws = l.dclip_encoder_workspace_bytes(h, 2, 1)
         bad, keep = _maps_desc([4], score=[buf])     # 2 layers x 2 repeats: executions 0..3
         neg, keep2 = _maps_desc([-1], prob=[buf])
+        far, keep6 = _maps_desc([64], score=[buf])   # beyond the record's 64 bits too: the range check comes first
         d, keep3 = _maps_desc([1], d_prob=[buf])     # a gradient for a map no forward of this workspace exported
         # the same refusals whether the image tower converts `input` itself or takes caller-cut patch rows
         for inp, rows in ((fake, None), (None, fake)):
-            for m in (bad, neg):
+            for m in (bad, neg, far):
                 with pytest.raises(ValueError, match='out of range'):
-                    l.dclip_encoder_forward(h, inp, rows, 2, params, fake, fake, ws, 1, fake, None, None, 0, ctypes.byref(m), None)
+                    l.dclip_encoder_forward(h, inp, rows, 2, params, fake, fake, ws, run, 1, fake, None, None, 0, ctypes.byref(m), None)
             with pytest.raises(ValueError, match='did not export'):
-                l.dclip_encoder_backward(h, inp, rows, 2, params, params, fake, fake, ws, fake, None, None, ctypes.byref(d), None, None,
+                l.dclip_encoder_backward(h, inp, rows, 2, params, params, fake, fake, ws, run, fake, None, None, ctypes.byref(d), None, None,
                                          None)
         # neither input nor patch rows
         with pytest.raises(ValueError, match='null argument'):
-            l.dclip_encoder_forward(h, None, None, 2, params, fake, fake, ws, 1, fake, None, None, 0, None, None)
+            l.dclip_encoder_forward(h, None, None, 2, params, fake, fake, ws, run, 1, fake, None, None, 0, None, None)
         with pytest.raises(ValueError, match='null argument'):
-            l.dclip_encoder_backward(h, None, None, 2, params, params, fake, fake, ws, fake, None, None, None, None, None, None)
+            l.dclip_encoder_backward(h, None, None, 2, params, params, fake, fake, ws, run, fake, None, None, None, None, None, None)
     finally:
         l.dclip_encoder_destroy(h)
     # the causal text teacher's caption-prefix shortcut cannot export maps, and a text tower takes no patch rows
@@ -118,11 +121,11 @@ def test_encoder_refuses_bad_map_requests_on_host():
         ws = l.dclip_encoder_workspace_bytes(t, 2, 0)
         m, keep4 = _maps_desc([0], score=[buf])
         with pytest.raises(ValueError, match='caption prefix'):
-            l.dclip_encoder_forward(t, fake, None, 2, params, fake, fake, ws, 0, fake, None, None, 5, ctypes.byref(m), None)
+            l.dclip_encoder_forward(t, fake, None, 2, params, fake, fake, ws, run, 0, fake, None, None, 5, ctypes.byref(m), None)
         with pytest.raises(ValueError, match='image towers only'):
-            l.dclip_encoder_forward(t, None, fake, 2, params, fake, fake, ws, 0, fake, None, None, 0, None, None)
+            l.dclip_encoder_forward(t, None, fake, 2, params, fake, fake, ws, run, 0, fake, None, None, 0, None, None)
         with pytest.raises(ValueError, match='null argument'):
-            l.dclip_encoder_forward(t, None, None, 2, params, fake, fake, ws, 0, fake, None, None, 0, None, None)
+            l.dclip_encoder_forward(t, None, None, 2, params, fake, fake, ws, run, 0, fake, None, None, 0, None, None)
     finally:
         l.dclip_encoder_destroy(t)
     # a trainable text tower: its backward refuses patch rows too
@@ -130,9 +133,9 @@ def test_encoder_refuses_bad_map_requests_on_host():
     try:
         ws = l.dclip_encoder_workspace_bytes(s, 2, 1)
         with pytest.raises(ValueError, match='image towers only'):
-            l.dclip_encoder_forward(s, None, fake, 2, params, fake, fake, ws, 1, fake, None, None, 0, None, None)
+            l.dclip_encoder_forward(s, None, fake, 2, params, fake, fake, ws, run, 1, fake, None, None, 0, None, None)
         with pytest.raises(ValueError, match='image towers only'):
-            l.dclip_encoder_backward(s, None, fake, 2, params, params, fake, fake, ws, fake, None, None, None, None, None, None)
+            l.dclip_encoder_backward(s, None, fake, 2, params, params, fake, fake, ws, run, fake, None, None, None, None, None, None)
     finally:
         l.dclip_encoder_destroy(s)
     # maps together with tokens_eff on patch rows (image towers): patch rows never combine with tokens_eff
@@ -141,9 +144,9 @@ def test_encoder_refuses_bad_map_requests_on_host():
         ws = l.dclip_encoder_workspace_bytes(h, 2, 0)
         m, keep5 = _maps_desc([0], score=[buf])
         with pytest.raises(ValueError, match='patches cannot be combined with tokens_eff'):
-            l.dclip_encoder_forward(h, None, fake, 2, params, fake, fake, ws, 0, fake, None, None, 5, ctypes.byref(m), None)
+            l.dclip_encoder_forward(h, None, fake, 2, params, fake, fake, ws, run, 0, fake, None, None, 5, ctypes.byref(m), None)
         with pytest.raises(ValueError, match='patches cannot be combined with tokens_eff'):
-            l.dclip_encoder_forward(h, None, fake, 2, params, fake, fake, ws, 0, fake, None, None, 5, None, None)
+            l.dclip_encoder_forward(h, None, fake, 2, params, fake, fake, ws, run, 0, fake, None, None, 5, None, None)
     finally:
         l.dclip_encoder_destroy(h)
 

@@ -18,7 +18,7 @@ def test_library_exports_every_declared_symbol():
     assert len(declared) >= 35
     for name in declared:
         assert hasattr(l._dll, name), name
-    assert l.dclip_version() == 5 and l.dclip_arch() == b'gfx950'
+    assert l.dclip_version() == 6 and l.dclip_arch() == b'gfx950'
 
 
 def test_loading_the_c_abi_before_torch_is_reported_in_words():

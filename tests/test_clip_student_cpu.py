@@ -28,7 +28,7 @@ def test_layer_mapped_initialisation_from_the_teacher():
 def test_trainable_clip_tower_plan_is_host_side():
     """kind 2 = the CLIP architecture and parameter order of kind 0 with the training workspace / backward of kind 1"""
     from distillclip_amd._lib import lib
-    from distillclip_amd.model.component._tower import EncoderCfg
+    from distillclip_amd.model.component._tower import EncoderCfg, EncoderRun
     l = lib()
     mk = lambda **kw: EncoderCfg(**dict(dict(kind=2, modality=0, tokens=50, width=512, heads=8, layers=4, repeats=1, mlp_dim=2048, out_dim=512,
                                              patch=32, resolution=224, in_chans=3, vocab=0, embed_rank=0, head_mix=0, causal=0), **kw))
@@ -42,7 +42,8 @@ def test_trainable_clip_tower_plan_is_host_side():
     l.dclip_encoder_grad_bucket(h2, 1, ctypes.byref(first), ctypes.byref(end))
     assert (first.value, end.value) == (5 + 12 * 3, 5 + 12 * 4)                                  # the last layer completes first
     with pytest.raises(ValueError, match='inference-only'):                                       # the frozen kind still refuses to train
-        l.dclip_encoder_forward(h0, 256, None, 1, (ctypes.c_void_p * 56)(), 256, 256, 1 << 40, 1, 256, None, None, 0, None, None)
+        l.dclip_encoder_forward(h0, 256, None, 1, (ctypes.c_void_p * 56)(), 256, 256, 1 << 40, ctypes.byref(EncoderRun()), 1, 256, None, None, 0, None,
+                                None)
     for h in (h2, h0):
         l.dclip_encoder_destroy(h)
     assert not l.dclip_encoder_create(ctypes.byref(mk(kind=3)))

@@ -508,8 +508,8 @@ def test_c_abi_backward_is_self_contained_on_a_repeated_or_foreign_call(tiny):
     """dclip_encoder_backward starts from a residual-stream gradient accumulator that the TRAINING FORWARD leaves cleared (the fills run beside
     the other towers instead of on the critical path).  A caller outside the Python wrapper may call the backward twice on one forward
     (several d_out: gradient checks), retry it, or use another workspace in between; round 4 then accumulated onto stale residual gradients
-    and returned wrong parameter gradients with rc = 0.  The handle now remembers which workspace its last training forward prepared and the
-    backward clears the seeds itself when it does not find its workspace there (include/dclip.h, dclip_encoder_backward): every variant below
+    and returned wrong parameter gradients with rc = 0.  The forward notes in the workspace's record (dclip_encoder_run) that it left the seeds
+    cleared, and the backward clears them itself when it does not find that note (include/dclip.h, dclip_encoder_backward): every variant below
     returns the gradients of a fresh forward + backward."""
     s_img, s_txt, _, _ = _tiny_modules()
     image = torch.from_numpy(tiny['image']).cuda()
@@ -542,6 +542,53 @@ def test_c_abi_backward_is_self_contained_on_a_repeated_or_foreign_call(tiny):
             err = (got - want).abs().max().item()
             assert err <= 2e-5 * scale, (type(enc).__name__, tag, err, scale)      # (f32 atomics of the small wgrads / column sums: order noise only)
         assert (g2 - r1).abs().max().item() > 1e-2 * scale  # the two d_out really give different gradients
+
+
+def test_two_workspaces_on_one_handle_may_interleave(tiny):
+    """What a forward left in a workspace is noted in the record that travels with that workspace (dclip_encoder_run), not in the handle:
+    forward on pair A with a score and a probability map of execution 0, plain training forward on pair B with other images, then A's
+    backward with d_out and map gradients, then B's.  Each gives the gradients of the same forward + backward run alone on one pair.
+    (With the record kept in the handle, one slot for the last workspace, A's backward was refused here: "did not export".)"""
+    from distillclip_amd.model.component._tower import EncoderRun
+    s_img = _tiny_modules()[0]
+    tw = s_img._tower
+    gen = torch.Generator().manual_seed(7)
+    xa = torch.from_numpy(tiny['image']).cuda()
+    xb = torch.randn(xa.shape, generator=gen).cuda()
+    B, N = xa.shape[0], tw.cfg.tokens
+    maps = (True, True, [0])
+    d_a = torch.randn((B, tw.cfg.out_dim), generator=gen).cuda()
+    d_b = torch.randn((B, tw.cfg.out_dim), generator=gen).cuda()
+    d_maps = ([0], [torch.randn((B, 1, N, N), generator=gen).cuda()], [torch.randn((B, 1, N, N), generator=gen).cuda()])
+
+    def grads_of(xin, d, dm=None):
+        tw.flat_grad.zero_()
+        tw._saved_batch = B                                 # (the Python wrapper tracks one forward; the C ABI tracks one per record)
+        tw.backward(xin, d, d_maps=dm)
+        torch.cuda.synchronize()
+        return tw.flat_grad.clone()
+
+    # reference: each forward + backward alone on the tower's own pair
+    xin_a = tw.forward(xa, training=True, maps=maps)[1]
+    r_a = grads_of(xin_a, d_a, d_maps)
+    xin_b = tw.forward(xb, training=True)[1]
+    r_b = grads_of(xin_b, d_b)
+    pair_a = (tw.workspace, tw._run)
+    pair_b = (torch.empty_like(tw.workspace), EncoderRun())
+    tw.workspace, tw._run = pair_a
+    tw.forward(xa, training=True, maps=maps)
+    tw.workspace, tw._run = pair_b
+    tw.forward(xb, training=True)
+    assert tw.workspace is pair_b[0] and tw._run is pair_b[1]
+    tw.workspace, tw._run = pair_a
+    g_a = grads_of(xin_a, d_a, d_maps)
+    tw.workspace, tw._run = pair_b
+    g_b = grads_of(xin_b, d_b)
+    for got, want, tag in ((g_a, r_a, 'A: maps'), (g_b, r_b, 'B: plain')):
+        scale = want.abs().max().item()
+        err = (got - want).abs().max().item()
+        assert err <= 2e-5 * scale, (tag, err, scale)       # (f32 atomics of the small wgrads / column sums: order noise only)
+    assert (g_a - r_b).abs().max().item() > 1e-2 * r_b.abs().max().item()    # the two runs really give different gradients
 
 
 def test_teacher_text_prefix_is_exact():
