@@ -12,7 +12,8 @@
 //   wcache         : bf16 copies of the GEMM weights (W and, for the student, W^T for dgrad), refreshed by _prepare
 //   workspace      : activations; in training mode everything backward needs stays resident between the two calls
 //   run            : host record of what the last forward left in that workspace (dclip_encoder_run)
-// No allocation, no synchronisation, no global state: safe to call from the autograd thread and capturable in a hipGraph.
+// No device allocation (the host-side std::vectors below are per-call scratch), no synchronisation, no global state: safe to call
+// from the autograd thread and capturable in a hipGraph.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,14 +46,16 @@ enum { P_PER_TBLOCK = 12, P_PER_SBLOCK = 8, P_PER_SREPEAT = 6 };
 
 struct Plan {
     dclip_encoder_cfg c;
-    int D, H, hd, N, Np, F, E, L, R, K;        // K = patch GEMM contraction (image)
+    int D, H, hd, N, Np, F, E, L, R;
+    int K;                                     // contraction of the embedding GEMM: in_chans * patch^2 (image), embed_rank (compressed text), else 0
     bool student, image, compressed;           // student = the weight-shared MiniViT architecture (kind 1)
     bool mixing;                               // conv_l / conv_w cross-head mixing (head_mix; students only)
     bool train;                                // the tower has a backward (kind 1, 2): transposed weights cached, f32 residual stream
-    // parameter indices
-    int p_embed0;                              // first embedding parameter
+    // parameter indices (canonical order, include/dclip.h), -1 = the tower has no such parameter
+    struct EmbP { int table, w, bias, cls, pos, ln_w, ln_b; } emb;    // w: the embedding GEMM's weight (patch conv / compressed-text linear);
+                                                                      // ln_w / ln_b: ln_pre (CLIP image tower); table: token embedding (text)
     int p_blocks;                              // first block parameter
-    int p_final;                               // norm / ln_post .. projection
+    struct HeadP { int norm_w, norm_b, head_w, head_b; } head;        // norm / ln_post / ln_final, head / proj / text_projection
     int n_params;
     // weight cache offsets (bf16 elements), -1 = absent
     struct BlockW { int64_t qkv, qkv_t, proj, proj_t, fc1, fc1_t, fc2, fc2_t; };
@@ -86,19 +89,29 @@ bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
         if (c.vocab <= 0) { dclip_set_error("encoder: vocab required for text"); return false; }
         if (p.compressed && c.embed_rank % 64) { dclip_set_error("encoder: embed_rank must be a multiple of 64"); return false; }
         if (p.compressed && !p.student) { dclip_set_error("encoder: a compressed token embedding exists for the weight-shared student only (kind 1)"); return false; }
+        if (p.compressed) p.K = c.embed_rank;
     }
     if (p.mixing && p.H != 2 && p.H != 4 && p.H != 8 && p.H != 12 && p.H != 24) {
         dclip_set_error("encoder: head count %d unsupported by the head-mixing kernels", p.H); return false;
     }
     // parameter order
     int n = 0;
-    p.p_embed0 = 0;
-    if (p.student) n += p.image ? 4 : (p.compressed ? 4 : 2);     // see header
-    else n += p.image ? 5 : 2;
+    Plan::EmbP& em = p.emb;
+    em = Plan::EmbP{-1, -1, -1, -1, -1, -1, -1};
+    if (p.image) {
+        em.w = n++;
+        if (p.student) em.bias = n++;
+        em.cls = n++; em.pos = n++;
+        if (!p.student) { em.ln_w = n++; em.ln_b = n++; }
+    } else {
+        em.table = n++;
+        if (p.compressed) { em.w = n++; em.bias = n++; }
+        em.pos = n++;
+    }
     p.p_blocks = n;
     n += p.student ? p.L * (P_PER_SBLOCK + p.R * P_PER_SREPEAT) : p.L * P_PER_TBLOCK;
-    p.p_final = n;
-    n += p.student ? 4 : 3;
+    p.head.norm_w = n++; p.head.norm_b = n++; p.head.head_w = n++;
+    p.head.head_b = p.student ? n++ : -1;                         // CLIP towers project without a bias
     p.n_params = n;
     // weight cache
     int64_t off = 0;
@@ -111,8 +124,8 @@ bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
         else b.qkv_t = b.proj_t = b.fc1_t = b.fc2_t = -1;
     }
     p.w_embed = p.w_embed_t = -1;
-    if (p.image) p.w_embed = wtake(off, D * p.K);
-    else if (p.compressed) { p.w_embed = wtake(off, D * c.embed_rank); p.w_embed_t = wtake(off, D * c.embed_rank); }
+    if (em.w >= 0) p.w_embed = wtake(off, D * p.K);
+    if (p.compressed) p.w_embed_t = wtake(off, D * p.K);          // dgrad towards the token table
     p.w_head = wtake(off, E * D);                                 // [E, D] (CLIP towers: proj^T)
     p.w_head_t = p.train ? wtake(off, E * D) : -1;                // [D, E]
     p.w_total = off;
@@ -159,6 +172,16 @@ void take_scores(Bump& b, const Plan& p, AttnPath path, int64_t B, int64_t N, in
     s.stats = path == AttnPath::Mix ? b.take<float>(B * p.H * N) : nullptr;
 }
 
+// What the row-local half of one block execution (exec_mlp) reads and writes, over `rows` rows:
+//   x_mid = xin + proj(ctx) ; xout = x_mid + fc2(act(fc1(LN2(x_mid)))).  The backward reads x_mid, mean2 / rstd2, z and rows of the same set.
+struct RowSet {
+    bf16_t* ctx;                           // attention output (out_proj operand)
+    void *xin, *x_mid, *xout;              // residual in, after the attention branch, out (stream dtype)
+    bf16_t *h2, *u;                        // LN2 output (fc1 operand), fc2 operand
+    float *mean2, *rstd2; uint8_t* z;      // training, else null: LN2 statistics, saved gelu'
+    int64_t rows;
+};
+
 struct Work {
     // persistent
     std::vector<void*> X;                  // residual stream: X[0] embedding output .. X[LR]; f32 for students, f16 for the frozen
@@ -185,14 +208,9 @@ struct Work {
     float* wg_dummy;                       // Mix: [2, H, H] sink for conv_l / conv_w gradients when those parameters are frozen
     float* mix_ws; size_t mix_ws_bytes;    // Mix: per-workgroup weight-gradient partials of dclip_attn_mix_bwd
     void* tn_ws; size_t tn_ws_bytes;       // partial tiles of the 256 x 256 wgrad launches (dclip_gemm_tn_acc)
-    // the last block execution run on the B picked rows only (prune_last): compact [B, .] operands.  Training: the first B rows of
-    // that execution's own saved buffers (the block's [R][M, .] wgrad operands then hold them at the start of slot R - 1) and of
-    // X[nex]; inference: buffers of their own, so that the shared residual stream keeps X[nex - 1] for last_layer_output.
+    // the last block execution run on the B picked rows only (prune_last); where these live is decided in layout()
+    RowSet compact;                        // its [B, .] operands: ctx and xin are gathered (dclip_rows_pick) from ctx_full and X[nex - 1]
     bf16_t* ctx_full;                      // the execution's attention output, all M rows, before its picked rows are gathered
-    void *xr, *xmc, *xoc;                  // gathered residual in, residual after the attention branch, output (stream dtype)
-    bf16_t *cctx, *ch2, *cu;               // out_proj / fc1 / fc2 operands
-    uint8_t* cz;                           // saved gelu' (training)
-    float *cmean2, *crstd2;                // LN2 statistics (training)
     float* Gc;                             // training: [B, D] residual-stream gradient of the compact rows
     AttnPath path;                         // the score stage every buffer above was sized for
     size_t bytes;
@@ -200,6 +218,7 @@ struct Work {
 
 void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_t N = 0) {
     Bump b(base);
+    w = Work{};                            // whatever this tower and mode do not use stays null
     if (N <= 0) N = p.N;
     const int64_t Npad = (N + 7) & ~(int64_t)7;
     const int64_t M = B * N, D = p.D, F = p.F, SN = B * p.H * N * Npad;
@@ -218,8 +237,7 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         shared.x_mid = xs;   // in-place residual stream
         shared.h1 = b.take<bf16_t>(M * D); shared.qkv = b.take<bf16_t>(M * 3 * D);
         take_scores(b, p, w.path, B, N, Npad, shared);
-        shared.ctx = b.take<bf16_t>(M * D); shared.h2 = shared.h1; shared.z = nullptr; shared.u = b.take<bf16_t>(M * F);
-        shared.mean1 = shared.rstd1 = shared.mean2 = shared.rstd2 = nullptr;
+        shared.ctx = b.take<bf16_t>(M * D); shared.h2 = shared.h1; shared.u = b.take<bf16_t>(M * F);
     }
     for (int e = 0; e <= nex; ++e) w.X[e] = save ? (void*)b.take<float>(M * D) : xs;
     for (int e = 0; e < nex; ++e) {
@@ -240,29 +258,34 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
             }
         }
     }
-    // compact operands of the last execution (prune_last)
+    // Compact [B, .] operands of a pruned last execution.  This is the one place that decides where they live; both directions reach
+    // them through w.compact only.
+    //   training : the first B rows of that execution's own saved buffers and of X[nex].  Its ctx / h2 / u are slot R - 1 of the last
+    //              block's [R][M, .] wgrad operands, so those wgrads find the compact rows at the start of that slot and contract over
+    //              (R - 1) M + B rows, with no copy.  The gathered input shares X[nex] with the output: out_proj consumes it before
+    //              fc2 writes.  The all-row attention output goes to the h2 slot, whose rows B.. a pruned execution does not use.
+    //   inference: buffers of their own, so that the shared residual stream keeps X[nex - 1] for last_layer_output.
     {
-        ExecSave& s = w.ex[nex - 1];
+        const ExecSave& s = w.ex[nex - 1];
         if (save) {
-            w.ctx_full = s.h2;                                       // rows B.. of the h2 slot are unused by a pruned execution
-            w.cctx = s.ctx; w.ch2 = s.h2; w.cu = s.u; w.cz = s.z; w.cmean2 = s.mean2; w.crstd2 = s.rstd2;
-            w.xmc = s.x_mid;
-            w.xr = w.xoc = w.X[nex];                                 // the gathered input is consumed (out_proj) before fc2 writes the output
+            w.ctx_full = s.h2;
+            w.compact = RowSet{s.ctx, w.X[nex], s.x_mid, w.X[nex], s.h2, s.u, s.mean2, s.rstd2, s.z, B};
         } else {
             w.ctx_full = shared.ctx;
-            w.cctx = b.take<bf16_t>(B * D); w.ch2 = shared.h1; w.cu = shared.u; w.cz = nullptr; w.cmean2 = w.crstd2 = nullptr;
+            bf16_t* cctx = b.take<bf16_t>(B * D);
             const size_t es = w.h16 ? 2 : 4;
-            w.xr = b.take<char>(B * D * es); w.xmc = b.take<char>(B * D * es); w.xoc = b.take<char>(B * D * es);
+            void* xr = b.take<char>(B * D * es); void* xmc = b.take<char>(B * D * es); void* xoc = b.take<char>(B * D * es);
+            w.compact = RowSet{cctx, xr, xmc, xoc, shared.h1, shared.u, nullptr, nullptr, nullptr, B};
         }
         w.Gc = save ? b.take<float>(B * D) : nullptr;
     }
-    w.patches = p.image ? b.take<bf16_t>(M * p.K) : (p.compressed ? b.take<bf16_t>(M * p.c.embed_rank) : nullptr);
+    w.patches = p.emb.w >= 0 ? b.take<bf16_t>(M * p.K) : nullptr;
     w.tok_table = b.take<float>((int64_t)N * D);
     w.pick = b.take<int32_t>(B);
     w.meanf = b.take<float>(B); w.rstdf = b.take<float>(B);
     w.hf = b.take<bf16_t>(B * D);
-    w.x0 = (!p.student && p.image) ? (w.h16 ? (void*)b.take<_Float16>(M * D) : (void*)b.take<float>(M * D)) : nullptr;
-    const bool pre = save && !p.student && p.image;
+    const bool pre_ln = p.emb.ln_w >= 0, pre = save && pre_ln;        // CLIP image tower
+    w.x0 = pre_ln ? (w.h16 ? (void*)b.take<_Float16>(M * D) : (void*)b.take<float>(M * D)) : nullptr;
     w.mean0 = pre ? b.take<float>(M) : nullptr; w.rstd0 = pre ? b.take<float>(M) : nullptr; w.G0 = pre ? b.take<float>(M * D) : nullptr;
     if (save) {
         w.G = b.take<float>(M * D); w.Gb = b.take<bf16_t>(M * D);
@@ -275,15 +298,19 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         w.mix_ws = w.mix_ws_bytes ? (float*)b.take<char>(w.mix_ws_bytes) : nullptr;
         w.tn_ws_bytes = dclip_gemm_tn_workspace_bytes();
         w.tn_ws = b.take<char>(w.tn_ws_bytes);
-        w.demb = p.compressed ? b.take<float>(M * p.c.embed_rank) : nullptr;
-    } else {
-        w.G = nullptr; w.Gb = nullptr; w.gb_f2 = w.gb_pr = nullptr; w.dbig = w.dh = w.dqkv = w.dR = w.dS = w.dout = nullptr; w.tok_sum = w.demb = nullptr; w.wg_dummy = nullptr;
-        w.mix_ws = nullptr; w.mix_ws_bytes = 0; w.tn_ws = nullptr; w.tn_ws_bytes = 0;
+        w.demb = p.compressed ? b.take<float>(M * p.K) : nullptr;
     }
     w.bytes = b.off;
 }
 
-inline const float* PF(const void* const* params, int i) { return (const float*)params[i]; }
+// the full-row set of block execution ei
+inline RowSet full_rows(const Work& w, int ei, int64_t M) {
+    const ExecSave& s = w.ex[ei];
+    return RowSet{s.ctx, w.X[ei], s.x_mid, w.X[ei + 1], s.h2, s.u, s.mean2, s.rstd2, s.z, M};
+}
+
+// parameter i of the canonical order, null for an index the tower does not have (-1)
+inline const float* PF(const void* const* params, int i) { return i < 0 ? nullptr : (const float*)params[i]; }
 
 // split count of the wgrad contraction: minimise  rounds(tiles*s / 512 resident workgroups) * work per workgroup
 //                                                   + atomic traffic (s * P*Q*4 bytes at ~1.3 TB/s, half hidden)
@@ -392,30 +419,17 @@ extern "C" size_t dclip_encoder_workspace_bytes(const dclip_encoder* e, int64_t 
 
 // parameter index helpers -------------------------------------------------------------------------------------
 namespace {
-struct TB { int ln1w, ln1b, inw, inb, outw, outb, ln2w, ln2b, fcw, fcb, prw, prb; };
-inline TB tblock(const Plan& p, int l) {
-    const int b = p.p_blocks + l * P_PER_TBLOCK;
-    return TB{b, b + 1, b + 2, b + 3, b + 4, b + 5, b + 6, b + 7, b + 8, b + 9, b + 10, b + 11};
-}
-struct SB { int qkvw, qkvb, prw, prb, f1w, f1b, f2w, f2b; };
-inline SB sblock(const Plan& p, int l) {
-    const int b = p.p_blocks + l * (P_PER_SBLOCK + p.R * P_PER_SREPEAT);
-    return SB{b, b + 1, b + 2, b + 3, b + 4, b + 5, b + 6, b + 7};
-}
-struct SR { int n1w, n1b, n2w, n2b, cl, cw; };
-// one block execution's parameters under the names the backward uses, for both architectures (CLIP: ln_1/2, in_proj, out_proj, c_fc, c_proj)
+// one block execution's parameters under the names the backward uses, for both architectures (CLIP: ln_1/2, in_proj, out_proj, c_fc, c_proj;
+// no conv_l / conv_w).  The order inside a block is the canonical one (include/dclip.h).
 struct BX { int n1w, n1b, n2w, n2b, qkvw, qkvb, prw, prb, f1w, f1b, f2w, f2b, cl, cw; };
-inline SR srepeat(const Plan& p, int l, int r) {
-    const int b = p.p_blocks + l * (P_PER_SBLOCK + p.R * P_PER_SREPEAT) + P_PER_SBLOCK + r * P_PER_SREPEAT;
-    return SR{b, b + 1, b + 2, b + 3, b + 4, b + 5};
-}
 inline BX bexec(const Plan& p, int l, int r) {
-    if (p.student) {
-        const SB s = sblock(p, l); const SR q = srepeat(p, l, r);
-        return BX{q.n1w, q.n1b, q.n2w, q.n2b, s.qkvw, s.qkvb, s.prw, s.prb, s.f1w, s.f1b, s.f2w, s.f2b, q.cl, q.cw};
+    if (!p.student) {       // ln_1, attn.in_proj, attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj: weight, bias each
+        const int b = p.p_blocks + l * P_PER_TBLOCK;
+        return BX{b, b + 1, b + 6, b + 7, b + 2, b + 3, b + 4, b + 5, b + 8, b + 9, b + 10, b + 11, -1, -1};
     }
-    const TB t = tblock(p, l);
-    return BX{t.ln1w, t.ln1b, t.ln2w, t.ln2b, t.inw, t.inb, t.outw, t.outb, t.fcw, t.fcb, t.prw, t.prb, -1, -1};
+    // the block's shared qkv, proj, fc1, fc2 (weight, bias each), then per repeat norm1 w b, norm2 w b, conv_l, conv_w
+    const int b = p.p_blocks + l * (P_PER_SBLOCK + p.R * P_PER_SREPEAT), q = b + P_PER_SBLOCK + r * P_PER_SREPEAT;
+    return BX{q, q + 1, q + 2, q + 3, b, b + 1, b + 2, b + 3, b + 4, b + 5, b + 6, b + 7, q + 4, q + 5};
 }
 
 // the parameters one block execution's forward reads
@@ -437,24 +451,23 @@ int exec_attn(const Plan& p, AttnPath path, const ExecSave& s, const bf16_t* W, 
     return attn_forward(path, p, s, e.wl, e.ww, B, N, st);
 }
 
-// second half, row-local, on `rows` rows: x_mid = xin + proj(ctx), xout = x_mid + fc2(act(fc1(LN2(x_mid)))).  z (nullable) receives
-// the saved activation derivative, mean2 / rstd2 (nullable) the LN2 statistics.
-int exec_mlp(const Plan& p, const bf16_t* W, int l, const EP& e, bool h16, const bf16_t* ctx, const void* xin, void* x_mid, bf16_t* h2,
-             float* mean2, float* rstd2, bf16_t* u, uint8_t* z, void* xout, int64_t rows, void* st) {
-    const int64_t D = p.D, F = p.F;
+// second half, row-local, on the rows of `rs` (see RowSet): z, if there, receives the saved activation derivative, mean2 / rstd2 the LN2
+// statistics
+int exec_mlp(const Plan& p, const bf16_t* W, int l, const EP& e, bool h16, const RowSet& rs, void* st) {
+    const int64_t D = p.D, F = p.F, rows = rs.rows;
     const auto& bw = p.bw[l];
     const int sdt = h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;            // dtype of the residual stream
-    const int act = p.student ? (z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU);
-    CK(gemm(ctx, D, W + bw.proj, D, x_mid, D, rows, D, D, e.bp, 0, nullptr, nullptr, xin, D, sdt, 0, nullptr, st));
-    CK(ln_stream(h16, x_mid, D, nullptr, e.n2w, e.n2b, h2, D, DCLIP_OUT_BF16, mean2, rstd2, rows, D, st));
-    CK(gemm(h2, D, W + bw.fc1, D, u, F, rows, F, D, e.b1, act, nullptr, z, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
-    return gemm(u, F, W + bw.fc2, F, xout, D, rows, D, F, e.b2, 0, nullptr, nullptr, x_mid, D, sdt, 0, nullptr, st);
+    const int act = p.student ? (rs.z ? DCLIP_ACT_GELU_SAVE : DCLIP_ACT_GELU) : (rs.z ? DCLIP_ACT_QUICKGELU_SAVE : DCLIP_ACT_QUICKGELU);
+    CK(gemm(rs.ctx, D, W + bw.proj, D, rs.x_mid, D, rows, D, D, e.bp, 0, nullptr, nullptr, rs.xin, D, sdt, 0, nullptr, st));
+    CK(ln_stream(h16, rs.x_mid, D, nullptr, e.n2w, e.n2b, rs.h2, D, DCLIP_OUT_BF16, rs.mean2, rs.rstd2, rows, D, st));
+    CK(gemm(rs.h2, D, W + bw.fc1, D, rs.u, F, rows, F, D, e.b1, act, nullptr, rs.z, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
+    return gemm(rs.u, F, W + bw.fc2, F, rs.xout, D, rows, D, F, e.b2, 0, nullptr, nullptr, rs.x_mid, D, sdt, 0, nullptr, st);
 }
 
 // Scratch of dclip_encoder_last_layer_output: after a pruned forward it re-runs the last execution on all rows into buffers of its
-// own (a pending backward's saved activations stay untouched).  h1 comes first: it is also the bf16 final-LN output, the whole
-// scratch an unpruned forward needs.
-size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base, ExecSave& t, void*& xout) {
+// own (a pending backward's saved activations stay untouched): t for its attention half, rs (reading the residual xin) for its
+// row-local half.  h1 comes first: it is also the bf16 final-LN output, the whole scratch an unpruned forward needs.
+size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base, void* xin, ExecSave& t, RowSet& rs) {
     Bump b(base);
     const int64_t N = p.N, M = B * N, D = p.D, F = p.F;
     const size_t es = h16 ? 2 : 4;
@@ -465,7 +478,7 @@ size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base
     t.ctx = b.take<bf16_t>(M * D);
     t.x_mid = b.take<char>(M * D * es);
     t.u = b.take<bf16_t>(M * F);
-    xout = b.take<char>(M * D * es);
+    rs = RowSet{t.ctx, xin, t.x_mid, b.take<char>(M * D * es), t.h2, t.u, nullptr, nullptr, nullptr, M};
     return b.off;
 }
 
@@ -473,6 +486,35 @@ size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base
 inline bool prune_last_enabled() {
     static const int v = [] { const char* e = getenv("DCLIP_PRUNE_LAST"); return e ? atoi(e) : 1; }();
     return v != 0;
+}
+
+// One walk of a dclip_attn_maps descriptor for both directions: its two pointer arrays (forward: the score / prob outputs; backward:
+// d_score / d_prob) checked against the plan and spread to one entry per block execution.  The forward (rec = null) also notes what it
+// was given as one bit per execution, for the record; the backward passes that record and is refused a gradient for a map not in it.
+template <class T> struct ExecMaps { std::vector<T*> score, prob; uint64_t score_bits = 0, prob_bits = 0; };
+template <class T>
+int exec_maps(const Plan& p, const dclip_attn_maps* maps, T* const* score, T* const* prob, const dclip_encoder_run* rec, const char* fn,
+              ExecMaps<T>& out) {
+    const int nex = p.L * p.R;
+    out.score.assign(nex, nullptr); out.prob.assign(nex, nullptr);
+    if (!maps || !maps->n) return DCLIP_OK;
+    DCLIP_REQUIRE(maps->n > 0 && maps->exec, "%s: maps need n > 0 execution indices", fn);
+    for (int k = 0; k < maps->n; ++k) {
+        const int ei = maps->exec[k];
+        DCLIP_REQUIRE(ei >= 0 && ei < nex, "%s: map %d: block execution %d out of range 0..%d", fn, k, ei, nex - 1);
+        T* sm = score ? score[k] : nullptr;
+        T* pm = prob ? prob[k] : nullptr;
+        if (!rec) {
+            DCLIP_REQUIRE(ei < 64, "%s: map %d: block execution %d: maps are exported for executions 0..63 only", fn, k, ei);
+        } else {
+            const bool had_s = ei < 64 && (rec->score_maps >> ei & 1), had_p = ei < 64 && (rec->prob_maps >> ei & 1);
+            DCLIP_REQUIRE((!sm || had_s) && (!pm || had_p), "%s: a gradient for the %s map of block execution %d, which the forward did not export",
+                          fn, sm && !had_s ? "score" : "probability", ei);
+        }
+        if (sm) { out.score[ei] = sm; out.score_bits |= (uint64_t)1 << ei; }
+        if (pm) { out.prob[ei] = pm; out.prob_bits |= (uint64_t)1 << ei; }
+    }
+    return DCLIP_OK;
 }
 }  // namespace
 
@@ -487,18 +529,15 @@ extern "C" int dclip_encoder_prepare(const dclip_encoder* e, const void* const* 
     auto job = [&](const float* w, void* b, void* t, int64_t R, int64_t C) { src.push_back(w); wb.push_back(b); wt.push_back(t); rr.push_back(R); cc.push_back(C); };
     for (int l = 0; l < p.L; ++l) {
         const auto& b = p.bw[l];
-        int iq, ip, i1, i2;
-        if (p.student) { SB s = sblock(p, l); iq = s.qkvw; ip = s.prw; i1 = s.f1w; i2 = s.f2w; }
-        else { TB t = tblock(p, l); iq = t.inw; ip = t.outw; i1 = t.fcw; i2 = t.prw; }
-        job(PF(params, iq), at(b.qkv), at(b.qkv_t), 3 * D, D);
-        job(PF(params, ip), at(b.proj), at(b.proj_t), D, D);
-        job(PF(params, i1), at(b.fc1), at(b.fc1_t), F, D);
-        job(PF(params, i2), at(b.fc2), at(b.fc2_t), D, F);
+        const BX bx = bexec(p, l, 0);
+        job(PF(params, bx.qkvw), at(b.qkv), at(b.qkv_t), 3 * D, D);
+        job(PF(params, bx.prw), at(b.proj), at(b.proj_t), D, D);
+        job(PF(params, bx.f1w), at(b.fc1), at(b.fc1_t), F, D);
+        job(PF(params, bx.f2w), at(b.fc2), at(b.fc2_t), D, F);
     }
-    if (p.image) job(PF(params, 0), at(p.w_embed), nullptr, D, p.K);                          // conv weight [D, C*p*p]
-    else if (p.compressed) job(PF(params, 1), at(p.w_embed), at(p.w_embed_t), D, p.c.embed_rank);
-    if (p.student) job(PF(params, p.p_final + 2), at(p.w_head), at(p.w_head_t), E, D);
-    else job(PF(params, p.p_final + 2), at(p.w_head_t), at(p.w_head), D, E);                  // proj [D,E] -> [E,D] (+ as it is: the dgrad operand of a trainable tower)
+    if (p.emb.w >= 0) job(PF(params, p.emb.w), at(p.w_embed), at(p.w_embed_t), D, p.K);       // conv weight [D, C*p*p] / compressed-text linear [D, rank]
+    if (p.student) job(PF(params, p.head.head_w), at(p.w_head), at(p.w_head_t), E, D);
+    else job(PF(params, p.head.head_w), at(p.w_head_t), at(p.w_head), D, E);                  // proj [D,E] -> [E,D] (+ as it is: the dgrad operand of a trainable tower)
     for (size_t i = 0; i < src.size(); ++i) DCLIP_REQUIRE(src[i], "dclip_encoder_prepare: parameter %zu missing", i);
     return dclip_cast_transpose_bf16_multi(src.data(), wb.data(), wt.data(), rr.data(), cc.data(), (int64_t)src.size(), st);
 }
@@ -513,18 +552,10 @@ extern "C" int dclip_encoder_prepare(const dclip_encoder* e, const void* const* 
 static int clear_backward_seeds(const Plan& p, const Work& w, int64_t M, int64_t B, bool pruned, void* st) {
     const int64_t D = p.D;
     hipStream_t hs = (hipStream_t)st;
-    if (pruned) {
-        if (hipMemsetAsync(w.Gc, 0, (size_t)B * D * 4, hs) != hipSuccess) {
-            dclip_set_error("dclip_encoder: clearing the backward seeds failed");
-            return DCLIP_ELAUNCH;
-        }
-        return DCLIP_OK;
-    }
     bf16_t* gb_last = w.gb_f2 + (int64_t)(p.R - 1) * M * D;
-    if (hipMemsetAsync(w.G, 0, (size_t)M * D * 4, hs) != hipSuccess || hipMemsetAsync(gb_last, 0, (size_t)M * D * 2, hs) != hipSuccess) {
-        dclip_set_error("dclip_encoder: clearing the backward seeds failed");
-        return DCLIP_ELAUNCH;
-    }
+    const bool ok = pruned ? hipMemsetAsync(w.Gc, 0, (size_t)B * D * 4, hs) == hipSuccess
+                           : hipMemsetAsync(w.G, 0, (size_t)M * D * 4, hs) == hipSuccess && hipMemsetAsync(gb_last, 0, (size_t)M * D * 2, hs) == hipSuccess;
+    if (!ok) { dclip_set_error("dclip_encoder: clearing the backward seeds failed"); return DCLIP_ELAUNCH; }
     return DCLIP_OK;
 }
 
@@ -545,22 +576,11 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     // attention; LN / MLP are per token), so the tower may run on the first tokens_eff positions with identical output.
     DCLIP_REQUIRE(tokens_eff == 0 || (!p.train && !p.image && p.c.causal && tokens_eff > 0 && tokens_eff <= p.N && !rep_out && !emb_out),
                   "dclip_encoder_forward: tokens_eff is only valid for the causal text teacher without hidden-state export");
-    // head-mean attention maps per block execution, and which were asked for as the record notes them (one bit per execution)
-    std::vector<float*> map_s(p.L * p.R, nullptr), map_p(p.L * p.R, nullptr);
-    uint64_t score_maps = 0, prob_maps = 0;
-    if (maps && maps->n) {
-        DCLIP_REQUIRE(maps->n > 0 && maps->exec, "dclip_encoder_forward: maps need n > 0 execution indices");
-        DCLIP_REQUIRE(tokens_eff == 0, "dclip_encoder_forward: attention maps cannot be exported from a caption prefix (tokens_eff)");
-        for (int k = 0; k < maps->n; ++k) {
-            const int ei = maps->exec[k];
-            DCLIP_REQUIRE(ei >= 0 && ei < p.L * p.R, "dclip_encoder_forward: map %d: block execution %d out of range 0..%d", k, ei, p.L * p.R - 1);
-            DCLIP_REQUIRE(ei < 64, "dclip_encoder_forward: map %d: block execution %d: maps are exported for executions 0..63 only", k, ei);
-            float* sm = maps->score ? maps->score[k] : nullptr;
-            float* pm = maps->prob ? maps->prob[k] : nullptr;
-            if (sm) { map_s[ei] = sm; score_maps |= (uint64_t)1 << ei; }
-            if (pm) { map_p[ei] = pm; prob_maps |= (uint64_t)1 << ei; }
-        }
-    }
+    // head-mean attention maps per block execution
+    DCLIP_REQUIRE(!(maps && maps->n > 0 && maps->exec) || tokens_eff == 0,
+                  "dclip_encoder_forward: attention maps cannot be exported from a caption prefix (tokens_eff)");
+    ExecMaps<float> xm;
+    CK(exec_maps<float>(p, maps, maps ? maps->score : nullptr, maps ? maps->prob : nullptr, nullptr, "dclip_encoder_forward", xm));
     Work w;
     layout(p, B, training != 0, workspace, w, tokens_eff);
     DCLIP_REQUIRE(ws_bytes >= w.bytes, "dclip_encoder_forward: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
@@ -570,36 +590,32 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     const int nex = p.L * p.R;
 
     // ---- embedding -----------------------------------------------------------------------------------------
-    if (p.image) {
+    // GEMM embeddings (image patches; compressed text): rows [M, K] x weight [D, K], plus a per-token table (pos + cls / bias) added by
+    // row group.  The CLIP image tower alone normalises the result (ln_pre) on its way into the stream; plain text is a gather.
+    const Plan::EmbP& em = p.emb;
+    const bool pre_ln = em.ln_w >= 0;
+    const int sdt = w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;            // dtype of the residual stream
+    if (em.w >= 0) {
         const bf16_t* rows = ext_patches ? ext_patches : w.patches;
-        if (!ext_patches) CK(dclip_im2row((const float*)input, w.patches, B, p.c.in_chans, p.c.resolution, p.c.patch, 1, st));
-        if (p.student) {   // params: 0 conv w, 1 conv b, 2 cls_token, 3 pos_embed
-            CK(dclip_token_table(PF(params, 3), PF(params, 2), PF(params, 1), w.tok_table, N, D, st));
-            CK(gemm(rows, p.K, W + p.w_embed, p.K, w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, N, w.tok_table, st));
-        } else {           // params: 0 conv1 w, 1 class_embedding, 2 positional_embedding, 3 ln_pre w, 4 ln_pre b
-            CK(dclip_token_table(PF(params, 2), PF(params, 1), nullptr, w.tok_table, N, D, st));
-            const int sdt0 = w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32;
-            CK(gemm(rows, p.K, W + p.w_embed, p.K, w.x0, D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, sdt0, N, w.tok_table, st));
-            CK(ln_stream(w.h16, w.x0, D, nullptr, PF(params, 3), PF(params, 4), w.X[0], D, sdt0, w.mean0, w.rstd0, M, D, st));
-        }
-    } else if (p.compressed) {   // params: 0 table [V,rank], 1 linear w [D,rank], 2 linear b, 3 pos
-        CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, 0), nullptr, w.patches, 0, M, N, p.c.embed_rank, st));
-        CK(dclip_token_table(PF(params, 3), nullptr, PF(params, 2), w.tok_table, N, D, st));
-        CK(gemm(w.patches, p.c.embed_rank, W + p.w_embed, p.c.embed_rank, w.X[0], D, M, D, p.c.embed_rank, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, N, w.tok_table, st));
-    } else {                     // params: 0 table [V,D], 1 pos [N,D]
-        CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, 0), PF(params, 1), w.X[0], w.h16 ? DCLIP_OUT_F16 : DCLIP_OUT_F32, M, N, D, st));
+        if (!p.image) CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, em.table), nullptr, w.patches, 0, M, N, p.K, st));
+        else if (!ext_patches) CK(dclip_im2row((const float*)input, w.patches, B, p.c.in_chans, p.c.resolution, p.c.patch, 1, st));
+        CK(dclip_token_table(PF(params, em.pos), PF(params, em.cls), PF(params, em.bias), w.tok_table, N, D, st));
+        CK(gemm(rows, p.K, W + p.w_embed, p.K, pre_ln ? w.x0 : w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, sdt, N, w.tok_table, st));
+        if (pre_ln) CK(ln_stream(w.h16, w.x0, D, nullptr, PF(params, em.ln_w), PF(params, em.ln_b), w.X[0], D, sdt, w.mean0, w.rstd0, M, D, st));
+    } else {
+        CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, em.table), PF(params, em.pos), w.X[0], sdt, M, N, D, st));
     }
 
     // optional export of the post-positional-embedding tokens (reference ControlOutput.need_emb: _common.py:204-206 captures
     // them BEFORE ln_pre; text_encoder.py:66-67 ; weight_share_model.py:350,490)
-    if (emb_out) CK(export_stream(w.h16, (!p.student && p.image) ? w.x0 : w.X[0], emb_out, M * D, st));
+    if (emb_out) CK(export_stream(w.h16, pre_ln ? w.x0 : w.X[0], emb_out, M * D, st));
 
     // ---- blocks --------------------------------------------------------------------------------------------
     // Only the picked token of each sample (class token / EOT = argmax of the ids) leaves the tower, and after the last execution's
     // attention everything is row-local: unless its hidden state or maps are exported, that execution's out_proj, LN2 and MLP run on
     // the B picked rows only (its attention still runs on all M rows: the picked queries attend to every key).
     CK(dclip_pick_index(p.image ? nullptr : (const int64_t*)input, p.N, w.pick, B, N, st));
-    const bool prune = prune_last_enabled() && !(rep_out && rep_out[nex - 1]) && !map_s[nex - 1] && !map_p[nex - 1];
+    const bool prune = prune_last_enabled() && !(rep_out && rep_out[nex - 1]) && !xm.score[nex - 1] && !xm.prob[nex - 1];
     for (int ei = 0; ei < nex; ++ei) {
         const int l = ei / p.R, r = ei % p.R;
         const ExecSave& s = w.ex[ei];
@@ -609,29 +625,26 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
         if (compact) sa.ctx = w.ctx_full;
         CK(exec_attn(p, w.path, sa, W, l, ep, w.h16, w.X[ei], B, N, st));
         // before the next execution reuses the inference set's qkv
-        if (map_s[ei] || map_p[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, ep.wl, map_s[ei], map_p[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
-        if (!compact) {
-            CK(exec_mlp(p, W, l, ep, w.h16, s.ctx, w.X[ei], s.x_mid, s.h2, s.mean2, s.rstd2, s.u, s.z, w.X[ei + 1], M, st));
-        } else {
-            CK(dclip_rows_pick(w.ctx_full, w.cctx, w.pick, B, D * 2, st));
-            CK(dclip_rows_pick(w.X[ei], w.xr, w.pick, B, D * (w.h16 ? 2 : 4), st));
-            CK(exec_mlp(p, W, l, ep, w.h16, w.cctx, w.xr, w.xmc, w.ch2, w.cmean2, w.crstd2, w.cu, w.cz, w.xoc, B, st));
+        if (xm.score[ei] || xm.prob[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, ep.wl, xm.score[ei], xm.prob[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
+        if (compact) {
+            CK(dclip_rows_pick(w.ctx_full, w.compact.ctx, w.pick, B, D * 2, st));
+            CK(dclip_rows_pick(w.X[ei], w.compact.xin, w.pick, B, D * (w.h16 ? 2 : 4), st));
         }
+        CK(exec_mlp(p, W, l, ep, w.h16, compact ? w.compact : full_rows(w, ei, M), st));
         // optional export of this execution's hidden state (ControlOutput.need_rep: _common.py:156-158, weight_share_model.py:211)
         if (rep_out && rep_out[ei]) CK(export_stream(w.h16, w.X[ei + 1], rep_out[ei], M * D, st));
     }
 
     // ---- final norm + projection on the picked token only ------------------------------------------------------
-    const int f = p.p_final;
-    CK(ln_stream(w.h16, prune ? w.xoc : w.X[nex], D, prune ? nullptr : w.pick, PF(params, f), PF(params, f + 1), w.hf, D, DCLIP_OUT_BF16,
-                 w.meanf, w.rstdf, B, D, st));
-    CK(gemm(w.hf, D, W + p.w_head, D, last_representation, E, B, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
+    CK(ln_stream(w.h16, prune ? w.compact.xout : w.X[nex], D, prune ? nullptr : w.pick, PF(params, p.head.norm_w), PF(params, p.head.norm_b), w.hf, D,
+                 DCLIP_OUT_BF16, w.meanf, w.rstdf, B, D, st));
+    CK(gemm(w.hf, D, W + p.w_head, D, last_representation, E, B, E, D, PF(params, p.head.head_b), 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
     *run = dclip_encoder_run{prune ? RUN_PRUNED : 0u, 0, 0, 0};
     if (training) {
         CK(clear_backward_seeds(p, w, M, B, prune, st));
         run->flags |= RUN_SEEDS_CLEAR;
-        run->score_maps = score_maps;
-        run->prob_maps = prob_maps;
+        run->score_maps = xm.score_bits;
+        run->prob_maps = xm.prob_bits;
     }
     return DCLIP_OK;
 }
@@ -644,11 +657,10 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
 // unpruned forward leaves, and nothing a pending backward reads is touched.
 extern "C" size_t dclip_encoder_last_layer_output_scratch_bytes(const dclip_encoder* e, int64_t B, int training) {
     if (!e || B <= 0) return 0;
-    Work w;
-    layout(e->p, B, training != 0, nullptr, w);
+    const Plan& p = e->p;
     ExecSave t;
-    void* xout;
-    return llo_scratch(e->p, w.path, w.h16, B, nullptr, t, xout);
+    RowSet rs;
+    return llo_scratch(p, attn_path(p, p.train && training != 0), !p.train, B, nullptr, nullptr, t, rs);
 }
 
 extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B, const void* const* params, const void* wcache,
@@ -663,20 +675,20 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
     DCLIP_REQUIRE(ws_bytes >= w.bytes, "dclip_encoder_last_layer_output: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
     const bf16_t* W = (const bf16_t*)wcache;
     const int64_t M = B * p.N, D = p.D, E = p.E;
-    const int nex = p.L * p.R, f = p.p_final;
+    const int nex = p.L * p.R;
     const void* xlast = w.X[nex];
     if (run->flags & RUN_PRUNED) {
         ExecSave t;
-        void* xout;
-        llo_scratch(p, w.path, w.h16, B, scratch, t, xout);
+        RowSet rs;
         const int ei = nex - 1, l = ei / p.R;
+        llo_scratch(p, w.path, w.h16, B, scratch, w.X[ei], t, rs);
         const EP ep = exec_params(p, params, l, ei % p.R);
         CK(exec_attn(p, w.path, t, W, l, ep, w.h16, w.X[ei], B, p.N, st));
-        CK(exec_mlp(p, W, l, ep, w.h16, t.ctx, w.X[ei], t.x_mid, t.h2, nullptr, nullptr, t.u, nullptr, xout, M, st));
-        xlast = xout;
+        CK(exec_mlp(p, W, l, ep, w.h16, rs, st));
+        xlast = rs.xout;
     }
-    CK(ln_stream(w.h16, xlast, D, nullptr, PF(params, f), PF(params, f + 1), scratch, D, DCLIP_OUT_BF16, nullptr, nullptr, M, D, st));
-    CK(gemm(scratch, D, W + p.w_head, D, out, E, M, E, D, p.student ? PF(params, f + 3) : nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
+    CK(ln_stream(w.h16, xlast, D, nullptr, PF(params, p.head.norm_w), PF(params, p.head.norm_b), scratch, D, DCLIP_OUT_BF16, nullptr, nullptr, M, D, st));
+    CK(gemm(scratch, D, W + p.w_head, D, out, E, M, E, D, PF(params, p.head.head_b), 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
     return DCLIP_OK;
 }
 
@@ -691,30 +703,12 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     DCLIP_REQUIRE(!ext_patches || p.image, "dclip_encoder_backward: patches: image towers only");
     DCLIP_REQUIRE(p.train, "dclip_encoder_backward: the frozen teacher tower (kind 0) has no backward");
     // gradients of exported head-mean maps, per block execution
-    std::vector<MapGrad> mgrad(p.L * p.R, MapGrad{nullptr, nullptr, nullptr, 0});
-    std::vector<uint8_t> has_mg(p.L * p.R, 0);
-    if (maps && maps->n) {
-        DCLIP_REQUIRE(maps->n > 0 && maps->exec, "dclip_encoder_backward: maps need n > 0 execution indices");
-        for (int k = 0; k < maps->n; ++k) {
-            const int ei = maps->exec[k];
-            DCLIP_REQUIRE(ei >= 0 && ei < p.L * p.R, "dclip_encoder_backward: map %d: block execution %d out of range 0..%d", k, ei, p.L * p.R - 1);
-            const float* gs = maps->d_score ? maps->d_score[k] : nullptr;
-            const float* gp = maps->d_prob ? maps->d_prob[k] : nullptr;
-            const bool had_s = ei < 64 && (run->score_maps >> ei & 1), had_p = ei < 64 && (run->prob_maps >> ei & 1);
-            DCLIP_REQUIRE((!gs || had_s) && (!gp || had_p),
-                          "dclip_encoder_backward: a gradient for the %s map of block execution %d, which the forward did not export",
-                          gs && !had_s ? "score" : "probability", ei);
-            if (gs) mgrad[ei].d_score = gs;
-            if (gp) mgrad[ei].d_prob = gp;
-            if (gs || gp) has_mg[ei] = 1;
-        }
-        if (p.mixing) {
-            const size_t need = dclip_attn_maps_bwd_workspace_bytes(B, p.H, p.N);
-            for (int ei = 0; ei < p.L * p.R; ++ei)
-                DCLIP_REQUIRE(!mgrad[ei].d_prob || (maps->scratch && maps->scratch_bytes >= need),
-                              "dclip_encoder_backward: probability-map gradients of a head-mixing tower need %zu bytes of maps scratch", need);
-        }
-        for (auto& g : mgrad) { g.scratch = maps->scratch; g.scratch_bytes = maps->scratch_bytes; }
+    ExecMaps<const float> gm;
+    CK(exec_maps<const float>(p, maps, maps ? maps->d_score : nullptr, maps ? maps->d_prob : nullptr, run, "dclip_encoder_backward", gm));
+    if (p.mixing && gm.prob_bits) {
+        const size_t need = dclip_attn_maps_bwd_workspace_bytes(B, p.H, p.N);
+        DCLIP_REQUIRE(maps->scratch && maps->scratch_bytes >= need,
+                      "dclip_encoder_backward: probability-map gradients of a head-mixing tower need %zu bytes of maps scratch", need);
     }
     Work w;
     layout(p, B, true, workspace, w);
@@ -727,9 +721,9 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     DCLIP_REQUIRE(!pruned || !(d_rep && d_rep[nex - 1]),
                   "dclip_encoder_backward: a gradient for the hidden state of block execution %d, which the forward ran on the class / EOT "
                   "rows only (request that hidden state in the forward, or set DCLIP_PRUNE_LAST=0)", nex - 1);
-    DCLIP_REQUIRE(!pruned || !has_mg[nex - 1],
+    DCLIP_REQUIRE(!pruned || !(gm.score[nex - 1] || gm.prob[nex - 1]),
                   "dclip_encoder_backward: a map gradient for block execution %d, which the forward ran on the class / EOT rows only", nex - 1);
-    auto GR = [&](int i) -> float* { return (float*)grads[i]; };
+    auto GR = [&](int i) -> float* { return i < 0 ? nullptr : (float*)grads[i]; };    // null: frozen, or no such parameter (-1)
     hipStream_t hs = (hipStream_t)st;
 
     // the seeds were cleared at the end of the training forward of this workspace (clear_backward_seeds) unless a backward has consumed
@@ -737,13 +731,12 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     if (run->flags & RUN_SEEDS_CLEAR) run->flags &= ~RUN_SEEDS_CLEAR;
     else CK(clear_backward_seeds(p, w, M, B, pruned, st));
     // ---- head + final norm -----------------------------------------------------------------------------------
-    const int f = p.p_final;
     CK(dclip_cast_bf16(d_last_representation, w.dout, B * E, st));
     if (p.student) {         // head = nn.Linear: weight [E, D], bias
-        if (GR(f + 2)) CK(dclip_gemm_tn_acc(w.dout, E, w.hf, D, GR(f + 2), D, B, E, D, 1, w.tn_ws, w.tn_ws_bytes, st));
-        if (GR(f + 3)) CK(dclip_colsum_acc(w.dout, E, GR(f + 3), B, E, st));
-    } else if (GR(f + 2)) {  // x @ proj: proj [D, E], no bias (reference _common.py:213, text_encoder.py:72)
-        CK(dclip_gemm_tn_acc(w.hf, D, w.dout, E, GR(f + 2), E, B, D, E, 1, w.tn_ws, w.tn_ws_bytes, st));
+        if (GR(p.head.head_w)) CK(dclip_gemm_tn_acc(w.dout, E, w.hf, D, GR(p.head.head_w), D, B, E, D, 1, w.tn_ws, w.tn_ws_bytes, st));
+        if (GR(p.head.head_b)) CK(dclip_colsum_acc(w.dout, E, GR(p.head.head_b), B, E, st));
+    } else if (GR(p.head.head_w)) {  // x @ proj: proj [D, E], no bias (reference _common.py:213, text_encoder.py:72)
+        CK(dclip_gemm_tn_acc(w.hf, D, w.dout, E, GR(p.head.head_w), E, B, D, E, 1, w.tn_ws, w.tn_ws_bytes, st));
     }
     CK(gemm(w.dout, E, W + p.w_head_t, E, w.dh, D, B, D, E, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
     // every LayerNorm backward also emits the column sums of the updated residual gradient = the bias gradient of the
@@ -751,8 +744,8 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     const int R = p.R;
     bf16_t* gb_last = w.gb_f2 + (int64_t)(R - 1) * M * D;            // fc2 of the last execution reads slot R - 1
     // (pruned: the compact rows of the last execution's output and of its gradient, identity pick)
-    CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)(pruned ? w.xoc : w.X[nex]), D, pruned ? nullptr : w.pick, PF(params, f), w.meanf, w.rstdf,
-                           pruned ? w.Gc : w.G, D, gb_last, D, GR(f), GR(f + 1), GR(bexec(p, (nex - 1) / p.R, 0).f2b), B, D, st));
+    CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)(pruned ? w.compact.xout : w.X[nex]), D, pruned ? nullptr : w.pick, PF(params, p.head.norm_w), w.meanf,
+                           w.rstdf, pruned ? w.Gc : w.G, D, gb_last, D, GR(p.head.norm_w), GR(p.head.norm_b), GR(bexec(p, (nex - 1) / p.R, 0).f2b), B, D, st));
     // gradient bucket 0 (final norm + head) is complete: every launch that writes it is enqueued on `st`
     if (on_bucket) on_bucket(cb_user, 0);
 
@@ -772,20 +765,21 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
         bf16_t* dqkv = w.dqkv + (int64_t)r * M * 3 * D;
         const int64_t MR = (int64_t)R * M;
         const ExecSave& s0 = w.ex[ei - r];                               // execution r = 0 of this block: base of the [R][M, .] operands
-        // pruned last execution: its out_proj / MLP backward runs on its B compact rows, which sit at the start of its slots, so the
-        // last block's fc1 / fc2 / out_proj wgrads contract over (R - 1) M + B rows
+        // the row-local half's saved operands: after a pruned forward the last execution's are the B compact rows, and the last block's
+        // fc1 / fc2 / out_proj wgrads contract over (R - 1) M + B rows (see layout())
         const bool compact = pruned && ei == nex - 1;
-        const int64_t Mx = compact ? B : M;
+        const RowSet rs = compact ? w.compact : full_rows(w, ei, M);
+        const int64_t Mx = rs.rows;
         const int64_t MRw = pruned && l == p.L - 1 ? (int64_t)(R - 1) * M + B : MR;
         // gradient arriving directly at this execution's output (feature-MSE terms): G += d_rep[ei], refresh the bf16 copy
         if (d_rep && d_rep[ei]) CK(dclip_axpy_f32(w.G, d_rep[ei], gb_f2, M * D, GR(bx.f2b), D, st));
         // MLP: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
-        CK(dclip_gemm_nt(gb_f2, D, W + bw.fc2_t, D, dbig, F, Mx, F, D, 1.f, nullptr, DCLIP_ACT_MULAUX, s.z, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr,
+        CK(dclip_gemm_nt(gb_f2, D, W + bw.fc2_t, D, dbig, F, Mx, F, D, 1.f, nullptr, DCLIP_ACT_MULAUX, rs.z, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr,
                          GR(bx.f1b), st));                                        // dz = (G W2) o gelu'(z) ; db1 += colsum(dz)
         if (r == 0 && GR(bx.f2w)) CK(dclip_gemm_tn_acc(w.gb_f2, D, s0.u, F, GR(bx.f2w), F, MRw, D, F, wsplits(MRw, D, F), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && GR(bx.f1w)) CK(dclip_gemm_tn_acc(w.dbig, F, s0.h2, D, GR(bx.f1w), D, MRw, F, D, wsplits(MRw, F, D), w.tn_ws, w.tn_ws_bytes, st));
         CK(gemm(dbig, F, W + bw.fc1_t, F, w.dh, D, Mx, D, F, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
-        CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)s.x_mid, D, nullptr, PF(params, bx.n2w), s.mean2, s.rstd2, compact ? w.Gc : w.G, D, gb_pr, D,
+        CK(dclip_layernorm_bwd(w.dh, D, 0, (const float*)rs.x_mid, D, nullptr, PF(params, bx.n2w), rs.mean2, rs.rstd2, compact ? w.Gc : w.G, D, gb_pr, D,
                                GR(bx.n2w), GR(bx.n2b), GR(bx.prb), Mx, D, st));
         // attention: x_mid = x_in + proj(attn(LN1(x_in)))
         if (r == 0 && GR(bx.prw)) CK(dclip_gemm_tn_acc(w.gb_pr, D, s0.ctx, D, GR(bx.prw), D, MRw, D, D, wsplits(MRw, D, D), w.tn_ws, w.tn_ws_bytes, st));
@@ -800,7 +794,8 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
             CK(dclip_rows_expand(dctx_c, dctx, w.pick, B, N, D * 2, st));
             CK(dclip_rows_expand(w.Gc, w.G, w.pick, B, N, D * 4, st));
         }
-        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, has_mg[ei] ? &mgrad[ei] : nullptr, st));
+        const MapGrad mg{gm.score[ei], gm.prob[ei], maps ? maps->scratch : nullptr, maps ? maps->scratch_bytes : 0};
+        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, mg.d_score || mg.d_prob ? &mg : nullptr, st));
         if (r == 0 && GR(bx.qkvw)) CK(dclip_gemm_tn_acc(w.dqkv, 3 * D, s0.h1, D, GR(bx.qkvw), D, MR, 3 * D, D, wsplits(MR, 3 * D, D), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && params[bx.qkvb] && GR(bx.qkvb)) CK(dclip_colsum_acc(w.dqkv, 3 * D, GR(bx.qkvb), MR, 3 * D, st));
         CK(gemm(dqkv, 3 * D, W + bw.qkv_t, 3 * D, w.dh, D, M, D, 3 * D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
@@ -814,41 +809,36 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
     }
 
     // ---- embedding ---------------------------------------------------------------------------------------------
-    const bool clip_image = !p.student && p.image;       // the exported embedding of a CLIP image tower is taken BEFORE ln_pre (_common.py:204-208)
-    if (d_emb && !clip_image) CK(dclip_axpy_f32(w.G, d_emb, w.Gb, M * D, nullptr, D, st));
+    const Plan::EmbP& em = p.emb;
+    const bool pre_ln = em.ln_w >= 0;                    // CLIP image tower; its exported embedding is taken BEFORE ln_pre (_common.py:204-208)
+    if (d_emb && !pre_ln) CK(dclip_axpy_f32(w.G, d_emb, w.Gb, M * D, nullptr, D, st));
     if (hipMemsetAsync(w.tok_sum, 0, (size_t)N * D * 4, hs) != hipSuccess) { dclip_set_error("dclip_encoder_backward: memset failed"); return DCLIP_ELAUNCH; }
-    if (clip_image) {        // grads: 0 conv1 w, 1 class_embedding, 2 positional_embedding, 3 ln_pre w, 4 ln_pre b
+    const float* Ge = w.G;                               // f32 gradient of the embedding's output; w.Gb is its bf16 copy
+    if (pre_ln) {
         // x = ln_pre(x0), no bypass: the gradient of x0 is LN'(G) alone, accumulated into a cleared buffer
         if (hipMemsetAsync(w.G0, 0, (size_t)M * D * 4, hs) != hipSuccess) { dclip_set_error("dclip_encoder_backward: memset failed"); return DCLIP_ELAUNCH; }
-        CK(dclip_layernorm_bwd(w.G, D, 1, (const float*)w.x0, D, nullptr, PF(params, 3), w.mean0, w.rstd0, w.G0, D, w.Gb, D, GR(3), GR(4), nullptr, M, D, st));
+        CK(dclip_layernorm_bwd(w.G, D, 1, (const float*)w.x0, D, nullptr, PF(params, em.ln_w), w.mean0, w.rstd0, w.G0, D, w.Gb, D, GR(em.ln_w), GR(em.ln_b),
+                               nullptr, M, D, st));
         if (d_emb) CK(dclip_axpy_f32(w.G0, d_emb, w.Gb, M * D, nullptr, D, st));
-        if (GR(0)) CK(dclip_gemm_tn_acc(w.Gb, D, ext_patches ? ext_patches : w.patches, p.K, GR(0), p.K, M, D, p.K, wsplits(M, D, p.K), w.tn_ws, w.tn_ws_bytes, st));
-        if (GR(1) || GR(2)) {
-            CK(dclip_batch_sum_acc(w.G0, w.tok_sum, B, N, D, st));
-            CK(dclip_token_table_bwd(w.tok_sum, GR(2), GR(1), nullptr, N, D, 1, st));
+        Ge = w.G0;
+    }
+    if (em.w >= 0) {         // GEMM embedding: weight, then the token table's parts (pos, cls, bias), then the compressed-text token table
+        const int64_t K = p.K;
+        const bf16_t* rows = ext_patches ? ext_patches : w.patches;
+        if (GR(em.w)) CK(dclip_gemm_tn_acc(w.Gb, D, rows, K, GR(em.w), K, M, D, K, wsplits(M, D, K), w.tn_ws, w.tn_ws_bytes, st));
+        if (GR(em.bias) || GR(em.cls) || GR(em.pos)) {
+            CK(dclip_batch_sum_acc(Ge, w.tok_sum, B, N, D, st));
+            CK(dclip_token_table_bwd(w.tok_sum, GR(em.pos), GR(em.cls), GR(em.bias), N, D, p.image ? 1 : 0, st));
         }
-    } else if (p.image) {    // grads: 0 conv w, 1 conv b, 2 cls, 3 pos
-        if (GR(0)) CK(dclip_gemm_tn_acc(w.Gb, D, ext_patches ? ext_patches : w.patches, p.K, GR(0), p.K, M, D, p.K, wsplits(M, D, p.K), w.tn_ws, w.tn_ws_bytes, st));
-        if (GR(1) || GR(2) || GR(3)) {
+        if (GR(em.table)) {
+            CK(gemm(w.Gb, D, W + p.w_embed_t, D, w.demb, K, M, K, D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
+            CK(dclip_embed_scatter_add((const int64_t*)input, w.demb, 1, GR(em.table), M, K, p.c.vocab, st));
+        }
+    } else {                 // plain text: token table scatter, positional sum
+        if (GR(em.table)) CK(dclip_embed_scatter_add((const int64_t*)input, w.G, 1, GR(em.table), M, D, p.c.vocab, st));
+        if (GR(em.pos)) {
             CK(dclip_batch_sum_acc(w.G, w.tok_sum, B, N, D, st));
-            CK(dclip_token_table_bwd(w.tok_sum, GR(3), GR(2), GR(1), N, D, 1, st));
-        }
-    } else if (p.compressed) {   // grads: 0 table, 1 linear w, 2 linear b, 3 pos
-        const int64_t rk = p.c.embed_rank;
-        if (GR(1)) CK(dclip_gemm_tn_acc(w.Gb, D, w.patches, rk, GR(1), rk, M, D, rk, wsplits(M, D, rk), w.tn_ws, w.tn_ws_bytes, st));
-        if (GR(2) || GR(3)) {
-            CK(dclip_batch_sum_acc(w.G, w.tok_sum, B, N, D, st));
-            CK(dclip_token_table_bwd(w.tok_sum, GR(3), nullptr, GR(2), N, D, 0, st));
-        }
-        if (GR(0)) {
-            CK(gemm(w.Gb, D, W + p.w_embed_t, D, w.demb, rk, M, rk, D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
-            CK(dclip_embed_scatter_add((const int64_t*)input, w.demb, 1, GR(0), M, rk, p.c.vocab, st));
-        }
-    } else {                     // grads: 0 table, 1 pos
-        if (GR(0)) CK(dclip_embed_scatter_add((const int64_t*)input, w.G, 1, GR(0), M, D, p.c.vocab, st));
-        if (GR(1)) {
-            CK(dclip_batch_sum_acc(w.G, w.tok_sum, B, N, D, st));
-            CK(dclip_token_table_bwd(w.tok_sum, GR(1), nullptr, nullptr, N, D, 0, st));
+            CK(dclip_token_table_bwd(w.tok_sum, GR(em.pos), nullptr, nullptr, N, D, 0, st));
         }
     }
     if (on_bucket) on_bucket(cb_user, p.L + 1);          // embedding parameters: the last bucket
@@ -864,7 +854,7 @@ extern "C" int dclip_encoder_grad_bucket(const dclip_encoder* e, int32_t bucket,
     const Plan& p = e->p;
     DCLIP_REQUIRE(bucket >= 0 && bucket <= p.L + 1, "dclip_encoder_grad_bucket: bucket %d out of range 0..%d", bucket, p.L + 1);
     const int per_block = p.student ? P_PER_SBLOCK + p.R * P_PER_SREPEAT : P_PER_TBLOCK;
-    if (bucket == 0) { *first_param = p.p_final; *end_param = p.n_params; }
+    if (bucket == 0) { *first_param = p.head.norm_w; *end_param = p.n_params; }
     else if (bucket == p.L + 1) { *first_param = 0; *end_param = p.p_blocks; }
     else { const int l = p.L - bucket; *first_param = p.p_blocks + l * per_block; *end_param = *first_param + per_block; }
     return DCLIP_OK;
