@@ -420,6 +420,173 @@ __global__ __launch_bounds__(256, NTM <= 7 ? 3 : 2) void attn_fused_fwd_kernel(A
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Streaming form of the fused forward for sequences the register-resident kernel cannot hold (N > 128: the frozen ViT-B/16,
+// ViT-L/14 teachers, 197 / 257 / 577 tokens), non-causal, HD = 64:
+//   ctx[(b,i), h*HD + d] = sum_j softmax_j(scale * q_i . k_j) v_j[d]
+// A workgroup of four waves owns 64 consecutive queries of one (b, h), 16 per wave, and walks the keys in chunks of SKC = 64.  The four
+// waves stage each chunk's K rows (row-major) and V rows (columns permuted as in wave_stage_perm4) once, through registers, into
+// one of two LDS buffers: the loads of chunk c + 1 are requested before chunk c is computed and written behind it, one barrier per chunk.
+// Per chunk a wave forms S^T = mfma(K frag, Q frag) (lane = query, as in attn_fused_fwd_kernel), moves its running maximum m,
+// rescales the O accumulators and its partial row sum by a = exp2((m_old - m) c2), writes the unnormalised e = exp2(fma(s, c2, -m c2))
+// as bf16 to its private P tile and adds O^T += V^T P^T.  1 / sum is applied to the 4 DT outputs at the end.  Keys behind N are zero
+// rows with score -inf (e = 0); whole 16-key tiles behind N are skipped.  Scores and probabilities never touch HBM.
+// Registers: Q 8 + S 16 + O 16 + staging 16 + fragments ~16 VGPRs, far below the 168 of three waves per SIMD.
+// LDS: 2 x (64 x 144 K + 64 x 160 V) + 4 x 16 x 144 P = 48 128 bytes: three workgroups (12 waves) per CU of 160 KB.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int SKC = 64;                        // keys per chunk
+constexpr int SQB = 64;                        // queries per workgroup
+
+struct AttnStream {
+    const bf16_t* qkv; int64_t ldq;      // [B*N, 3*H*HD] : q | k | v
+    bf16_t* ctx; int64_t ldc;
+    int B, H, N, nqb;                    // nqb = ceil(N / SQB) workgroups per (b, h)
+    float scale;
+};
+
+template <int HD>
+__global__ __launch_bounds__(256, 3) void attn_stream_fwd_kernel(AttnStream p) {
+    constexpr int KROWB = HD * 2 + 16, VROWB = HD * 2 + 32, PROWB = SKC * 2 + 16;
+    constexpr int KS = HD / 32, DT = HD / 16, NKT = SKC / 16;
+    constexpr int CPR = HD / 8;                         // 16-byte pieces per K / V row
+    constexpr int NLD = SKC * CPR / 256;                // pieces per thread and operand of one chunk
+    constexpr int KBUF = SKC * KROWB, VBUF = SKC * VROWB;
+    __shared__ __attribute__((aligned(16))) char smem[2 * (KBUF + VBUF) + 4 * 16 * PROWB];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int prob = (int)blockIdx.x / p.nqb, qb = (int)blockIdx.x - prob * p.nqb;
+    const int b = prob / p.H, h = prob - b * p.H;
+    const int D = p.H * HD;
+    const bf16_t* Q = p.qkv + (int64_t)b * p.N * p.ldq + h * HD;
+    const bf16_t* K = Q + D;
+    const bf16_t* V = Q + 2 * D;
+    char* pt = smem + 2 * (KBUF + VBUF) + wave * (16 * PROWB);
+    const int fr = lane & 15, g = lane >> 4, fk = g * 8;
+    const int q0 = qb * SQB + wave * 16;                // this wave's first query
+    const bool wave_live = q0 < p.N;                    // (a wave without queries still stages)
+    const int i = q0 + fr;                              // this lane's query
+    bf16x8 qf[KS];
+    {
+        const int ia = min(i, p.N - 1);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const bf16x8*)(Q + (int64_t)ia * p.ldq + ks * 32 + fk);
+    }
+    u32x4 rk[NLD], rv[NLD];
+    auto load_chunk = [&](int c0) {
+#pragma unroll
+        for (int k = 0; k < NLD; ++k) {
+            const int idx = k * 256 + tid, r = idx / CPR, c = idx % CPR;
+            rk[k] = rv[k] = u32x4{0u, 0u, 0u, 0u};
+            if (c0 + r < p.N) {
+                rk[k] = *(const u32x4*)(K + (int64_t)(c0 + r) * p.ldq + c * 8);
+                rv[k] = *(const u32x4*)(V + (int64_t)(c0 + r) * p.ldq + c * 8);
+            }
+        }
+    };
+    auto store_chunk = [&](int buf) {
+        char* kt = smem + buf * (KBUF + VBUF);
+        char* vt = kt + KBUF;
+#pragma unroll
+        for (int k = 0; k < NLD; ++k) {
+            const int idx = k * 256 + tid, r = idx / CPR, c = idx % CPR;
+            *(u32x4*)(kt + r * KROWB + c * 16) = rk[k];
+            const int g0 = 2 * c, g1 = 2 * c + 1;       // column groups of four, permuted as in wave_stage_perm4
+            *(u32x2*)(vt + r * VROWB + (4 * (g0 % DT) + g0 / DT) * 8) = u32x2{rv[k][0], rv[k][1]};
+            *(u32x2*)(vt + r * VROWB + (4 * (g1 % DT) + g1 / DT) * 8) = u32x2{rv[k][2], rv[k][3]};
+        }
+    };
+    const int nchunk = (p.N + SKC - 1) / SKC;
+    load_chunk(0);
+    store_chunk(0);
+    __syncthreads();
+    const float c2 = p.scale * 1.4426950408889634f;
+    float m = -INFINITY, lsum = 0.f;                    // running maximum of the raw scores; this lane's share of the row sum
+    f32x4 oc[DT];
+#pragma unroll
+    for (int d = 0; d < DT; ++d) oc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ch = 0; ch < nchunk; ++ch) {
+        if (ch + 1 < nchunk) load_chunk((ch + 1) * SKC);
+        if (wave_live) {
+            const char* kt = smem + (ch & 1) * (KBUF + VBUF);
+            const char* vt = kt + KBUF;
+            const int left = p.N - ch * SKC;                        // keys from this chunk's first to the end
+            const int nkt = left >= SKC ? NKT : (left + 15) >> 4;   // 16-key tiles with a key in them
+            f32x4 st[NKT];
+            float mc = m;
+#pragma unroll
+            for (int jt = 0; jt < NKT; ++jt)
+                if (jt < nkt) {
+                    st[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    bf16x8 kf[KS];
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        kf[ks] = *(const bf16x8*)(kt + (jt * 16 + fr) * KROWB + (ks * 32 + fk) * 2);
+                        st[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], qf[ks], st[jt], 0, 0, 0);
+                    }
+                    if (jt * 16 + 16 > left) {                      // (wave-uniform: the tile the sequence ends in)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) st[jt][r] = jt * 16 + g * 4 + r < left ? st[jt][r] : -INFINITY;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mc = fmaxf(mc, st[jt][r]);
+                    // the K fragments stay live past the VALU work on their tile: hipcc otherwise lets the accumulator share the registers of
+                    // the first fragment, and the mask's select then writes a queued MFMA's SrcA registers (attention_mix.hip, hw::keep_alive)
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) asm volatile("" :: "v"(kf[ks]));
+                }
+            mc = fmaxf(mc, __shfl_xor(mc, 16));
+            mc = fmaxf(mc, __shfl_xor(mc, 32));
+            // (every chunk has a key: mc is finite.  First chunk: m = -inf and a = 0 meet accumulators that are still 0)
+            const float nm = -mc * c2;
+            const float a = __builtin_amdgcn_exp2f(fmaf(m, c2, nm));
+            m = mc;
+            float cs = 0.f;
+#pragma unroll
+            for (int jt = 0; jt < NKT; ++jt) {
+                if (jt < nkt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float e = __builtin_amdgcn_exp2f(fmaf(st[jt][r], c2, nm));
+                        st[jt][r] = e;
+                        cs += e;
+                    }
+                    *(bf16x4*)(pt + fr * PROWB + (jt * 16 + g * 4) * 2) = bf16x4{f2bf(st[jt][0]), f2bf(st[jt][1]), f2bf(st[jt][2]), f2bf(st[jt][3])};
+                } else if (jt == nkt && (nkt & 1)) {                // upper half of the last 32-key step
+                    *(bf16x4*)(pt + fr * PROWB + (jt * 16 + g * 4) * 2) = bf16x4{f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
+                }
+            }
+            lsum = fmaf(lsum, a, cs);
+#pragma unroll
+            for (int d = 0; d < DT; ++d) oc[d] *= a;
+            // wave-private tile, in-order DS queue: only the compiler has to keep the order (attn_fused_fwd_kernel)
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int ks = 0; ks < NKT / 2; ++ks)
+                if (ks * 2 < nkt) {
+                    const bf16x8 pf = *(const bf16x8*)(pt + fr * PROWB + (ks * 32 + fk) * 2);
+#pragma unroll
+                    for (int d = 0; d < DT; ++d)
+                        oc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<VROWB>(vt, ks * 32, d * 16, lane), pf, oc[d], 0, 0, 0);
+                }
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (ch + 1 < nchunk) store_chunk((ch + 1) & 1);
+        __syncthreads();
+    }
+    lsum += __shfl_xor(lsum, 16);
+    lsum += __shfl_xor(lsum, 32);
+    const float inv = 1.f / lsum;
+    if (wave_live && i < p.N) {
+        // (columns permuted when V was staged: this lane holds the 4 DT consecutive columns from (4 DT) g of query i)
+        bf16_t* o = p.ctx + ((int64_t)b * p.N + i) * p.ldc + h * HD + g * (4 * DT);
+#pragma unroll
+        for (int d = 0; d < DT; d += 2)
+            *(bf16x8*)(o + d * 4) = bf16x8{f2bf(oc[d][0] * inv), f2bf(oc[d][1] * inv), f2bf(oc[d][2] * inv), f2bf(oc[d][3] * inv),
+                                            f2bf(oc[d + 1][0] * inv), f2bf(oc[d + 1][1] * inv), f2bf(oc[d + 1][2] * inv), f2bf(oc[d + 1][3] * inv)};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // TN: C[(b,j), h*HD + d] = alpha * sum_i A[b,h,i,j] * B[(b,i), h*HD + d]   (contraction over query rows)
 // ---------------------------------------------------------------------------------------------------------
 
@@ -1174,6 +1341,22 @@ extern "C" int dclip_attn_fused_fwd(const void* qkv, int64_t ldq, void* ctx, int
     else { if (NT == 4) FUSED_LAUNCH(64, 4); else if (NT == 5) FUSED_LAUNCH(64, 5); else if (NT == 7) FUSED_LAUNCH(64, 7); else FUSED_LAUNCH(64, 8); }
 #undef FUSED_LAUNCH
     return dclip_check_launch("dclip_attn_fused_fwd");
+}
+
+// Long-sequence companion of dclip_attn_fused_fwd (attn_stream_fwd_kernel): any N >= 1, non-causal, hd = 64.
+extern "C" int dclip_attn_stream_fwd(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
+                                     float scale, void* stream) {
+    DCLIP_REQUIRE(qkv && ctx, "dclip_attn_stream_fwd: null operand");
+    DCLIP_REQUIRE(B > 0 && H > 0 && N > 0, "dclip_attn_stream_fwd: need B, H, N > 0 (B=%ld H=%ld N=%ld)", (long)B, (long)H, (long)N);
+    DCLIP_REQUIRE(hd == 64, "dclip_attn_stream_fwd: head dim must be 64 (got %ld)", (long)hd);
+    DCLIP_REQUIRE(ldq % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)ctx % 16) == 0, "dclip_attn_stream_fwd: misaligned buffers");
+    DCLIP_REQUIRE(ldq >= 3 * H * hd && ldc >= H * hd, "dclip_attn_stream_fwd: row strides shorter than the rows (ldq >= 3 H hd, ldc >= H hd)");
+    const int64_t nqb = (N + SQB - 1) / SQB;
+    DCLIP_REQUIRE(N < (1 << 24) && B * H * nqb < (1LL << 31) && B * N < (1LL << 31), "dclip_attn_stream_fwd: problem too large for one launch");
+    AttnStream p{(const bf16_t*)qkv, ldq, (bf16_t*)ctx, ldc, (int)B, (int)H, (int)N, (int)nqb, scale};
+    TraceScope tr(DCLIP_TRACE_ATTN, 4.0 * B * H * N * N * hd, 8.0 * B * H * N * hd, stream, (int)(B * H), (int)N, (int)hd, 7);
+    hipLaunchKernelGGL((attn_stream_fwd_kernel<64>), dim3((unsigned)(B * H * nqb)), dim3(256), 0, (hipStream_t)stream, p);
+    return dclip_check_launch("dclip_attn_stream_fwd");
 }
 
 #define SM_DISPATCH_H(Hv, NSv, ...)                                               \

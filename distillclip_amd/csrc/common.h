@@ -34,6 +34,10 @@ void dclip_set_error(const char* fmt, ...);
 extern "C" int dclip_rows_pick(const void* src, void* dst, const int32_t* idx, int64_t B, int64_t row_bytes, void* stream);
 extern "C" int dclip_rows_expand(const void* src, void* dst, const int32_t* idx, int64_t B, int64_t N, int64_t row_bytes, void* stream);
 
+// dst bf16 [R, ldd] = src f32 [R, C], columns [C, ldd) zero (elementwise.hip; the frozen patch-14 towers' conv1 weight, whose contraction
+// width is padded to a multiple of 64; used by encoder.cpp, not C ABI)
+extern "C" int dclip_cast_bf16_pad(const float* src, void* dst, int64_t R, int64_t C, int64_t ldd, void* stream);
+
 // launch trace (capi.cpp): open() returns false unless dclip_trace_begin() enabled tracing
 bool dclip_trace_open(int kind, double flops, double bytes, void* stream, int* slot, int d0 = 0, int d1 = 0, int d2 = 0, int d3 = 0);
 void dclip_trace_close(int slot, void* stream);

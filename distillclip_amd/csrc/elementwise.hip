@@ -122,6 +122,38 @@ __global__ __launch_bounds__(256) void im2row_kernel(const float* __restrict__ i
     }
 }
 
+// im2row_kernel with rows of stride ldk >= K = C p^2 (columns [K, ldk) zero) and an even patch: a patch row of 14 floats starts on an
+// 8-byte boundary at best, so two scalar loads and one 4-byte store per thread (0.1 ms of a ViT-L/14 step)
+__global__ __launch_bounds__(256) void im2row_ld_kernel(const float* __restrict__ img, bf16_t* __restrict__ out, int B, int C,
+                                                        int res, int p, int G, int cls, int ldk) {
+    const int K = C * p * p;
+    const int kq = ldk / 2;                     // column pairs per row
+    const int rows = B * (G * G + cls);
+    const int64_t total = (int64_t)rows * kq;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int row = (int)(i / kq), q = (int)(i % kq);
+        const int b = row / (G * G + cls), t = row % (G * G + cls);
+        const int k = q * 2;
+        bf16x2 o = {f2bf(0.f), f2bf(0.f)};
+        if (t >= cls && k < K) {
+            const int pi = t - cls, py = pi / G, px = pi % G;
+            const int c = k / (p * p), ky = (k / p) % p, kx = k % p;          // (p even: k and k + 1 lie in one patch row)
+            const float* src = img + (((int64_t)b * C + c) * res + (py * p + ky)) * res + px * p + kx;
+            o = bf16x2{f2bf(src[0]), f2bf(src[1])};
+        }
+        *(bf16x2*)(out + (int64_t)row * ldk + k) = o;
+    }
+}
+
+// dst bf16 [R, ldd] = src f32 [R, C] with columns [C, ldd) zero
+__global__ __launch_bounds__(256) void cast_pad_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int R, int C, int ldd) {
+    const int64_t total = (int64_t)R * ldd;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int r = (int)(i / ldd), c = (int)(i % ldd);
+        dst[i] = f2bf(c < C ? src[(int64_t)r * C + c] : 0.f);
+    }
+}
+
 // out[0] = pos[0] + cls ; out[n>=1] = pos[n] + bias      (cls / bias may be null)
 __global__ void token_table_kernel(const float* __restrict__ pos, const float* __restrict__ cls,
                                    const float* __restrict__ bias, float* __restrict__ out, int ntok, int D) {
@@ -491,6 +523,27 @@ extern "C" int dclip_im2row(const float* img, void* rows, int64_t B, int64_t C, 
     hipLaunchKernelGGL(im2row_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, img, (bf16_t*)rows, (int)B,
                        (int)C, (int)res, (int)patch, G, cls_rows);
     return dclip_check_launch("dclip_im2row");
+}
+
+extern "C" int dclip_im2row_ld(const float* img, void* rows, int64_t ldk, int64_t B, int64_t C, int64_t res, int64_t patch, int cls_rows,
+                               void* stream) {
+    DCLIP_REQUIRE(img && rows && B > 0 && C > 0 && res >= patch && patch > 0, "dclip_im2row_ld: bad argument");
+    DCLIP_REQUIRE(patch % 2 == 0, "dclip_im2row_ld: patch must be even (got %ld)", (long)patch);
+    DCLIP_REQUIRE(ldk >= C * patch * patch && ldk % 2 == 0 && ((uintptr_t)rows % 4) == 0,
+                  "dclip_im2row_ld: ldk must be even and >= C * patch^2 = %ld (got %ld), rows 4-byte aligned", (long)(C * patch * patch), (long)ldk);
+    DCLIP_REQUIRE(cls_rows == 0 || cls_rows == 1, "dclip_im2row_ld: cls_rows must be 0 or 1");
+    const int G = (int)(res / patch);
+    DCLIP_REQUIRE(B * (G * G + cls_rows) < (1LL << 31) && ldk < (1LL << 24), "dclip_im2row_ld: problem too large for one launch");
+    const int64_t work = B * (G * G + cls_rows) * (ldk / 2);
+    hipLaunchKernelGGL(im2row_ld_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, img, (bf16_t*)rows, (int)B,
+                       (int)C, (int)res, (int)patch, G, cls_rows, (int)ldk);
+    return dclip_check_launch("dclip_im2row_ld");
+}
+
+extern "C" int dclip_cast_bf16_pad(const float* src, void* dst, int64_t R, int64_t C, int64_t ldd, void* stream) {
+    DCLIP_REQUIRE(src && dst && R > 0 && C > 0 && ldd >= C && R < (1LL << 31) && ldd < (1LL << 31), "dclip_cast_bf16_pad: bad argument");
+    hipLaunchKernelGGL(cast_pad_kernel, dim3(grid_for(R * ldd)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (int)R, (int)C, (int)ldd);
+    return dclip_check_launch("dclip_cast_bf16_pad");
 }
 
 extern "C" int dclip_token_table(const float* pos, const float* cls, const float* bias, float* out, int64_t ntok, int64_t D,

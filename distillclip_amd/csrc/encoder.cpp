@@ -48,6 +48,8 @@ struct Plan {
     dclip_encoder_cfg c;
     int D, H, hd, N, Np, F, E, L, R;
     int K;                                     // contraction of the embedding GEMM: in_chans * patch^2 (image), embed_rank (compressed text), else 0
+    int Kp;                                    // its width in memory (rows of w.patches and of the cached weight): K, or round_up(K, 64) with zero
+                                               // pad columns in both operands for a frozen image tower (patch 14: 588 -> 640)
     bool student, image, compressed;           // student = the weight-shared MiniViT architecture (kind 1)
     bool mixing;                               // conv_l / conv_w cross-head mixing (head_mix; students only)
     bool train;                                // the tower has a backward (kind 1, 2): transposed weights cached, f32 residual stream
@@ -74,22 +76,36 @@ bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
     p.hd = p.D / p.H;
     if (p.hd != 32 && p.hd != 64) { dclip_set_error("encoder: head dim %d unsupported (32 or 64)", p.hd); return false; }
     if (p.D % 64 || p.F % 64 || p.E % 64 || p.D > 1024) { dclip_set_error("encoder: width/mlp/out dims must be multiples of 64, width <= 1024"); return false; }
-    if (p.N <= 0 || p.N > 128) { dclip_set_error("encoder: tokens must be in 1..128 (got %d)", p.N); return false; }
+    // sequences above 128 tokens run dclip_attn_stream_fwd, which exists for the frozen, non-causal, hd = 64 case only
+    const bool long_ok = c.kind == 0 && p.image && !c.causal && p.hd == 64;
+    if (p.N <= 0 || p.N > (long_ok ? 640 : 128)) {
+        if (long_ok) dclip_set_error("encoder: tokens must be in 1..640 for a frozen image tower (got %d)", p.N);
+        else if (p.N > 128 && c.kind != 0) dclip_set_error("encoder: tokens must be in 1..128 for a trainable tower (kind %d; got %d): only frozen image towers run longer sequences", c.kind, p.N);
+        else if (p.N > 128 && !p.image) dclip_set_error("encoder: tokens must be in 1..128 for a text tower (got %d): only frozen image towers run longer sequences", p.N);
+        else if (p.N > 128) dclip_set_error("encoder: tokens must be in 1..128 for a causal or head-dim-%d tower (got %d): longer sequences need a non-causal tower with head dim 64", p.hd, p.N);
+        else dclip_set_error("encoder: tokens must be in 1..128 (got %d)", p.N);
+        return false;
+    }
     if (p.L <= 0 || p.R <= 0 || (!p.student && p.R != 1)) { dclip_set_error("encoder: bad layers/repeats"); return false; }
     p.Np = (p.N + 7) & ~7;
     p.compressed = !p.image && c.embed_rank > 0;
-    p.K = 0;
+    p.K = p.Kp = 0;
     if (p.image) {
         if (c.patch <= 0 || c.resolution < c.patch || c.in_chans <= 0) { dclip_set_error("encoder: bad patch geometry"); return false; }
         const int g = c.resolution / c.patch;
         if (g * g + 1 != p.N) { dclip_set_error("encoder: tokens %d != (res/patch)^2 + 1 = %d", p.N, g * g + 1); return false; }
         p.K = c.in_chans * c.patch * c.patch;
-        if (p.K % 64) { dclip_set_error("encoder: in_chans*patch^2 = %d must be a multiple of 64", p.K); return false; }
+        p.Kp = p.K;
+        if (p.K % 64) {
+            if (p.train) { dclip_set_error("encoder: in_chans*patch^2 = %d must be a multiple of 64 in a trainable tower", p.K); return false; }
+            if (c.patch % 2) { dclip_set_error("encoder: patch %d must be even", c.patch); return false; }
+            p.Kp = (p.K + 63) & ~63;
+        }
     } else {
         if (c.vocab <= 0) { dclip_set_error("encoder: vocab required for text"); return false; }
         if (p.compressed && c.embed_rank % 64) { dclip_set_error("encoder: embed_rank must be a multiple of 64"); return false; }
         if (p.compressed && !p.student) { dclip_set_error("encoder: a compressed token embedding exists for the weight-shared student only (kind 1)"); return false; }
-        if (p.compressed) p.K = c.embed_rank;
+        if (p.compressed) p.K = p.Kp = c.embed_rank;
     }
     if (p.mixing && p.H != 2 && p.H != 4 && p.H != 8 && p.H != 12 && p.H != 24) {
         dclip_set_error("encoder: head count %d unsupported by the head-mixing kernels", p.H); return false;
@@ -124,7 +140,7 @@ bool make_plan(const dclip_encoder_cfg& c, Plan& p) {
         else b.qkv_t = b.proj_t = b.fc1_t = b.fc2_t = -1;
     }
     p.w_embed = p.w_embed_t = -1;
-    if (em.w >= 0) p.w_embed = wtake(off, D * p.K);
+    if (em.w >= 0) p.w_embed = wtake(off, D * p.Kp);
     if (p.compressed) p.w_embed_t = wtake(off, D * p.K);          // dgrad towards the token table
     p.w_head = wtake(off, E * D);                                 // [E, D] (CLIP towers: proj^T)
     p.w_head_t = p.train ? wtake(off, E * D) : -1;                // [D, E]
@@ -279,7 +295,7 @@ void layout(const Plan& p, int64_t B, bool training, void* base, Work& w, int64_
         }
         w.Gc = save ? b.take<float>(B * D) : nullptr;
     }
-    w.patches = p.emb.w >= 0 ? b.take<bf16_t>(M * p.K) : nullptr;
+    w.patches = p.emb.w >= 0 ? b.take<bf16_t>(M * p.Kp) : nullptr;
     w.tok_table = b.take<float>((int64_t)N * D);
     w.pick = b.take<int32_t>(B);
     w.meanf = b.take<float>(B); w.rstdf = b.take<float>(B);
@@ -358,7 +374,10 @@ inline int export_stream(bool h16, const void* src, float* dst, int64_t n, void*
 int attn_forward(AttnPath path, const Plan& p, const ExecSave& s, const float* wl, const float* ww, int64_t B, int64_t N, void* st) {
     const int64_t D = p.D, H = p.H, hd = p.hd, Np = (N + 7) & ~(int64_t)7;
     const float scale = 1.f / sqrtf((float)hd);
-    if (path == AttnPath::Fused) return dclip_attn_fused_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, p.c.causal, st);
+    if (path == AttnPath::Fused) {
+        if (N <= 128) return dclip_attn_fused_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, p.c.causal, st);
+        return dclip_attn_stream_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, st);      // (make_plan: frozen, non-causal, hd = 64)
+    }
     if (path == AttnPath::Mix) {
         CK(dclip_attn_mix_fwd(s.qkv, 3 * D, wl, ww, s.Rm, s.stats, B, H, N, Np, hd, scale, st));
         return dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 1, st);
@@ -535,10 +554,15 @@ extern "C" int dclip_encoder_prepare(const dclip_encoder* e, const void* const* 
         job(PF(params, bx.f1w), at(b.fc1), at(b.fc1_t), F, D);
         job(PF(params, bx.f2w), at(b.fc2), at(b.fc2_t), D, F);
     }
-    if (p.emb.w >= 0) job(PF(params, p.emb.w), at(p.w_embed), at(p.w_embed_t), D, p.K);       // conv weight [D, C*p*p] / compressed-text linear [D, rank]
+    const bool pad_embed = p.Kp != p.K;                                                       // (frozen patch-14 towers: cast apart, below)
+    if (p.emb.w >= 0 && !pad_embed) job(PF(params, p.emb.w), at(p.w_embed), at(p.w_embed_t), D, p.K);       // conv weight [D, C*p*p] / compressed-text linear [D, rank]
     if (p.student) job(PF(params, p.head.head_w), at(p.w_head), at(p.w_head_t), E, D);
     else job(PF(params, p.head.head_w), at(p.w_head_t), at(p.w_head), D, E);                  // proj [D,E] -> [E,D] (+ as it is: the dgrad operand of a trainable tower)
     for (size_t i = 0; i < src.size(); ++i) DCLIP_REQUIRE(src[i], "dclip_encoder_prepare: parameter %zu missing", i);
+    if (pad_embed) {
+        DCLIP_REQUIRE(PF(params, p.emb.w), "dclip_encoder_prepare: the patch-embedding weight is missing");
+        CK(dclip_cast_bf16_pad(PF(params, p.emb.w), at(p.w_embed), D, p.K, p.Kp, st));       // [D, Kp], columns [K, Kp) zero
+    }
     return dclip_cast_transpose_bf16_multi(src.data(), wb.data(), wt.data(), rr.data(), cc.data(), (int64_t)src.size(), st);
 }
 
@@ -571,6 +595,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     const bf16_t* ext_patches = (const bf16_t*)patches;
     DCLIP_REQUIRE(!ext_patches || (p.image && ((uintptr_t)ext_patches % 16) == 0), "dclip_encoder_forward: patches: image towers only, 16-byte aligned rows");
     DCLIP_REQUIRE(!ext_patches || tokens_eff == 0, "dclip_encoder_forward: patches cannot be combined with tokens_eff");
+    DCLIP_REQUIRE(!ext_patches || p.Kp == p.K, "dclip_encoder_forward: this tower pads its patch rows (%d -> %d columns) and cuts them itself: pass the images", p.K, p.Kp);
     DCLIP_REQUIRE(!training || p.train, "dclip_encoder_forward: the frozen teacher tower (kind 0) is inference-only");
     // tokens_eff: causal text teacher only.  Positions after the longest caption's EOT cannot influence any EOT row (causal
     // attention; LN / MLP are per token), so the tower may run on the first tokens_eff positions with identical output.
@@ -579,6 +604,8 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     // head-mean attention maps per block execution
     DCLIP_REQUIRE(!(maps && maps->n > 0 && maps->exec) || tokens_eff == 0,
                   "dclip_encoder_forward: attention maps cannot be exported from a caption prefix (tokens_eff)");
+    DCLIP_REQUIRE(!(maps && maps->n > 0) || p.N <= 128,
+                  "dclip_encoder_forward: attention maps cannot be exported from a tower of %d tokens (dclip_attn_maps_fwd / _bwd take N <= 128)", p.N);
     ExecMaps<float> xm;
     CK(exec_maps<float>(p, maps, maps ? maps->score : nullptr, maps ? maps->prob : nullptr, nullptr, "dclip_encoder_forward", xm));
     Work w;
@@ -598,9 +625,10 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     if (em.w >= 0) {
         const bf16_t* rows = ext_patches ? ext_patches : w.patches;
         if (!p.image) CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, em.table), nullptr, w.patches, 0, M, N, p.K, st));
+        else if (!ext_patches && p.Kp != p.K) CK(dclip_im2row_ld((const float*)input, w.patches, p.Kp, B, p.c.in_chans, p.c.resolution, p.c.patch, 1, st));
         else if (!ext_patches) CK(dclip_im2row((const float*)input, w.patches, B, p.c.in_chans, p.c.resolution, p.c.patch, 1, st));
         CK(dclip_token_table(PF(params, em.pos), PF(params, em.cls), PF(params, em.bias), w.tok_table, N, D, st));
-        CK(gemm(rows, p.K, W + p.w_embed, p.K, pre_ln ? w.x0 : w.X[0], D, M, D, p.K, nullptr, 0, nullptr, nullptr, nullptr, 0, sdt, N, w.tok_table, st));
+        CK(gemm(rows, p.Kp, W + p.w_embed, p.Kp, pre_ln ? w.x0 : w.X[0], D, M, D, p.Kp, nullptr, 0, nullptr, nullptr, nullptr, 0, sdt, N, w.tok_table, st));
         if (pre_ln) CK(ln_stream(w.h16, w.x0, D, nullptr, PF(params, em.ln_w), PF(params, em.ln_b), w.X[0], D, sdt, w.mean0, w.rstd0, M, D, st));
     } else {
         CK(dclip_embed_gather((const int64_t*)input, p.N, PF(params, em.table), PF(params, em.pos), w.X[0], sdt, M, N, D, st));

@@ -60,8 +60,8 @@ class shared_image_patches:
     dclip_im2row conversion (made here, on the current stream) instead of converting the batch once each.  The reference feeds
     teacher and student the same `image` (dual_distill_model.py:107-109) and both start with the same stride-p unfolding
     (_common.py:196-198, weight_share_model.py:344).  A tower keeps the rows alive until its backward has used them (patch-embedding
-    wgrad).  No-op unless at least two of `towers` are image towers of equal patch size and channel count; DCLIP_SHARE_PATCHES=0
-    switches it off."""
+    wgrad).  No-op unless at least two of `towers` are image towers, ALL image towers have one patch size and channel count, and
+    their rows are unpadded (C p^2 a multiple of 64); DCLIP_SHARE_PATCHES=0 switches it off."""
 
     def __init__(self, image, towers):
         self.image, self.entry = image, None
@@ -69,13 +69,14 @@ class shared_image_patches:
         ok = (len(tw) >= 2 and isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.float32 and image.dim() == 4
               and image.is_contiguous() and image.shape[2] == image.shape[3] and os.environ.get('DCLIP_SHARE_PATCHES', '1') != '0'
               and len({(int(t.cfg.patch), int(t.cfg.in_chans)) for t in tw}) == 1 and image.shape[1] == tw[0].cfg.in_chans
-              and image.shape[-1] % 4 == 0 and tw[0].cfg.patch % 4 == 0)
+              and image.shape[-1] % 4 == 0 and tw[0].cfg.patch % 4 == 0
+              and (tw[0].cfg.in_chans * tw[0].cfg.patch ** 2) % 64 == 0)      # (other widths: a frozen tower pads its rows and cuts them itself)
         if ok:
             patch, chans, res, B = int(tw[0].cfg.patch), int(tw[0].cfg.in_chans), int(image.shape[-1]), int(image.shape[0])
             grid = res // patch
             rows = torch.empty((B * (grid * grid + 1), chans * patch * patch), dtype=torch.bfloat16, device=image.device)
             lib().dclip_im2row(image.data_ptr(), rows.data_ptr(), B, chans, res, patch, 1, torch.cuda.current_stream().cuda_stream)
-            self.entry = dict(key=(image.data_ptr(), tuple(image.shape), image._version), patch=patch, chans=chans, rows=rows,
+            self.entry = dict(key=(image.data_ptr(), tuple(image.shape), image._version), patch=patch, chans=chans, res=res, rows=rows,
                               stream=torch.cuda.current_stream())
 
     def __enter__(self):
@@ -96,6 +97,10 @@ def _shared_rows_for(x, cfg):
     if int(cfg.patch) != e['patch'] or int(cfg.in_chans) != e['chans']:
         return None
     rows = e['rows']
+    # the same resolution (the rows hold this tower's token count per image) and unpadded rows of C p^2 values: a ViT-B/16 teacher next to
+    # a patch-32 student, or a tower that pads its contraction (patch 14), cuts its own
+    if int(x.shape[-1]) != e['res'] or rows.shape[0] != x.shape[0] * int(cfg.tokens) or rows.shape[1] % 64:
+        return None
     cur = torch.cuda.current_stream()
     if cur != e['stream']:
         rows.record_stream(cur)                # cut on the share's stream (the tower streams wait for it), read on this one

@@ -19,12 +19,15 @@ _ARCH = {   # name -> (vision width, layers, patch, resolution, text width, text
     'ViT-B/32': (768, 12, 32, 224, 512, 12, 512),
     'ViT-B/16': (768, 12, 16, 224, 512, 12, 512),
     'ViT-L/14': (1024, 24, 14, 224, 768, 12, 768),
+    'ViT-L/14@336px': (1024, 24, 14, 336, 768, 12, 768),
 }
 
 
 def available_models():
-    """the archive names the reference knows (utils.py:18-28, :64-65).  Runnable on the HIP towers: ViT teachers of at most 128 tokens whose patch
-    has a multiple of 64 values (ViT-B/32, the teacher of every shipped config); ResNet teachers are out of scope."""
+    """the archive names the reference knows (utils.py:18-28, :64-65).  Runnable on the HIP towers as frozen teachers: every ViT of the list --
+    ViT-B/32 (50 tokens; the teacher of every shipped config), ViT-B/16 (197), ViT-L/14 (257) and ViT-L/14@336px (577): an image teacher
+    may have up to 640 tokens and any even patch (include/dclip.h: dclip_encoder_cfg).  Towers that train keep the limits of 128 tokens
+    and a patch with a multiple of 64 values; ResNet teachers are out of scope."""
     return ['RN50', 'RN101', 'RN50x4', 'RN50x16', 'RN50x64', 'ViT-B/32', 'ViT-B/16', 'ViT-L/14', 'ViT-L/14@336px']
 
 

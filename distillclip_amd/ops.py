@@ -208,6 +208,30 @@ def attn_fused_fwd(qkv, B, N, H, hd, causal=False):
     return ctx
 
 
+def attn_stream_fwd(qkv, B, N, H, hd):
+    """attn_fused_fwd for sequences of any length (the frozen ViT-B/16 / ViT-L/14 teachers), non-causal, hd = 64: keys streamed in chunks
+    with a running maximum and sum (include/dclip.h: dclip_attn_stream_fwd); qkv: [B*N, 3*H*hd] bf16."""
+    _chk(qkv)
+    D = H * hd
+    ctx = torch.empty((B * N, D), dtype=torch.bfloat16, device=qkv.device)
+    lib().dclip_attn_stream_fwd(_p(qkv), qkv.stride(0), _p(ctx), D, B, H, N, hd, hd ** -0.5, _stream())
+    return ctx
+
+
+def im2row_ld(image, patch, ldk=None, cls_rows=1):
+    """image f32 [B, C, R, R] -> bf16 patch rows [B * ((R // patch)^2 + cls_rows), ldk], ldk >= C * patch^2 (default: rounded up to 64),
+    pad columns zero, any even patch (include/dclip.h: dclip_im2row_ld)"""
+    _chk(image)
+    assert image.dtype == torch.float32 and image.dim() == 4 and image.is_contiguous() and image.shape[2] == image.shape[3]
+    B, C, R, _ = image.shape
+    K = C * patch * patch
+    ldk = (K + 63) // 64 * 64 if ldk is None else int(ldk)
+    g = R // patch
+    rows = torch.empty((B * (g * g + cls_rows), ldk), dtype=torch.bfloat16, device=image.device)
+    lib().dclip_im2row_ld(_p(image), _p(rows), ldk, B, C, R, patch, cls_rows, _stream())
+    return rows
+
+
 def embed_scatter_add(ids, dx, dtable):
     _chk(ids, dx, dtable)
     rows, D = dx.shape

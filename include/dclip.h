@@ -123,7 +123,7 @@ int dclip_layernorm_bwd(const void* dy, int64_t lddy, int dy_f32, const float* x
  * Attention building blocks.  q/k/v/ctx are token-major bf16 (row = b*N + n, column = head*hd + d, row stride ld*);
  * score-like tensors are [B,H,N,Np], Np = round_up(N, 8) in the towers (the product entries take any multiple of 8 with
  * N <= Np <= 128 and refuse others), pad columns [N, Np) zero: nt writes them as +0, nn / tn require them of A.
- * hd in {32, 64}, N <= 128.
+ * hd in {32, 64}, N <= 128 (dclip_attn_stream_fwd alone takes longer sequences).
  *   reference teacher: _common.py:73-89 ; student: weight_share_model.py:101-125 (scale, QK^T, conv_l, softmax,
  *   conv_w, PV) ; causal mask: text_encoder.py:54-60.
  * nt : C[b,h,i,j] = alpha * sum_d A[(b,i),h*hd+d] * Bm[(b,j),h*hd+d]          (S = QK^T ; dR = dO V^T)
@@ -146,6 +146,13 @@ int dclip_attn_tn(const void* A, const void* Bm, int64_t ldb, void* C, int64_t l
  *              qkv is the fused [B*N, 3*H*hd] projection ; scores / probabilities never reach HBM. */
 int dclip_attn_fused_fwd(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
                          float scale, int causal, void* stream);
+/* stream_fwd : the same product for sequences dclip_attn_fused_fwd does not take (the frozen ViT-B/16 / ViT-L/14 teachers: 197, 257, 577
+ *              tokens): any N >= 1, non-causal, hd = 64 only.  64 queries per workgroup, keys streamed through LDS in chunks of 64 with a
+ *              running maximum and sum per query; scores / probabilities never reach HBM.  ldq >= 3*H*hd and
+ *              ldc >= H*hd in elements, multiples of 8; qkv and ctx 16-byte aligned.  Refused (DCLIP_EINVAL, nothing launched): a null
+ *              pointer, N <= 0, hd != 64, a misaligned pointer or stride.  Added without a version bump: no existing signature changed. */
+int dclip_attn_stream_fwd(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
+                          float scale, void* stream);
 int dclip_attn_softmax_fwd(const float* S, const float* Wl, const float* Ww, void* P, void* R, int64_t B, int64_t H,
                            int64_t N, int64_t Np, int causal, void* stream);
 int dclip_attn_softmax_bwd(const void* dR, const void* P, const void* S, int scores_bf16, const float* Wl, const float* Ww,
@@ -205,6 +212,8 @@ int dclip_attn_maps_bwd(const void* qkv, int64_t ld, const float* Wl, const floa
  * cast_transpose_bf16_multi : per job, W f32 [R,C] -> Wb bf16 [R,C] (nullable) and Wt bf16 [C,R] (nullable; the dgrad operand).
  * im2row               : image f32 [B,C,res,res] -> bf16 rows [B*(G*G+cls_rows), C*p*p], G = res / p; the class-token row
  *                        is zero.  Conv2d(k=p,s=p) of _common.py:176,196 / timm PatchEmbed (weight_share_model.py:250).
+ * im2row_ld            : im2row with rows of stride ldk >= C*p*p elements (ldk even), columns [C*p*p, ldk) zero, and any EVEN patch:
+ *                        patch 14 gives C*p*p = 588, which the GEMM contraction (K % 64 == 0) takes padded to 640.
  * token_table          : out[0] = pos[0] + cls ; out[n>=1] = pos[n] + bias  (cls NULL: out[n] = pos[n] + bias)
  *                        (_common.py:199-202 ; weight_share_model.py:346-349, :489) ; token_table_bwd is its adjoint given
  *                        tok_sum[n] = sum_b G[b,n,:] from batch_sum_acc.
@@ -224,6 +233,8 @@ int dclip_axpy_f32(float* dst, const float* src, void* dst_bf16, int64_t n, floa
 int dclip_cast_transpose_bf16_multi(const float* const* W, void* const* Wb, void* const* Wt, const int64_t* R, const int64_t* C,
                                     int64_t n, void* stream);
 int dclip_im2row(const float* img, void* rows, int64_t B, int64_t C, int64_t res, int64_t patch, int cls_rows, void* stream);
+int dclip_im2row_ld(const float* img, void* rows, int64_t ldk, int64_t B, int64_t C, int64_t res, int64_t patch, int cls_rows,
+                    void* stream);
 int dclip_token_table(const float* pos, const float* cls, const float* bias, float* out, int64_t ntok, int64_t D, void* stream);
 int dclip_token_table_bwd(const float* tok_sum, float* dpos, float* dcls, float* dbias, int64_t ntok, int64_t D, int has_cls,
                           void* stream);
@@ -365,7 +376,8 @@ typedef struct dclip_encoder_cfg {
     int32_t kind;        /* 0 teacher (CLIP residual blocks, QuickGELU; frozen), 1 student (weight-shared MiniViT blocks, erf GELU),
                           * 2 CLIP tower that trains (architecture and parameter order of kind 0, workspace / backward of kind 1) */
     int32_t modality;    /* 0 image, 1 text */
-    int32_t tokens;      /* N: (resolution / patch)^2 + 1 for images, context_length for text */
+    int32_t tokens;      /* N: (resolution / patch)^2 + 1 for images, context_length for text.  1..128; a frozen (kind 0), non-causal
+                          * image tower with D / H = 64 may have up to 640 (ViT-B/16: 197, ViT-L/14: 257, at 336 px: 577) */
     int32_t width;       /* D */
     int32_t heads;       /* H (D / H in {32, 64}) */
     int32_t layers;      /* distinct blocks: teacher = transformer layers, student = depth / repeated_times */
@@ -373,7 +385,9 @@ typedef struct dclip_encoder_cfg {
     int32_t mlp_dim;     /* int(D * mlp_ratio) */
     int32_t out_dim;     /* E */
     int32_t patch, resolution, in_chans;  /* image only; resolution = height = width of the INPUT images; the patch conv floors
-                                           * (grid = resolution / patch: 336 px at patch 32 reads the top-left 320 x 320) */
+                                           * (grid = resolution / patch: 336 px at patch 32 reads the top-left 320 x 320).
+                                           * in_chans * patch^2 must be a multiple of 64, except in a frozen (kind 0) tower, which takes
+                                           * any even patch and pads the contraction to the next multiple of 64 (patch 14: 588 -> 640) */
     int32_t vocab, embed_rank;            /* text only; embed_rank = embedding_compression_dim or 0 */
     int32_t head_mix;    /* use_transform: conv_l / conv_w cross-head mixing */
     int32_t causal;      /* CLIP text towers: 1 */
@@ -398,7 +412,8 @@ int dclip_encoder_prepare(const dclip_encoder* enc, const void* const* params, v
  *                        may receive a gradient.
  *   scratch            : backward, dclip_attn_maps_bwd_workspace_bytes(B, heads, tokens) bytes (head-mixing students with d_prob)
  * Refused (DCLIP_EINVAL, nothing launched): an index out of range or, in the forward, above 63 (one bit per execution in the record),
- * maps together with tokens_eff != 0, a gradient for a map the forward did not export.  maps = NULL or n = 0 exports nothing;
+ * maps together with tokens_eff != 0, maps from a tower of more than 128 tokens (the limit of dclip_attn_maps_fwd), a gradient for a map
+ * the forward did not export.  maps = NULL or n = 0 exports nothing;
  * workspace sizes do not depend on maps. */
 typedef struct dclip_attn_maps {
     int32_t n;
@@ -424,7 +439,8 @@ typedef struct dclip_encoder_run {
  * dclip_im2row(..., cls_rows = 1), 16-byte aligned.  Teacher and student see the same image batch (reference
  * dual_distill_model.py:107-109, distil_model.py forward) and, when their patch size and resolution agree, the same conv1 /
  * PatchEmbed unfolding (_common.py:196-198, weight_share_model.py:344): one conversion then serves both towers.  input may then be
- * NULL (not both); patches are refused on text towers and together with tokens_eff != 0.
+ * NULL (not both); patches are refused on text towers, together with tokens_eff != 0, and on a tower that pads its patch rows
+ * (a frozen tower whose in_chans * patch^2 is not a multiple of 64: it cuts its own rows with dclip_im2row_ld).
  * training = 1 keeps every activation backward needs inside `workspace` (kinds 1 and 2).
  * rep_out (nullable array of layers*repeats nullable f32 [B*N, D] pointers) / emb_out (nullable f32 [B*N, D]) receive the hidden
  * state after each block execution and the post-positional-embedding tokens (ControlOutput.need_rep / need_emb of the

@@ -702,6 +702,33 @@ def attn_maps():
     print('attn_maps.npz', len(out), 'arrays', {k: float(v) for k, v in out.items() if k.endswith('.loss')})
 
 
+LONG_TEACHERS = {      # tag -> (seed, B, width, layers, patch, res, out_dim): frozen image towers past 128 tokens / with a padded patch
+    'b16': (2031, 2, 128, 2, 8, 112, 64),       # 197 tokens, K = 192: the token count of ViT-B/16
+    'p14': (2032, 2, 128, 2, 14, 56, 64),       # 17 tokens, K = 588: the padded unfold alone
+    'l14': (2033, 1, 128, 2, 14, 224, 64),      # 257 tokens, K = 588: the geometry of ViT-L/14
+}
+
+
+def long_teacher():
+    """tests/test_long_teacher_gpu.py: the reference's own ImageEncoder on three small frozen towers.  The images are synth.images(seed, B, res)
+    (deterministic; kept out of the file, with their float64 sum as a check): hidden states and the pooled output are what is stored."""
+    out = {}
+    for tag, (seed, B, width, layers, patch, res, out_dim) in LONG_TEACHERS.items():
+        m = build_teacher_image(seed, width, layers, patch, res, out_dim)
+        image = torch.from_numpy(synth.images(seed, B, res))
+        with torch.no_grad():
+            o = m(image, ControlOutput(need_rep=True, need_emb=True))
+        assert len(o.representations) == layers
+        out[f'{tag}.cfg'] = np.asarray([seed, B, width, layers, patch, res, out_dim], dtype=np.int64)
+        out[f'{tag}.image_sum'] = np.float64(image.double().sum().item())
+        out[f'{tag}.last_representation'] = np_(o.last_representation)
+        for i, r in enumerate(o.representations):
+            out[f'{tag}.rep{i}'] = np_(r)
+        print(tag, 'tokens', o.representations[0].shape[1], 'pooled', tuple(o.last_representation.shape))
+    np.savez_compressed(os.path.join(OUT, 'long_teacher.npz'), **out)
+    print('long_teacher.npz', len(out), 'arrays', os.path.getsize(os.path.join(OUT, 'long_teacher.npz')), 'bytes')
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ['tiny', 'loss', 'real', 'trajectory']
@@ -726,3 +753,5 @@ if __name__ == '__main__':
     if 'clip_student' in which:
         clip_student_tiny()
         clip_student_real()
+    if 'long_teacher' in which:
+        long_teacher()
