@@ -26,10 +26,8 @@ DEVFN f32x4 mfma_f16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f
 DEVFN float exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 DEVFN float log2(float x) { return __builtin_amdgcn_logf(x); }
 DEVFN bool any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-// LDS traffic of ONE wave (the weight-gradient tiles are wave-private).  The DS queue of a wave is in order, so a ds_read issued
-// after a ds_write sees the data of every lane; all that is needed is that the compiler keeps the program order.  (A workgroup-
-// scope release fence would also emit s_waitcnt vmcnt(0): the full latency of the LDS-DMA request in flight for the next quad.)
-DEVFN void lds_fence() { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+// LDS traffic of ONE wave (the weight-gradient tiles are wave-private): common.h, wave_lds_fence
+DEVFN void lds_fence() { wave_lds_fence(); }
 DEVFN void block_sync() { __syncthreads(); }
 // 16-byte LDS fragment read the compiler does not see as an LDS access (no s_waitcnt of its own: pair it with lds_wait_frags)
 template <int OFF>
@@ -51,15 +49,10 @@ DEVFN void lds_wait_frags(bf16x8 (&f)[GF]) {
 // the value lives in an AGPR from here on (MFMA B operands may be AGPRs; VGPRs stay free for what the VALU touches)
 DEVFN void pin_acc(bf16x8& v) { asm volatile("" : "+a"(v)); }
 DEVFN unsigned long long clock() { return __builtin_readcyclecounter(); }
-// MFMA source registers must outlive the MFMA's issue by ~10 issue slots.  The matrix pipe accepts MFMAs faster than it starts
-// them: an MFMA that queues behind two or three others reads its A / B registers only when its turn comes, and neither the hardware
-// nor hipcc's hazard recogniser keeps a VALU instruction from overwriting them meanwhile (asynchronous LDS / memory returns arrive
-// late enough).  Found with H = 8, hd = 32: the compiler reused the packed dA operand of the LAST of four back-to-back mix MFMAs
-// three instructions after it — wrong dS for the fourth key of every quad but the (peeled) first, deterministically, with no
-// tool complaining (tools/diag/mix_fuzz.py).  keep_alive() pins operands built by the VALU until a point well past the group,
-// at no cost in instructions; mfma_src_guard() is the blunt form (12 idle slots) where the operands cannot be named.
-template <class T8> DEVFN void keep_alive(const T8 (&f)[4]) { asm volatile("" :: "v"(f[0]), "v"(f[1]), "v"(f[2]), "v"(f[3])); }
-template <class T8> DEVFN void keep_alive(const T8& f) { asm volatile("" :: "v"(f)); }
+// operands built by the VALU stay live until a point well past their (queued) MFMAs (common.h, mfma_keep_alive);
+// mfma_src_guard() is the blunt form (12 idle slots) where the operands cannot be named.
+template <class T8> DEVFN void keep_alive(const T8 (&f)[4]) { mfma_keep_alive(f); }
+template <class T8> DEVFN void keep_alive(const T8& f) { mfma_keep_alive(f); }
 DEVFN void mfma_src_guard() { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 7\n\ts_nop 3" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
 // no instruction moves across this point.  Required, not a tuning knob: the hand-placed ds_read / s_waitcnt pairs around the ring
 // are only ordered against the MFMAs that consume them by these fences (a build without them fails test_kernels_gpu).

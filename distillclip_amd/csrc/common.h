@@ -80,6 +80,22 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// LDS traffic of ONE wave (wave-private tiles).  The DS queue of a wave is in order, so a ds_read issued after a ds_write sees the
+// data of every lane; all that is needed is that the compiler keeps the program order.  (A workgroup-scope release fence would also
+// emit s_waitcnt vmcnt(0): the full latency of whatever global loads / LDS-DMA requests are in flight for the next tile.)
+__device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+
+// MFMA source registers must outlive the MFMA's issue by ~10 issue slots.  The matrix pipe accepts MFMAs faster than it starts
+// them: an MFMA that queues behind two or three others reads its A / B registers only when its turn comes, and neither the hardware
+// nor hipcc's hazard recogniser keeps a VALU instruction from overwriting them meanwhile (asynchronous LDS / memory returns arrive
+// late enough).  Found with H = 8, hd = 32: the compiler reused the packed dA operand of the LAST of four back-to-back mix MFMAs
+// three instructions after it — wrong dS for the fourth key of every quad but the (peeled) first, deterministically, with no
+// tool complaining (tools/diag/mix_fuzz.py; tools/asm/mfma_hazard.py now looks for it).  mfma_keep_alive() pins operands (one
+// fragment, or a group of 2 or 4) until a point well past their MFMAs, at no cost in instructions.
+template <class T> __device__ __forceinline__ void mfma_keep_alive(const T& f) { asm volatile("" :: "v"(f)); }
+template <class T> __device__ __forceinline__ void mfma_keep_alive(const T (&f)[2]) { asm volatile("" :: "v"(f[0]), "v"(f[1])); }
+template <class T> __device__ __forceinline__ void mfma_keep_alive(const T (&f)[4]) { asm volatile("" :: "v"(f[0]), "v"(f[1]), "v"(f[2]), "v"(f[3])); }
+
 __device__ __forceinline__ float quick_gelu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * x)); }   // v_rcp_f32: 1 ulp
 // exact-GELU pieces with a branch-free erf (Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7, i.e. at the f32 rounding level of
 // libdevice's erff but ~4x fewer instructions; the activations are stored as bf16 anyway).  phi = exp(-x^2/2) is shared
