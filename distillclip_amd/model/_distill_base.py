@@ -104,6 +104,23 @@ class DistillBase(nn.Module):
         self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with
         return [opt], [sched]
 
+    def configure_gradient_clipping(self, optimizer, *args, gradient_clip_val=None, gradient_clip_algorithm=None, **kw):
+        """Lightning's hook for the trainer keys gradient_clip_val / gradient_clip_algorithm: called before every optimizer step as
+        (optimizer, gradient_clip_val, gradient_clip_algorithm), by older releases as (optimizer, optimizer_idx, gradient_clip_val,
+        gradient_clip_algorithm).  The clipping itself runs inside FusedAdamW.step(), on the gradients the optimizer really reads
+        (under the built-in exchange the averaged gradient shards, which p.grad never shows): this only hands over the threshold."""
+        args = list(args)
+        if len(args) >= 3 or (len(args) == 2 and isinstance(args[0], int) and not isinstance(args[1], (str, type(None)))):
+            args = args[1:]                                        # (optimizer_idx first)
+        if args:
+            gradient_clip_val = args[0]
+        if len(args) > 1:
+            gradient_clip_algorithm = args[1]
+        algorithm = getattr(gradient_clip_algorithm, 'value', gradient_clip_algorithm)       # (Lightning's GradClipAlgorithmType enum)
+        if algorithm not in (None, 'norm'):
+            raise ValueError(f'configure_gradient_clipping: FusedAdamW clips the global L2 norm only, not by {algorithm!r}')
+        optimizer.max_grad_norm = float(gradient_clip_val) if gradient_clip_val else None
+
     def unfreeze_embed(self):
         for _, p in self.student.named_parameters():
             p.requires_grad = True

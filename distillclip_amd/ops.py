@@ -284,3 +284,40 @@ def cast_transpose_multi(ws, want_b=True, want_t=True):
     C = (ctypes.c_int64 * n)(*[w.shape[1] for w in ws])
     lib().dclip_cast_transpose_bf16_multi(arr(ws), arr(wb), arr(wt), R, C, n, _stream())
     return (wb if want_b else None), (wt if want_t else None)
+
+
+SUMSQ_PARTIALS = 1024      # DCLIP_SUMSQ_PARTIALS (include/dclip.h): partial sums one dclip_sumsq_multi launch writes
+ADAMW_MAX_RANGES = 24      # DCLIP_ADAMW_MAX_RANGES
+
+
+def sumsq_multi(gs, partials, stream=None):
+    """partials[:SUMSQ_PARTIALS] <- partial sums of g^2 over at most 24 read-only f32 ranges `gs` in ONE launch, the rest of `partials` <- 0
+    (include/dclip.h: dclip_sumsq_multi); dclip_clip_coef adds them up"""
+    import ctypes
+    _chk(partials, *gs)
+    n = len(gs)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[g.data_ptr() for g in gs])
+    lens = (ctypes.c_int64 * max(n, 1))(*[g.numel() for g in gs])
+    lib().dclip_sumsq_multi(ptrs, lens, n, _p(partials), partials.numel(), _stream() if stream is None else stream)
+    return partials
+
+
+def clip_coef(partials, max_norm, out, extra_sumsq=None, stream=None):
+    """out[0] <- sqrt(sum(partials) [+ extra_sumsq[0]]), out[1] <- min(1, max_norm / (out[0] + 1e-6)) (include/dclip.h: dclip_clip_coef)"""
+    _chk(partials, extra_sumsq, out)
+    lib().dclip_clip_coef(_p(partials), partials.numel(), _p(extra_sumsq), float(max_norm), _p(out), _stream() if stream is None else stream)
+    return out
+
+
+def adamw_multi_scaled(items, lr, betas, eps, weight_decay, step, zero_grad=False, gscale=None, stream=None):
+    """AdamW on at most 24 ranges [(p, g, m, v)] of equally long 1-D f32 tensors in ONE launch, on g * gscale[0] (gscale: a device tensor,
+    None = unscaled; include/dclip.h: dclip_adamw_multi_scaled)"""
+    import ctypes
+    for it in items:
+        _chk(*it)
+    _chk(gscale)
+    n = len(items)
+    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items])
+    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
+    lib().dclip_adamw_multi_scaled(arr(0), arr(1), arr(2), arr(3), lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
+                                   1 if zero_grad else 0, _p(gscale), _stream() if stream is None else stream)

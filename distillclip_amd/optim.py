@@ -23,9 +23,16 @@ class FusedAdamW:
     (dual_distill_model.py:195, distil_model.py:161): parameters unfrozen later (unfreeze_embed) do not enter it.
 
     Data-parallel runs (tower.dp set by parallel.GradSync.plan): each rank updates only its 1/W shard of every gradient bucket
-    from the reduce-scattered average, keeps m / v for that shard only, and the updated parameters are all-gathered."""
+    from the reduce-scattered average, keeps m / v for that shard only, and the updated parameters are all-gathered.
 
-    def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=()):
+    max_grad_norm (None = off; a plain attribute, may change between steps): the step clips the global L2 norm of the gradients of
+    exactly the parameters this optimizer was built over, like torch.nn.utils.clip_grad_norm_(params, max_grad_norm) before
+    torch.optim.AdamW.step(): coef = min(1, max_grad_norm / (norm + 1e-6)) and the update uses g * coef.  Norm and coefficient
+    stay on the device (no host synchronisation); last_grad_norm is a 1-element device tensor holding the norm after step(), None
+    while clipping is off.  A non-finite norm is not special-cased: coef and the update become NaN, as in torch.  Gradients
+    scaled by a loss scaler (precision: 16) must be unscaled before step().  Not optimizer state: state_dict() does not carry it."""
+
+    def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None):
         """extra_params: trainable parameters that live outside the towers' flat buffers — the embedding_projection / hidden_projection
         linears of a plain CLIP encoder in the student role (reference image_encoder.py:23-25, text_encoder.py:45-47): four small tensors
         whose gradients autograd produces; each gets its own dclip_adamw launch (after an all-reduce of its gradient in a data-parallel
@@ -44,6 +51,9 @@ class FusedAdamW:
         # overlap mode only: also re-cast the bf16 weight cache right after the update.  Off by default: the re-cast of the NEXT
         # forward runs under the teacher towers' forward (4 streams wide), which hides it better than the end of the step does
         self.refresh_cache_in_step = False
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm = None
+        self._clip_parts = self._clip_out = None
 
     def _ranges(self, tw):
         """contiguous [begin, end) element ranges of the parameters this optimizer was built over"""
@@ -52,28 +62,56 @@ class FusedAdamW:
             r = self._fixed_ranges[id(tw)] = [list(x) for x in tw.trainable_ranges()]
         return r
 
-    def _adamw_hip(self, p, g, m, v, zero_grad, st):
+    def _adamw_hip(self, p, g, m, v, zero_grad, st, gscale=None):
         """p, g, m, v: equally long 1-D f32 views.  (tests/test_parallel_cpu.py substitutes a torch version as `_adamw` to rehearse the
-        sharded bookkeeping over gloo; the product path is the HIP kernel.)"""
+        sharded bookkeeping over gloo; the product path is the HIP kernel.)  gscale: 1-element tensor, the step uses g * gscale
+        (passed only by a clipping step)."""
+        if gscale is not None:
+            from . import ops
+            return ops.adamw_multi_scaled([(p, g, m, v)], self.lr, self.betas, self.eps, self.weight_decay, self.step_count, zero_grad, gscale, st)
         lib().dclip_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), self.lr, self.betas[0],
                           self.betas[1], self.eps, self.weight_decay, self.step_count, 1 if zero_grad else 0, st)
 
     _adamw = _adamw_hip
 
-    def _adamw_many(self, items, zero_grad, st):
+    def _sumsq_hip(self, views, out, st):
+        """out (f32, ops.SUMSQ_PARTIALS slots per 24 views, every slot written) <- partial sums of the squares of the 1-D f32 `views`.
+        (`_sumsq` and `_coef` can be substituted by torch versions like `_adamw`, for the gloo rehearsals.)"""
+        from . import ops
+        for i in range(0, len(views), ops.ADAMW_MAX_RANGES):
+            k = i // ops.ADAMW_MAX_RANGES
+            ops.sumsq_multi(views[i:i + ops.ADAMW_MAX_RANGES], out[k * ops.SUMSQ_PARTIALS:(k + 1) * ops.SUMSQ_PARTIALS], st)
+
+    _sumsq = _sumsq_hip
+
+    def _coef_hip(self, partials, extra, out, st):
+        """out[0] <- sqrt(sum(partials) + extra[0]) (extra may be None), out[1] <- min(1, max_grad_norm / (out[0] + 1e-6))"""
+        from . import ops
+        ops.clip_coef(partials, self.max_grad_norm, out, extra, st)
+
+    _coef = _coef_hip
+
+    def _adamw_many(self, items, zero_grad, st, gscale=None):
         """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE dclip_adamw_multi launch per 24 ranges (the sharded step has one
         owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower)"""
         import ctypes
         if type(self)._adamw is not FusedAdamW._adamw_hip or any(p.numel() % 4 or (p.data_ptr() | g.data_ptr() | m.data_ptr() | v.data_ptr()) % 16
                                                                   for p, g, m, v in items):
             for p, g, m, v in items:
-                self._adamw(p, g, m, v, zero_grad, st)
+                if gscale is None:
+                    self._adamw(p, g, m, v, zero_grad, st)
+                else:
+                    self._adamw(p, g, m, v, zero_grad, st, gscale)
             return
         for i in range(0, len(items), 24):
             chunk = items[i:i + 24]
             n = len(chunk)
             arr = lambda k: (ctypes.c_void_p * n)(*[t[k].data_ptr() for t in chunk])
             lens = (ctypes.c_int64 * n)(*[t[0].numel() for t in chunk])
+            if gscale is not None:
+                lib().dclip_adamw_multi_scaled(arr(0), arr(1), arr(2), arr(3), lens, n, self.lr, self.betas[0], self.betas[1], self.eps,
+                                               self.weight_decay, self.step_count, 1 if zero_grad else 0, gscale.data_ptr(), st)
+                continue
             lib().dclip_adamw_multi(arr(0), arr(1), arr(2), arr(3), lens, n, self.lr, self.betas[0], self.betas[1], self.eps,
                                     self.weight_decay, self.step_count, 1 if zero_grad else 0, st)
 
@@ -135,7 +173,20 @@ class FusedAdamW:
                                 torch.zeros(max(n, 1), dtype=torch.float32, device=tw.flat.device))
         return self._state[key]
 
-    def _step_sharded(self, tw):
+    @staticmethod
+    def _shard_items(tw, m, v):
+        """[(p, g, m, v)] of the trainable slices this rank owns: one per gradient bucket and trainable range inside its shard"""
+        items = []
+        for b in tw.dp.buckets:
+            if b is None:
+                continue
+            b0, b1, o0, o1, off, own_tr = b
+            for a, e in own_tr:
+                lo, hi = off + a - o0, off + e - o0
+                items.append((tw.flat[a:e], tw.gshard[lo:hi], m[lo:hi], v[lo:hi]))
+        return items
+
+    def _step_sharded(self, tw, gscale=None):
         """reduce-scattered gradient shards -> AdamW on the owned slices -> all-gather of the updated parameters, all on the
         exchange stream behind the tower's reduce-scatters (which were released from inside its backward)."""
         from .parallel import all_gather_flat
@@ -151,16 +202,9 @@ class FusedAdamW:
         works = []
         with sync._On(s):
             st = s.cuda_stream if s is not None else None
-            items = []
-            for b in tw.dp.buckets:
-                if b is None:
-                    continue
-                b0, b1, o0, o1, off, own_tr = b
-                for a, e in own_tr:
-                    lo, hi = off + a - o0, off + e - o0
-                    items.append((tw.flat[a:e], tw.gshard[lo:hi], m[lo:hi], v[lo:hi]))
+            items = self._shard_items(tw, m, v)
             if items:
-                self._adamw_many(items, False, st)
+                self._adamw_many(items, False, st, gscale)
             for b in tw.dp.buckets:
                 if b is not None:
                     b0, b1, o0, o1, off, own_tr = b
@@ -194,6 +238,9 @@ class FusedAdamW:
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
         on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
         main = torch.cuda.current_stream() if on_gpu else None
+        if self.max_grad_norm is not None:
+            return self._step_clipped(zero_grad, overlap, join, main)
+        self.last_grad_norm = None
         joined = []
         for tw in self.towers:
             if tw.flat is None:
@@ -233,6 +280,96 @@ class FusedAdamW:
             for tw in self.towers:
                 tw.opt_done = None
 
+    def _step_clipped(self, zero_grad, overlap, join, main):
+        """step() with max_grad_norm set.  Three phases, ordered by events only:
+          1. every tower's sum of squared gradients, on the stream that tower's update runs on (behind its backward / exchange);
+          2. on the current stream, after all of them: the extras' sum, the cross-rank sum, ONE clip_coef -> (norm, coef);
+          3. every update, after the coefficient, reading it from the device.
+        Data-parallel: a sharded tower contributes the squares of this rank's owned slices of the averaged gradient (tw.gshard), so
+        those sums are added over the ranks (one all-reduce of one double); gradients every rank holds whole — the extras after
+        their all-reduce, a tower that is not sharded — are identical everywhere and enter once, as clip_coef's extra_sumsq.
+        Every rank computes the coefficient from the same bits in the same order."""
+        from . import ops
+        from .model.component._tower import autograd_params_mode
+        from .parallel import GradSync, all_reduce_sum
+        G, R = ops.SUMSQ_PARTIALS, ops.ADAMW_MAX_RANGES
+        towers = [tw for tw in self.towers if tw.flat is not None]
+        jobs = []                                                # [tower, stream, items, sharded]
+        for tw in towers:
+            m, v = self._moments(tw)
+            if self._sharded(tw):
+                jobs.append([tw, tw.sync.stream_for(tw.flat, tw), self._shard_items(tw, m, v), True])
+                continue
+            stream = tw.bwd_stream if (overlap and not autograd_params_mode(tw) and getattr(tw, 'bwd_stream', None) is not None) else main
+            jobs.append([tw, stream, [(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)], False])
+        jobs.sort(key=lambda j: not j[3])                        # (stable) the sharded towers' partial sums lie first
+        extras = self._extra_items()
+        slots = [G * ((len(j[2]) + R - 1) // R) for j in jobs] + [G * ((len(extras) + R - 1) // R)]
+        device = towers[0].flat.device if towers else self.extras[0].device
+        if self._clip_parts is None or self._clip_parts.numel() != max(sum(slots), 1) or self._clip_parts.device != device:
+            self._clip_parts = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
+        parts, out = self._clip_parts, self._clip_out
+        # ---- 1. sums
+        at = 0
+        for (tw, stream, items, sharded), n in zip(jobs, slots):
+            if stream is not None and stream != main:
+                stream.wait_stream(main)                         # whatever the caller enqueued before step() (see step / _step_sharded)
+            if not sharded and getattr(tw, 'grads_ready', None) is not None:
+                stream.wait_event(tw.grads_ready)
+                tw.grads_ready = None
+            with GradSync._On(stream):
+                if not sharded and autograd_params_mode(tw):
+                    self._pack_autograd_grads(tw)
+                if items:
+                    self._sumsq([it[1] for it in items], parts[at:at + n], stream.cuda_stream if stream is not None else None)
+            if stream is not None and stream != main:
+                ev = torch.cuda.Event()
+                ev.record(stream)
+                main.wait_event(ev)
+            at += n
+        # ---- 2. one coefficient
+        st = main.cuda_stream if main is not None else None
+        if extras:
+            self._sumsq([it[1] for it in extras], parts[at:at + slots[-1]], st)
+        n_sharded = sum(n for j, n in zip(jobs, slots) if j[3])
+        if any(j[3] for j in jobs):
+            total = parts[:n_sharded].sum(dtype=torch.float64).view(1)
+            all_reduce_sum(total)
+            rest = parts[n_sharded:sum(slots)]
+            self._coef(total.float(), rest.sum(dtype=torch.float64).float().view(1) if rest.numel() else None, out, st)
+        else:
+            self._coef(parts, None, out, st)
+        self.last_grad_norm, coef = out[0:1], out[1:2]
+        # ---- 3. updates
+        joined = []
+        for tw, stream, items, sharded in jobs:
+            if sharded:
+                s = self._step_sharded(tw, coef)                 # (its exchange stream waits for the current one: the coefficient)
+                if s is not None:
+                    joined.append(s)
+                continue
+            if stream is not None and stream != main:
+                stream.wait_stream(main)
+            with GradSync._On(stream):
+                self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef)
+                tw.wcache_dirty = True
+                tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
+                if overlap and self.refresh_cache_in_step:
+                    tw._prepare_always = False
+                    tw.prepare()
+            if stream is not None and stream != main:
+                joined.append(stream)
+                tw.opt_done = torch.cuda.Event()
+                tw.opt_done.record(stream)
+        if extras:
+            self._adamw_many(extras, zero_grad, st, coef)
+        if join:
+            for stream in joined:
+                main.wait_stream(stream)
+            for tw in self.towers:
+                tw.opt_done = None
+
     def _extra_moments(self, p):
         st = self._extra_state.get(id(p))
         if st is None:
@@ -242,8 +379,14 @@ class FusedAdamW:
 
     def _step_extras(self, zero_grad, main):
         """the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)"""
+        items = self._extra_items()
+        if items:
+            self._adamw_many(items, zero_grad, main.cuda_stream if main is not None else None)
+
+    def _extra_items(self):
+        """[(p, g, m, v)] of the extras that have a gradient, the gradients averaged over the ranks"""
         if not self.extras:
-            return
+            return []
         from .parallel import all_reduce_avg
         sync = next((tw.sync for tw in self.towers if getattr(tw, 'sync', None) is not None), None)
         items = []
@@ -256,8 +399,7 @@ class FusedAdamW:
                 all_reduce_avg(p.grad)
             m, v = self._extra_moments(p)
             items.append((p.data.view(-1), p.grad.view(-1), m, v))
-        if items:
-            self._adamw_many(items, zero_grad, main.cuda_stream if main is not None else None)
+        return items
 
     def join(self):
         """order the current stream after every tower's pending (un-joined) update"""

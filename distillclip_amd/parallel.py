@@ -58,6 +58,11 @@ def all_reduce_avg(t, group=None):
     t.mul_(1.0 / dist.get_world_size())
 
 
+def all_reduce_sum(t, group=None):
+    """t <- element-wise sum over the ranks, in place: the same bits on every rank (the clipping step's sum of squares)"""
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+
 def all_gather_flat(out, inp, async_op=False, group=None):
     """out[r * n:(r + 1) * n] <- rank r's `inp` (out may contain inp in place)"""
     if _native() or not inp.is_cuda:

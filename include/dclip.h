@@ -251,6 +251,26 @@ int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, flo
 #define DCLIP_ADAMW_MAX_RANGES 24
 int dclip_adamw_multi(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
                       float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, void* stream);
+/* dclip_adamw_multi on gs = g * (*gscale), the product rounded to f32 before anything else uses it (gscale: DEVICE pointer to one
+ * f32, read by the kernel, e.g. out + 1 of dclip_clip_coef).  gscale NULL: dclip_adamw_multi itself. */
+int dclip_adamw_multi_scaled(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count,
+                             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad,
+                             const float* gscale, void* stream);
+/*
+ * Global gradient-norm clipping, torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) (the reference reaches it through
+ * Lightning's gradient_clip_val), without a host-visible norm:
+ *   sumsq_multi : sum of g^2 over `count` <= DCLIP_ADAMW_MAX_RANGES read-only ranges (HOST arrays; the alignment rules of
+ *                 dclip_adamw_multi) as DCLIP_SUMSQ_PARTIALS f32 partial sums, one per workgroup, partials[0 .. n_partials)
+ *                 (n_partials >= DCLIP_SUMSQ_PARTIALS; the slots past the workgroups' are written as 0).  No atomics: the same
+ *                 call gives the same bits.
+ *   clip_coef   : sum = partials[0] + ... + partials[n_partials - 1] (in double, fixed order) + *extra_sumsq (DEVICE, may be NULL:
+ *                 a sum of squares that is already complete, e.g. of gradients every rank holds whole) ;
+ *                 out[0] = (float)sqrt(sum) ; out[1] = min(1, max_norm / (out[0] + 1e-6f)).  A non-finite sum is not
+ *                 special-cased: NaN gives out[1] = NaN, as torch does.
+ */
+#define DCLIP_SUMSQ_PARTIALS 1024
+int dclip_sumsq_multi(const float* const* g, const int64_t* n, int32_t count, float* partials, int64_t n_partials, void* stream);
+int dclip_clip_coef(const float* partials, int64_t n_partials, const float* extra_sumsq, float max_norm, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused distillation loss, forward + backward.
