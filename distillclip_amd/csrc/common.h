@@ -66,6 +66,12 @@ static inline int dclip_check_launch(const char* what) {
     return DCLIP_OK;
 }
 
+// workgroups of a grid-stride launch: ceil(work / per_block), at least 1, at most cap
+static inline int grid_for(int64_t work, int per_block = 256, int cap = 2048 * 4) {
+    int64_t g = (work + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
 __device__ __forceinline__ float bf2f(bf16_t x) { return (float)x; }
 __device__ __forceinline__ bf16_t f2bf(float x) { return (bf16_t)x; }   // v_cvt_pk_bf16_f32: RNE, NaN-preserving
 

@@ -331,56 +331,6 @@ __global__ __launch_bounds__(256) void pick_index_kernel(const int64_t* __restri
     if (lane == 0) idx[b] = b * N + best;
 }
 
-// torch.optim.AdamW semantics (decoupled weight decay; bias-corrected), reference distil_model.py:160-162
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2,
-                                                    float eps, float wd, float bc1, float bc2_sqrt, int zero_grad) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float gi = g[i];
-        float pi = p[i] * (1.f - lr * wd);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        pi -= (lr / bc1) * (mi / denom);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (zero_grad) g[i] = 0.f;                // the gradient is consumed: leave the accumulator clean for the next backward
-    }
-}
-
-// float4 form of adamw_kernel (same per-element arithmetic).  The loads of the next grid-stride iteration are issued before the
-// stores of the current one: vmcnt retires loads and stores in one in-order queue, so loads that follow stores wait for the
-// stores' acknowledgements as well.
-__device__ __forceinline__ void adamw_elem(float& pi, float gi, float& mi, float& vi, float lr, float b1, float b2, float eps,
-                                           float wd, float bc1, float bc2_sqrt) {
-    pi = pi * (1.f - lr * wd);
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-}
-__global__ __launch_bounds__(256) void adamw4_kernel(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m,
-                                                     float4* __restrict__ v, int64_t n4, float lr, float b1, float b2, float eps,
-                                                     float wd, float bc1, float bc2_sqrt, int zero_grad) {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
-    for (;;) {
-        const int64_t nx = i + stride;
-        const bool more = nx < n4;
-        float4 pn = pi, gn = gi, mn = mi, vn = vi;
-        if (more) { pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx]; }
-        adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (zero_grad) g[i] = float4{0.f, 0.f, 0.f, 0.f};
-        if (!more) break;
-        i = nx; pi = pn; gi = gn; mi = mn; vi = vn;
-    }
-}
-
 // dst += src (f32) ; optional bf16 copy of the updated dst.  Four independent 16-byte pieces per thread and trip: all their loads are in
 // flight before the first store.
 __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ dst, const float* __restrict__ src, bf16_t* __restrict__ dst_bf16, int64_t n) {
@@ -463,11 +413,6 @@ __global__ __launch_bounds__(256) void rows_expand_kernel(const u32x4* __restric
         const int j = (int)(c - row * q);
         dst[c] = row == idx[b] ? src[b * q + j] : u32x4{0u, 0u, 0u, 0u};
     }
-}
-
-inline int grid_for(int64_t work, int per_block = 256, int cap = 2048 * 4) {
-    int64_t g = (work + per_block - 1) / per_block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 }  // namespace
@@ -603,115 +548,6 @@ extern "C" int dclip_pick_index(const int64_t* ids, int64_t id_stride, int32_t* 
     DCLIP_REQUIRE(idx && B > 0 && N > 0 && id_stride >= N, "dclip_pick_index: bad argument");
     hipLaunchKernelGGL(pick_index_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ids, (int)id_stride, idx, (int)B, (int)N);
     return dclip_check_launch("dclip_pick_index");
-}
-
-// several ranges in one launch (blockIdx.y = range): the sharded data-parallel step updates one owned slice per gradient bucket — 9 launches
-// of ~20 us each per step for the two l_clip students where two whole-tower launches do the same bytes
-struct AdamwRanges { float4* p[DCLIP_ADAMW_MAX_RANGES]; float4* g[DCLIP_ADAMW_MAX_RANGES]; float4* m[DCLIP_ADAMW_MAX_RANGES]; float4* v[DCLIP_ADAMW_MAX_RANGES]; int64_t n4[DCLIP_ADAMW_MAX_RANGES]; };
-__global__ __launch_bounds__(256) void adamw4_multi_kernel(AdamwRanges r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                           int zero_grad) {
-    const int k = blockIdx.y;
-    float4* __restrict__ p = r.p[k]; float4* __restrict__ g = r.g[k]; float4* __restrict__ m = r.m[k]; float4* __restrict__ v = r.v[k];
-    const int64_t n4 = r.n4[k];
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
-    for (;;) {
-        const int64_t nx = i + stride;
-        const bool more = nx < n4;
-        float4 pn = pi, gn = gi, mn = mi, vn = vi;
-        if (more) { pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx]; }
-        adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (zero_grad) g[i] = float4{0.f, 0.f, 0.f, 0.f};
-        if (!more) break;
-        i = nx; pi = pn; gi = gn; mi = mn; vi = vn;
-    }
-}
-// the same kernel on g * (*gscale), one f32 product per element before anything else uses it: the coefficient of the global-norm clipping
-// (gradnorm.hip) is read from the device, so no host waits for the norm
-__global__ __launch_bounds__(256) void adamw4_multi_scaled_kernel(AdamwRanges r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                           int zero_grad, const float* __restrict__ gscale) {
-    const int k = blockIdx.y;
-    float4* __restrict__ p = r.p[k]; float4* __restrict__ g = r.g[k]; float4* __restrict__ m = r.m[k]; float4* __restrict__ v = r.v[k];
-    const int64_t n4 = r.n4[k];
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    const float gs = *gscale;
-    float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
-    for (;;) {
-        const int64_t nx = i + stride;
-        const bool more = nx < n4;
-        float4 pn = pi, gn = gi, mn = mi, vn = vi;
-        if (more) { pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx]; }
-        gi.x *= gs; gi.y *= gs; gi.z *= gs; gi.w *= gs;
-        adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (zero_grad) g[i] = float4{0.f, 0.f, 0.f, 0.f};
-        if (!more) break;
-        i = nx; pi = pn; gi = gn; mi = mn; vi = vn;
-    }
-}
-
-static int adamw_multi_launch(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
-                              float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, const float* gscale, void* stream) {
-    DCLIP_REQUIRE(p && g && m && v && n && count > 0 && count <= DCLIP_ADAMW_MAX_RANGES && step >= 1, "%s: bad argument (1..%d ranges)", what, DCLIP_ADAMW_MAX_RANGES);
-    AdamwRanges r;
-    int64_t longest = 0;
-    for (int k = 0; k < count; ++k) {
-        DCLIP_REQUIRE(p[k] && g[k] && m[k] && v[k] && n[k] > 0 && n[k] % 4 == 0 && ((((uintptr_t)p[k] | (uintptr_t)g[k] | (uintptr_t)m[k] | (uintptr_t)v[k]) & 15) == 0),
-                      "%s: range %d must be non-empty, a multiple of 4 elements and 16-byte aligned", what, k);
-        r.p[k] = (float4*)p[k]; r.g[k] = (float4*)g[k]; r.m[k] = (float4*)m[k]; r.v[k] = (float4*)v[k]; r.n4[k] = n[k] / 4;
-        longest = r.n4[k] > longest ? r.n4[k] : longest;
-    }
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
-    const int per_range = 8192 / count < 256 ? 256 : 8192 / count;          // (grid-stride loop: the longest range sets the width, capped)
-    const dim3 grid(grid_for(longest, 256, per_range), (unsigned)count);
-    if (gscale)
-        hipLaunchKernelGGL(adamw4_multi_scaled_kernel, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
-                           zero_grad, gscale);
-    else
-        hipLaunchKernelGGL(adamw4_multi_kernel, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad);
-    return dclip_check_launch(what);
-}
-
-extern "C" int dclip_adamw_multi(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
-                                 float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, void* stream) {
-    return adamw_multi_launch("dclip_adamw_multi", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, nullptr, stream);
-}
-
-extern "C" int dclip_adamw_multi_scaled(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count,
-                                        float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad,
-                                        const float* gscale, void* stream) {
-    return adamw_multi_launch("dclip_adamw_multi_scaled", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, gscale, stream);
-}
-
-extern "C" int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                           float eps, float weight_decay, int64_t step, int zero_grad, void* stream) {
-    DCLIP_REQUIRE(p && g && m && v && n > 0 && step >= 1, "dclip_adamw: bad argument");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
-    // 16-byte aligned buffers (the flat parameter layout guarantees it; odd slices fall back): float4 kernel for the multiple-of-4
-    // part, the scalar kernel for a tail of < 4 elements
-    int64_t n4 = 0;
-    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) n4 = n / 4;
-    if (n4 > 0)
-        hipLaunchKernelGGL(adamw4_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (float4*)g, (float4*)m,
-                           (float4*)v, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad);
-    const int64_t done = 4 * n4;
-    if (done < n)
-        hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n - done)), dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done,
-                           v + done, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad);
-    return dclip_check_launch("dclip_adamw");
 }
 
 extern "C" int dclip_axpy_f32(float* dst, const float* src, void* dst_bf16, int64_t n, float* colsum_acc, int64_t D, void* stream) {

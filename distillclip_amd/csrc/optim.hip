@@ -1,0 +1,223 @@
+// The optimizer step's device code.  Global gradient norm for clipping (include/dclip.h: dclip_sumsq_multi, dclip_clip_coef):
+// torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) with the norm and the coefficient staying on the device.  AdamW
+// (dclip_adamw, dclip_adamw_multi, dclip_adamw_multi_scaled): torch.optim.AdamW on f32 ranges, optionally on g * that coefficient.
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+
+// One workgroup tile: 256 lanes x SUMSQ_LOADS float4 (16-byte) loads, all issued before the first is used.
+constexpr int SUMSQ_LOADS = 8;
+constexpr int SUMSQ_TILE4 = 256 * SUMSQ_LOADS;          // float4 per tile (SUMSQ_TILE4 * 4 = 8192 elements)
+
+struct SumsqRanges {
+    const float4* g[DCLIP_ADAMW_MAX_RANGES];
+    int64_t n4[DCLIP_ADAMW_MAX_RANGES];
+    int64_t tile0[DCLIP_ADAMW_MAX_RANGES + 1];          // first tile of range k in the launch's tile list ; [count] = all tiles
+};
+
+// partials[b] = sum of g^2 over the tiles b, b + DCLIP_SUMSQ_PARTIALS, ... of the ranges' tile list (every range starts a new tile;
+// the grid is DCLIP_SUMSQ_PARTIALS workgroups whatever the data, so each partial is the same sum in the same order on every call).
+//
+// Rounding: per tile a lane squares-and-adds its SUMSQ_LOADS float4 into four f32 accumulators, one per component, by fmaf (the
+// square is not rounded on its own), so the longest serial f32 accumulation chain is
+//     L = SUMSQ_LOADS = 8 elements,
+// followed by a tree of two f32 additions.  The lane's tile sum then goes into a double, and everything after it (the lane's
+// further tiles, the wave, the workgroup) is added in double; the f32 partial is one rounding of that.  HBM-bound: 4 bytes per
+// element read once, 1 v_fma_f32 per element and 2 double-rate instructions per 32.
+__global__ __launch_bounds__(256) void sumsq_multi_kernel(SumsqRanges r, int count, float* __restrict__ partials, int64_t n_partials) {
+    __shared__ double wave_part[4];
+    const int64_t tiles = r.tile0[count];
+    double acc = 0.0;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        int k = 0;
+        while (t >= r.tile0[k + 1]) ++k;                 // (uniform ; t < tile0[count] ends it inside the table)
+        const float4* __restrict__ g = r.g[k];
+        const int64_t n4 = r.n4[k];
+        const int64_t base = (t - r.tile0[k]) * SUMSQ_TILE4 + threadIdx.x;
+        float4 x[SUMSQ_LOADS];
+        if ((t - r.tile0[k] + 1) * SUMSQ_TILE4 <= n4) {  // (uniform) a whole tile: eight loads back to back, no per-lane test between them
+#pragma unroll
+            for (int u = 0; u < SUMSQ_LOADS; ++u) x[u] = g[base + u * 256];
+        } else {                                         // the range's last tile
+#pragma unroll
+            for (int u = 0; u < SUMSQ_LOADS; ++u) {
+                const int64_t i = base + u * 256;
+                x[u] = i < n4 ? g[i] : float4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        float4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < SUMSQ_LOADS; ++u) {
+            s.x = fmaf(x[u].x, x[u].x, s.x);
+            s.y = fmaf(x[u].y, x[u].y, s.y);
+            s.z = fmaf(x[u].z, x[u].z, s.z);
+            s.w = fmaf(x[u].w, x[u].w, s.w);
+        }
+        acc += (double)((s.x + s.y) + (s.z + s.w));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (float)(((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3]);
+    if (blockIdx.x == 0)
+        for (int64_t i = (int64_t)gridDim.x + threadIdx.x; i < n_partials; i += 256) partials[i] = 0.f;
+}
+
+// One workgroup.  Lane t adds the slots t, t + 256, ... in rising index order, the 256 lane sums meet in a fixed tree: all in
+// double, where the order of at most a few thousand non-negative f32 terms moves the sum by parts in 2^-40 — nothing the f32
+// results can show — and a fixed order gives every call (and every rank of a data-parallel run) the same bits.
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, int64_t n_partials, const float* __restrict__ extra_sumsq,
+                                                        float max_norm, float* __restrict__ out) {
+    __shared__ double wave_part[4];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n_partials; i += 256) acc += (double)partials[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
+        if (extra_sumsq) sum += (double)*extra_sumsq;
+        const float norm = (float)sqrt(sum);
+        const float c = max_norm / (norm + 1e-6f);
+        out[0] = norm;
+        out[1] = c > 1.f ? 1.f : c;                      // (a NaN stays a NaN, like torch.clamp(max=1))
+    }
+}
+
+// torch.optim.AdamW semantics (decoupled weight decay; bias-corrected), reference distil_model.py:160-162
+__device__ __forceinline__ void adamw_elem(float& pi, float gi, float& mi, float& vi, float lr, float b1, float b2, float eps,
+                                           float wd, float bc1, float bc2_sqrt) {
+    pi = pi * (1.f - lr * wd);
+    mi = b1 * mi + (1.f - b1) * gi;
+    vi = b2 * vi + (1.f - b2) * gi * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+}
+
+// an element per thread: ranges that are misaligned, and the tail of < 4 elements of the others
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2,
+                                                    float eps, float wd, float bc1, float bc2_sqrt, int zero_grad) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float gi = g[i];
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_elem(pi, gi, mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (zero_grad) g[i] = 0.f;                // the gradient is consumed: leave the accumulator clean for the next backward
+    }
+}
+
+// float4 form, several ranges in one launch (blockIdx.y = range): the sharded data-parallel step updates one owned slice per gradient
+// bucket — 9 launches of ~20 us each per step for the two l_clip students where two whole-tower launches do the same bytes.
+// SCALED: on g * (*gscale), one f32 product per element before anything else uses it: the coefficient of the global-norm clipping is
+// read from the device, so no host waits for the norm.
+// The loads of the next grid-stride iteration are issued before the stores of the current one: vmcnt retires loads and stores in
+// one in-order queue, so loads that follow stores wait for the stores' acknowledgements as well.
+struct AdamwRanges { float4* p[DCLIP_ADAMW_MAX_RANGES]; float4* g[DCLIP_ADAMW_MAX_RANGES]; float4* m[DCLIP_ADAMW_MAX_RANGES]; float4* v[DCLIP_ADAMW_MAX_RANGES]; int64_t n4[DCLIP_ADAMW_MAX_RANGES]; };
+template <bool SCALED>
+__global__ __launch_bounds__(256) void adamw4_multi_kernel(AdamwRanges r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                           int zero_grad, const float* __restrict__ gscale) {
+    const int k = blockIdx.y;
+    float4* __restrict__ p = r.p[k]; float4* __restrict__ g = r.g[k]; float4* __restrict__ m = r.m[k]; float4* __restrict__ v = r.v[k];
+    const int64_t n4 = r.n4[k];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float gs = SCALED ? *gscale : 1.f;
+    float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
+    for (;;) {
+        const int64_t nx = i + stride;
+        const bool more = nx < n4;
+        float4 pn = pi, gn = gi, mn = mi, vn = vi;
+        if (more) { pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx]; }
+        if (SCALED) { gi.x *= gs; gi.y *= gs; gi.z *= gs; gi.w *= gs; }
+        adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (zero_grad) g[i] = float4{0.f, 0.f, 0.f, 0.f};
+        if (!more) break;
+        i = nx; pi = pn; gi = gn; mi = mn; vi = vn;
+    }
+}
+
+int adamw_multi_launch(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, const float* gscale, void* stream) {
+    DCLIP_REQUIRE(p && g && m && v && n && count > 0 && count <= DCLIP_ADAMW_MAX_RANGES && step >= 1, "%s: bad argument (1..%d ranges)", what, DCLIP_ADAMW_MAX_RANGES);
+    AdamwRanges r;
+    int64_t longest = 0;
+    for (int k = 0; k < count; ++k) {
+        DCLIP_REQUIRE(p[k] && g[k] && m[k] && v[k] && n[k] > 0 && n[k] % 4 == 0 && ((((uintptr_t)p[k] | (uintptr_t)g[k] | (uintptr_t)m[k] | (uintptr_t)v[k]) & 15) == 0),
+                      "%s: range %d must be non-empty, a multiple of 4 elements and 16-byte aligned", what, k);
+        r.p[k] = (float4*)p[k]; r.g[k] = (float4*)g[k]; r.m[k] = (float4*)m[k]; r.v[k] = (float4*)v[k]; r.n4[k] = n[k] / 4;
+        longest = r.n4[k] > longest ? r.n4[k] : longest;
+    }
+    const float bc1 = 1.f - powf(beta1, (float)step);
+    const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
+    const int per_range = 8192 / count < 256 ? 256 : 8192 / count;          // (grid-stride loop: the longest range sets the width, capped)
+    const dim3 grid(grid_for(longest, 256, per_range), (unsigned)count);
+    hipLaunchKernelGGL(gscale ? adamw4_multi_kernel<true> : adamw4_multi_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps,
+                       weight_decay, bc1, bc2, zero_grad, gscale);
+    return dclip_check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int dclip_sumsq_multi(const float* const* g, const int64_t* n, int32_t count, float* partials, int64_t n_partials, void* stream) {
+    DCLIP_REQUIRE(g && n && partials && count > 0 && count <= DCLIP_ADAMW_MAX_RANGES, "dclip_sumsq_multi: bad argument (1..%d ranges)", DCLIP_ADAMW_MAX_RANGES);
+    DCLIP_REQUIRE(n_partials >= DCLIP_SUMSQ_PARTIALS && ((uintptr_t)partials & 3) == 0, "dclip_sumsq_multi: partials needs at least %d slots", DCLIP_SUMSQ_PARTIALS);
+    SumsqRanges r;
+    r.tile0[0] = 0;
+    for (int k = 0; k < count; ++k) {
+        DCLIP_REQUIRE(g[k] && n[k] > 0 && n[k] % 4 == 0 && ((uintptr_t)g[k] & 15) == 0,
+                      "dclip_sumsq_multi: range %d must be non-empty, a multiple of 4 elements and 16-byte aligned", k);
+        r.g[k] = (const float4*)g[k];
+        r.n4[k] = n[k] / 4;
+        r.tile0[k + 1] = r.tile0[k] + (r.n4[k] + SUMSQ_TILE4 - 1) / SUMSQ_TILE4;
+    }
+    for (int k = count; k < DCLIP_ADAMW_MAX_RANGES; ++k) { r.g[k] = nullptr; r.n4[k] = 0; r.tile0[k + 1] = r.tile0[count]; }
+    hipLaunchKernelGGL(sumsq_multi_kernel, dim3(DCLIP_SUMSQ_PARTIALS), dim3(256), 0, (hipStream_t)stream, r, (int)count, partials, n_partials);
+    return dclip_check_launch("dclip_sumsq_multi");
+}
+
+extern "C" int dclip_clip_coef(const float* partials, int64_t n_partials, const float* extra_sumsq, float max_norm, float* out, void* stream) {
+    DCLIP_REQUIRE(partials && n_partials > 0 && out, "dclip_clip_coef: bad argument");
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, n_partials, extra_sumsq, max_norm, out);
+    return dclip_check_launch("dclip_clip_coef");
+}
+
+extern "C" int dclip_adamw_multi(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, void* stream) {
+    return adamw_multi_launch("dclip_adamw_multi", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, nullptr, stream);
+}
+
+extern "C" int dclip_adamw_multi_scaled(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count,
+                                        float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad,
+                                        const float* gscale, void* stream) {
+    return adamw_multi_launch("dclip_adamw_multi_scaled", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, gscale, stream);
+}
+
+extern "C" int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, int64_t step, int zero_grad, void* stream) {
+    DCLIP_REQUIRE(p && g && m && v && n > 0 && step >= 1, "dclip_adamw: bad argument");
+    // 16-byte aligned buffers (the flat parameter layout guarantees it; odd slices fall back): the float4 kernel, one range, for the
+    // multiple-of-4 part, the scalar kernel for a tail of < 4 elements
+    int64_t done = 0;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) done = n / 4 * 4;
+    if (done > 0) {
+        const int rc = adamw_multi_launch("dclip_adamw", &p, &g, &m, &v, &done, 1, lr, beta1, beta2, eps, weight_decay, step, zero_grad, nullptr, stream);
+        if (rc != DCLIP_OK) return rc;
+    }
+    if (done < n) {
+        const float bc1 = 1.f - powf(beta1, (float)step);
+        const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
+        hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n - done)), dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done,
+                           v + done, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad);
+    }
+    return dclip_check_launch("dclip_adamw");
+}

@@ -17,7 +17,8 @@ def cosine_with_warmup(step, warm, total):
 
 
 class FusedAdamW:
-    """One dclip_adamw launch per contiguous trainable range of each tower's flat buffer.
+    """AdamW over the contiguous trainable ranges of each tower's flat buffer: one multi-range launch (dclip_adamw_multi_scaled) per
+    tower and 24 ranges; a range of odd length or off a 16-byte boundary gets a dclip_adamw launch of its own.
 
     The trainable set is fixed when the optimizer is built, like the reference's AdamW(filter(requires_grad, parameters()))
     (dual_distill_model.py:195, distil_model.py:161): parameters unfrozen later (unfreeze_embed) do not enter it.
@@ -35,8 +36,8 @@ class FusedAdamW:
     def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None):
         """extra_params: trainable parameters that live outside the towers' flat buffers — the embedding_projection / hidden_projection
         linears of a plain CLIP encoder in the student role (reference image_encoder.py:23-25, text_encoder.py:45-47): four small tensors
-        whose gradients autograd produces; each gets its own dclip_adamw launch (after an all-reduce of its gradient in a data-parallel
-        run whose exchange this package owns)."""
+        whose gradients autograd produces; they are updated together, like one more tower's ranges (after an all-reduce of each gradient
+        in a data-parallel run whose exchange this package owns)."""
         self.towers = list(towers)
         self.extras = [p for p in extra_params if p.requires_grad]
         self._extra_state = {}
@@ -92,28 +93,19 @@ class FusedAdamW:
     _coef = _coef_hip
 
     def _adamw_many(self, items, zero_grad, st, gscale=None):
-        """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE dclip_adamw_multi launch per 24 ranges (the sharded step has one
-        owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower)"""
-        import ctypes
+        """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE multi-range launch per ops.ADAMW_MAX_RANGES ranges (the sharded step
+        has one owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower).  A substituted
+        `_adamw`, an odd length or a misaligned pointer: one `_adamw` call per range."""
+        from . import ops
+        scale = () if gscale is None else (gscale,)
         if type(self)._adamw is not FusedAdamW._adamw_hip or any(p.numel() % 4 or (p.data_ptr() | g.data_ptr() | m.data_ptr() | v.data_ptr()) % 16
                                                                   for p, g, m, v in items):
             for p, g, m, v in items:
-                if gscale is None:
-                    self._adamw(p, g, m, v, zero_grad, st)
-                else:
-                    self._adamw(p, g, m, v, zero_grad, st, gscale)
+                self._adamw(p, g, m, v, zero_grad, st, *scale)
             return
-        for i in range(0, len(items), 24):
-            chunk = items[i:i + 24]
-            n = len(chunk)
-            arr = lambda k: (ctypes.c_void_p * n)(*[t[k].data_ptr() for t in chunk])
-            lens = (ctypes.c_int64 * n)(*[t[0].numel() for t in chunk])
-            if gscale is not None:
-                lib().dclip_adamw_multi_scaled(arr(0), arr(1), arr(2), arr(3), lens, n, self.lr, self.betas[0], self.betas[1], self.eps,
-                                               self.weight_decay, self.step_count, 1 if zero_grad else 0, gscale.data_ptr(), st)
-                continue
-            lib().dclip_adamw_multi(arr(0), arr(1), arr(2), arr(3), lens, n, self.lr, self.betas[0], self.betas[1], self.eps,
-                                    self.weight_decay, self.step_count, 1 if zero_grad else 0, st)
+        for i in range(0, len(items), ops.ADAMW_MAX_RANGES):
+            ops.adamw_multi_scaled(items[i:i + ops.ADAMW_MAX_RANGES], self.lr, self.betas, self.eps, self.weight_decay, self.step_count, zero_grad,
+                                   gscale, st)
 
     def zero_grad(self, set_to_none=False):
         from .model.component._tower import autograd_params_mode
@@ -220,6 +212,105 @@ class FusedAdamW:
             tw.opt_done.record(s)
         return s
 
+    def _jobs(self, overlap, main, clip):
+        """[(tower, stream, items, sharded)] of the materialised towers, in tower order: the stream the tower's update runs on and the
+        [(p, g, m, v)] ranges it updates (a sharded tower's: only for the sums of a clipping step, _step_sharded takes its own)"""
+        from .model.component._tower import autograd_params_mode
+        jobs = []
+        for tw in self.towers:
+            if tw.flat is None:
+                continue
+            m, v = self._moments(tw)
+            if self._sharded(tw):
+                jobs.append((tw, tw.sync.stream_for(tw.flat, tw), self._shard_items(tw, m, v) if clip else [], True))
+                continue
+            # (gradients that went through autograd may have been written by anybody's stream — a DDP reducer's —: take them on `main`)
+            stream = tw.bwd_stream if (overlap and not autograd_params_mode(tw) and getattr(tw, 'bwd_stream', None) is not None) else main
+            jobs.append((tw, stream, [(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)], False))
+        return jobs
+
+    def _await_grads(self, job, main):
+        """a tower that is not sharded: its stream waits for the caller's and for the tower's gradients, which then lie in flat_grad"""
+        from .model.component._tower import autograd_params_mode
+        from .parallel import GradSync
+        tw, stream = job[0], job[1]
+        if stream != main:
+            stream.wait_stream(main)                         # whatever the caller enqueued before step() (e.g. zero_grad of others)
+        if getattr(tw, 'grads_ready', None) is not None:
+            stream.wait_event(tw.grads_ready)                # this tower's gradient average (RCCL side stream), whichever stream updates
+            tw.grads_ready = None
+        if autograd_params_mode(tw):
+            with GradSync._On(stream):
+                self._pack_autograd_grads(tw)
+
+    def _update(self, job, zero_grad, overlap, main, coef=None):
+        """one tower's AdamW, on g * coef if given, and what follows it on the tower's stream.  Returns the stream the current one has
+        to join, None if there is none."""
+        from .parallel import GradSync
+        tw, stream, items, sharded = job
+        if sharded:
+            return self._step_sharded(tw, coef)              # (its exchange stream waits for the current one: the coefficient)
+        if coef is not None and stream != main:
+            stream.wait_stream(main)
+        with GradSync._On(stream):
+            self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef)
+            tw.wcache_dirty = True
+            tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
+            if overlap and self.refresh_cache_in_step:
+                tw._prepare_always = False                   # from now on this optimizer keeps the bf16 cache in step
+                tw.prepare()
+        if stream == main:
+            return None
+        tw.opt_done = torch.cuda.Event()
+        tw.opt_done.record(stream)
+        return stream
+
+    def _clip_coef(self, jobs, extras, main):
+        """max_grad_norm is set: (norm, coef) as two 1-element device tensors, ordered by events only:
+          1. every tower's sum of squared gradients, on the stream that tower's update runs on (behind its backward / exchange);
+          2. on the current stream, after all of them: the extras' sum, the cross-rank sum, ONE clip_coef -> (norm, coef).
+        The updates follow the coefficient and read it from the device.
+        Data-parallel: a sharded tower contributes the squares of this rank's owned slices of the averaged gradient (tw.gshard), so
+        those sums are added over the ranks (one all-reduce of one double); gradients every rank holds whole — the extras after
+        their all-reduce, a tower that is not sharded — are identical everywhere and enter once, as clip_coef's extra_sumsq.
+        Every rank computes the coefficient from the same bits in the same order: `jobs` has the sharded towers first."""
+        from . import ops
+        from .parallel import GradSync, all_reduce_sum
+        G, R = ops.SUMSQ_PARTIALS, ops.ADAMW_MAX_RANGES
+        slots = [G * ((len(j[2]) + R - 1) // R) for j in jobs] + [G * ((len(extras) + R - 1) // R)]
+        device = jobs[0][0].flat.device if jobs else self.extras[0].device
+        if self._clip_parts is None or self._clip_parts.numel() != max(sum(slots), 1) or self._clip_parts.device != device:
+            self._clip_parts = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
+        parts, out = self._clip_parts, self._clip_out
+        at = 0
+        for job, n in zip(jobs, slots):
+            tw, stream, items, sharded = job
+            if not sharded:
+                self._await_grads(job, main)
+            elif stream != main:
+                stream.wait_stream(main)
+            if items:
+                with GradSync._On(stream):
+                    self._sumsq([it[1] for it in items], parts[at:at + n], stream.cuda_stream if stream is not None else None)
+            if stream != main:
+                ev = torch.cuda.Event()
+                ev.record(stream)
+                main.wait_event(ev)
+            at += n
+        st = main.cuda_stream if main is not None else None
+        if extras:
+            self._sumsq([it[1] for it in extras], parts[at:at + slots[-1]], st)
+        n_sharded = sum(n for j, n in zip(jobs, slots) if j[3])
+        if any(j[3] for j in jobs):                          # (the same on every rank, whatever this rank owns)
+            total = parts[:n_sharded].sum(dtype=torch.float64).view(1)
+            all_reduce_sum(total)
+            rest = parts[n_sharded:sum(slots)]
+            self._coef(total.float(), rest.sum(dtype=torch.float64).float().view(1) if rest.numel() else None, out, st)
+        else:
+            self._coef(parts, None, out, st)
+        return out[0:1], out[1:2]
+
     @torch.no_grad()
     def step(self, zero_grad=False, overlap=False, join=True):
         """zero_grad=True: the kernel clears each gradient element once it has consumed it (saves the separate 306 MB fill that
@@ -233,140 +324,31 @@ class FusedAdamW:
         dependency (backward -> exchange -> update -> next forward of that tower) and the next step's frozen teacher towers
         may start while the last gradient exchange and update are still running; join() orders the current stream after them
         (zero_grad() and state_dict() call it)."""
-        from .model.component._tower import autograd_params_mode
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
         on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
         main = torch.cuda.current_stream() if on_gpu else None
-        if self.max_grad_norm is not None:
-            return self._step_clipped(zero_grad, overlap, join, main)
-        self.last_grad_norm = None
-        joined = []
-        for tw in self.towers:
-            if tw.flat is None:
-                continue
-            if self._sharded(tw):
-                s = self._step_sharded(tw)
-                if s is not None:
-                    joined.append(s)
-                continue
-            m, v = self._moments(tw)
-            through_autograd = autograd_params_mode(tw)
-            # (gradients that went through autograd may have been written by anybody's stream — a DDP reducer's —: take them on `main`)
-            stream = tw.bwd_stream if (overlap and not through_autograd and getattr(tw, 'bwd_stream', None) is not None) else main
-            if stream != main:
-                stream.wait_stream(main)                     # whatever the caller enqueued before step() (e.g. zero_grad of others)
-            if getattr(tw, 'grads_ready', None) is not None:
-                stream.wait_event(tw.grads_ready)            # this tower's gradient average (RCCL side stream), whichever stream updates
-                tw.grads_ready = None
-            with torch.cuda.stream(stream):
-                st = stream.cuda_stream
-                if through_autograd:
-                    self._pack_autograd_grads(tw)
-                self._adamw_many([(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)], zero_grad, st)
-                tw.wcache_dirty = True
-                tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
-                if overlap and self.refresh_cache_in_step:
-                    tw._prepare_always = False               # from now on this optimizer keeps the bf16 cache in step
-                    tw.prepare()
-            if stream != main:
-                joined.append(stream)
-                tw.opt_done = torch.cuda.Event()
-                tw.opt_done.record(stream)
-        self._step_extras(zero_grad, main)
-        if join:
-            for stream in joined:
-                main.wait_stream(stream)
-            for tw in self.towers:
-                tw.opt_done = None
-
-    def _step_clipped(self, zero_grad, overlap, join, main):
-        """step() with max_grad_norm set.  Three phases, ordered by events only:
-          1. every tower's sum of squared gradients, on the stream that tower's update runs on (behind its backward / exchange);
-          2. on the current stream, after all of them: the extras' sum, the cross-rank sum, ONE clip_coef -> (norm, coef);
-          3. every update, after the coefficient, reading it from the device.
-        Data-parallel: a sharded tower contributes the squares of this rank's owned slices of the averaged gradient (tw.gshard), so
-        those sums are added over the ranks (one all-reduce of one double); gradients every rank holds whole — the extras after
-        their all-reduce, a tower that is not sharded — are identical everywhere and enter once, as clip_coef's extra_sumsq.
-        Every rank computes the coefficient from the same bits in the same order."""
-        from . import ops
-        from .model.component._tower import autograd_params_mode
-        from .parallel import GradSync, all_reduce_sum
-        G, R = ops.SUMSQ_PARTIALS, ops.ADAMW_MAX_RANGES
-        towers = [tw for tw in self.towers if tw.flat is not None]
-        jobs = []                                                # [tower, stream, items, sharded]
-        for tw in towers:
-            m, v = self._moments(tw)
-            if self._sharded(tw):
-                jobs.append([tw, tw.sync.stream_for(tw.flat, tw), self._shard_items(tw, m, v), True])
-                continue
-            stream = tw.bwd_stream if (overlap and not autograd_params_mode(tw) and getattr(tw, 'bwd_stream', None) is not None) else main
-            jobs.append([tw, stream, [(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)], False])
-        jobs.sort(key=lambda j: not j[3])                        # (stable) the sharded towers' partial sums lie first
-        extras = self._extra_items()
-        slots = [G * ((len(j[2]) + R - 1) // R) for j in jobs] + [G * ((len(extras) + R - 1) // R)]
-        device = towers[0].flat.device if towers else self.extras[0].device
-        if self._clip_parts is None or self._clip_parts.numel() != max(sum(slots), 1) or self._clip_parts.device != device:
-            self._clip_parts = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
-            self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
-        parts, out = self._clip_parts, self._clip_out
-        # ---- 1. sums
-        at = 0
-        for (tw, stream, items, sharded), n in zip(jobs, slots):
-            if stream is not None and stream != main:
-                stream.wait_stream(main)                         # whatever the caller enqueued before step() (see step / _step_sharded)
-            if not sharded and getattr(tw, 'grads_ready', None) is not None:
-                stream.wait_event(tw.grads_ready)
-                tw.grads_ready = None
-            with GradSync._On(stream):
-                if not sharded and autograd_params_mode(tw):
-                    self._pack_autograd_grads(tw)
-                if items:
-                    self._sumsq([it[1] for it in items], parts[at:at + n], stream.cuda_stream if stream is not None else None)
-            if stream is not None and stream != main:
-                ev = torch.cuda.Event()
-                ev.record(stream)
-                main.wait_event(ev)
-            at += n
-        # ---- 2. one coefficient
-        st = main.cuda_stream if main is not None else None
-        if extras:
-            self._sumsq([it[1] for it in extras], parts[at:at + slots[-1]], st)
-        n_sharded = sum(n for j, n in zip(jobs, slots) if j[3])
-        if any(j[3] for j in jobs):
-            total = parts[:n_sharded].sum(dtype=torch.float64).view(1)
-            all_reduce_sum(total)
-            rest = parts[n_sharded:sum(slots)]
-            self._coef(total.float(), rest.sum(dtype=torch.float64).float().view(1) if rest.numel() else None, out, st)
+        jobs = self._jobs(overlap, main, self.max_grad_norm is not None)
+        if self.max_grad_norm is None:
+            self.last_grad_norm = coef = None
+            joined = []
+            for job in jobs:                                 # tower by tower
+                if not job[3]:
+                    self._await_grads(job, main)
+                joined.append(self._update(job, zero_grad, overlap, main))
+            extras = self._extra_items()
         else:
-            self._coef(parts, None, out, st)
-        self.last_grad_norm, coef = out[0:1], out[1:2]
-        # ---- 3. updates
-        joined = []
-        for tw, stream, items, sharded in jobs:
-            if sharded:
-                s = self._step_sharded(tw, coef)                 # (its exchange stream waits for the current one: the coefficient)
-                if s is not None:
-                    joined.append(s)
-                continue
-            if stream is not None and stream != main:
-                stream.wait_stream(main)
-            with GradSync._On(stream):
-                self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef)
-                tw.wcache_dirty = True
-                tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
-                if overlap and self.refresh_cache_in_step:
-                    tw._prepare_always = False
-                    tw.prepare()
-            if stream is not None and stream != main:
-                joined.append(stream)
-                tw.opt_done = torch.cuda.Event()
-                tw.opt_done.record(stream)
+            jobs.sort(key=lambda j: not j[3])                # (stable) the sharded towers' partial sums lie first
+            extras = self._extra_items()
+            self.last_grad_norm, coef = self._clip_coef(jobs, extras, main)
+            joined = [self._update(job, zero_grad, overlap, main, coef) for job in jobs]
         if extras:
-            self._adamw_many(extras, zero_grad, st, coef)
+            # the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)
+            self._adamw_many(extras, zero_grad, main.cuda_stream if main is not None else None, coef)
         if join:
             for stream in joined:
-                main.wait_stream(stream)
+                if stream is not None:
+                    main.wait_stream(stream)
             for tw in self.towers:
                 tw.opt_done = None
 
@@ -376,12 +358,6 @@ class FusedAdamW:
             st = self._extra_state[id(p)] = (torch.zeros(p.numel(), dtype=torch.float32, device=p.device),
                                              torch.zeros(p.numel(), dtype=torch.float32, device=p.device))
         return st
-
-    def _step_extras(self, zero_grad, main):
-        """the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)"""
-        items = self._extra_items()
-        if items:
-            self._adamw_many(items, zero_grad, main.cuda_stream if main is not None else None)
 
     def _extra_items(self):
         """[(p, g, m, v)] of the extras that have a gradient, the gradients averaged over the ranks"""

@@ -301,3 +301,77 @@ def test_sharded_clipped_step_world2_equals_clip_grad_norm_on_the_averaged_gradi
         assert torch.equal(flat[~mask], ref.flat[~mask])
         for a, b in zip(got_extras, extras):
             assert torch.allclose(a, b.detach(), rtol=1e-5, atol=1e-6), rank
+
+
+def test_a_tower_that_is_not_sharded_steps_unclipped_on_the_cpu_like_torch_adamw():
+    """one process, no exchange, no clipping: step() takes the tower's ranges from flat_grad on the caller's (here: no) stream"""
+    gen = torch.Generator().manual_seed(5)
+    tw = _FakeTower(16 * 8 + 16 + 16, [(0, 16 * 8 + 16 + 16)], [[0, 16 * 8], [16 * 8 + 16, 16 * 8 + 32]], seed=4)
+    before = tw.flat.clone()
+    ref = [torch.nn.Parameter(tw.flat[a:b].clone()) for a, b in tw.trainable_ranges()]
+    opt = _rehearsal_optimizer()([tw], lr=1e-2, weight_decay=1e-2)
+    topt = torch.optim.AdamW(ref, lr=1e-2, weight_decay=1e-2)
+    for step in range(3):
+        for q, (a, b) in zip(ref, tw.trainable_ranges()):
+            q.grad = torch.randn(b - a, generator=gen)
+            tw.flat_grad[a:b] = q.grad
+        opt.step(zero_grad=True)
+        topt.step()
+        assert opt.last_grad_norm is None
+        for q, (a, b) in zip(ref, tw.trainable_ranges()):
+            assert torch.allclose(tw.flat[a:b], q.detach(), rtol=1e-5, atol=1e-6), step
+            assert not tw.flat_grad[a:b].any()                    # consumed and cleared
+    assert torch.equal(tw.flat[16 * 8:16 * 8 + 16], before[16 * 8:16 * 8 + 16])      # the frozen range
+    assert tw.wcache_dirty and not tw._grad_clean                 # two ranges: not the whole buffer
+
+
+# one bucket whose trainable part lies in rank 0's half: rank 1 owns no slice, and still takes part in the sum over the ranks
+_HALF_TOTAL, _HALF_TRAINABLE = 64 * 4, [[0, 64 * 2]]
+
+
+def _half_grad(step, rank):
+    g = torch.zeros(_HALF_TOTAL)
+    g[:64 * 2] = torch.randn(64 * 2, generator=torch.Generator().manual_seed(300 + 10 * step + rank))
+    return g
+
+
+def _half_owner_worker(rank, world, rdzv, q):
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group('gloo', init_method='file://' + rdzv, rank=rank, world_size=world)
+    from distillclip_amd.parallel import GradSync
+    tw = _FakeTower(_HALF_TOTAL, [(0, _HALF_TOTAL)], _HALF_TRAINABLE, seed=9)
+    sync = GradSync()
+    sync.attach([tw])
+    opt = _rehearsal_optimizer()([tw], lr=1e-2, weight_decay=1e-2, max_grad_norm=_MAX_NORM)
+    outs = []
+    for step in range(2):
+        tw.flat_grad.add_(_half_grad(step, rank))
+        sync.bucket_ready(tw, 0)
+        sync.finish(tw)
+        opt.step()
+        outs.append(opt._clip_out.clone())
+        opt.zero_grad()
+    q.put((rank, tw.flat.clone(), torch.stack(outs), len(opt._shard_items(tw, *opt._moments(tw)))))
+    dist.monitored_barrier()
+    dist.destroy_process_group()
+
+
+def test_a_rank_that_owns_no_trainable_slice_still_gets_the_global_coefficient():
+    world = 2
+    res = sorted(_run_ranks(_half_owner_worker, world, timeout=120), key=lambda r: r[0])
+    assert [r[3] for r in res] == [1, 0]                              # the layout does what the test is about
+    assert torch.equal(res[0][2].view(torch.int32), res[1][2].view(torch.int32))
+    assert torch.equal(res[0][1].view(torch.int32), res[1][1].view(torch.int32))
+    ref = _FakeTower(_HALF_TOTAL, [(0, _HALF_TOTAL)], _HALF_TRAINABLE, seed=9)
+    chunk = torch.nn.Parameter(ref.flat[:64 * 2].clone())
+    topt = torch.optim.AdamW([chunk], lr=1e-2, weight_decay=1e-2)
+    for step in range(2):
+        chunk.grad = (sum(_half_grad(step, r) for r in range(world)) / world)[:64 * 2].clone()
+        G = float(chunk.grad.double().norm())
+        norm, coef = (float(x) for x in res[0][2][step])
+        assert abs(norm - G) <= 2.0 ** -22 * G and G > _MAX_NORM and abs(coef - _MAX_NORM / (G + 1e-6)) <= 1e-6
+        torch.nn.utils.clip_grad_norm_([chunk], _MAX_NORM)
+        topt.step()
+    for r in res:
+        assert torch.allclose(r[1][:64 * 2], chunk.detach(), rtol=1e-5, atol=1e-6), r[0]
+        assert torch.equal(r[1][64 * 2:], ref.flat[64 * 2:])

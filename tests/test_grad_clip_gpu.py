@@ -1,8 +1,8 @@
-"""Global gradient-norm clipping inside the fused AdamW step: dclip_sumsq_multi + dclip_clip_coef (csrc/gradnorm.hip),
-dclip_adamw_multi_scaled (csrc/elementwise.hip), FusedAdamW(max_grad_norm=...).  Semantics: torch.nn.utils.clip_grad_norm_(params, c)
+"""Global gradient-norm clipping inside the fused AdamW step: dclip_sumsq_multi + dclip_clip_coef,
+dclip_adamw_multi_scaled (csrc/optim.hip), FusedAdamW(max_grad_norm=...).  Semantics: torch.nn.utils.clip_grad_norm_(params, c)
 followed by torch.optim.AdamW.step(), with norm and coefficient staying on the device.
 
-Kernel constants the probes straddle (csrc/gradnorm.hip): a lane loads LANE = 4 elements (one float4) at a time, the workgroup's 256 lanes
+Kernel constants the probes straddle (csrc/optim.hip): a lane loads LANE = 4 elements (one float4) at a time, the workgroup's 256 lanes
 one ROW = 1024 elements per load, SUMSQ_LOADS = 8 loads make a workgroup TILE = 8192 elements, and a launch has PARTIALS = 1024 workgroups
 (DCLIP_SUMSQ_PARTIALS), so a workgroup meets a second tile only past PARTIALS * TILE elements.  The kernel documents the longest serial
 f32 accumulation chain as L = 8 (SUMSQ_LOADS).
