@@ -1,6 +1,8 @@
 // The optimizer step's device code.  Global gradient norm for clipping (include/dclip.h: dclip_sumsq_multi, dclip_clip_coef):
 // torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) with the norm and the coefficient staying on the device.  AdamW
 // (dclip_adamw, dclip_adamw_multi, dclip_adamw_multi_scaled): torch.optim.AdamW on f32 ranges, optionally on g * that coefficient.
+// Under a loss scaler (dclip_amp_prepare, dclip_adamw_multi_amp): the same step driven by a device record that also carries the
+// scaler's 1 / scale, its overflow flag and the bias corrections of the steps that were not skipped.
 #include "common.h"
 
 #include <math.h>
@@ -66,25 +68,76 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(SumsqRanges r, int cou
         for (int64_t i = (int64_t)gridDim.x + threadIdx.x; i < n_partials; i += 256) partials[i] = 0.f;
 }
 
-// One workgroup.  Lane t adds the slots t, t + 256, ... in rising index order, the 256 lane sums meet in a fixed tree: all in
-// double, where the order of at most a few thousand non-negative f32 terms moves the sum by parts in 2^-40 — nothing the f32
-// results can show — and a fixed order gives every call (and every rank of a data-parallel run) the same bits.
-__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, int64_t n_partials, const float* __restrict__ extra_sumsq,
-                                                        float max_norm, float* __restrict__ out) {
-    __shared__ double wave_part[4];
+// One workgroup's sum of the partials, valid in lane 0.  Lane t adds the slots t, t + 256, ... in rising index order, the 256 lane
+// sums meet in a fixed tree: all in double, where the order of at most a few thousand non-negative f32 terms moves the sum by parts
+// in 2^-40 — nothing the f32 results can show — and a fixed order gives every call (and every rank of a data-parallel run) the same bits.
+__device__ __forceinline__ double sum_partials(const float* __restrict__ partials, int64_t n_partials, double* wave_part) {
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n_partials; i += 256) acc += (double)partials[i];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
     __syncthreads();
+    return ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
+}
+
+__device__ __forceinline__ float clip_coef_of(float max_norm, float norm) {
+    const float c = max_norm / (norm + 1e-6f);
+    return c > 1.f ? 1.f : c;                            // (a NaN stays a NaN, like torch.clamp(max=1))
+}
+
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, int64_t n_partials, const float* __restrict__ extra_sumsq,
+                                                        float max_norm, float* __restrict__ out) {
+    __shared__ double wave_part[4];
+    double sum = sum_partials(partials, n_partials, wave_part);
     if (threadIdx.x == 0) {
-        double sum = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
         if (extra_sumsq) sum += (double)*extra_sumsq;
         const float norm = (float)sqrt(sum);
-        const float c = max_norm / (norm + 1e-6f);
         out[0] = norm;
-        out[1] = c > 1.f ? 1.f : c;                      // (a NaN stays a NaN, like torch.clamp(max=1))
+        out[1] = clip_coef_of(max_norm, norm);
+    }
+}
+
+// beta^t for the host's powf(beta, (float)t) (adamw_multi_launch): square-and-multiply in double (a relative error below
+// 2 * 24 * 2^-53 for t < 2^24, far inside the half-ulp of the f32 it is rounded to), i.e. the correctly rounded f32.  The host's powf
+// is within 0.52 ulp of that: the bias corrections agree bit for bit except for a rare last bit (DESIGN.md section 7.0 counts them).
+__device__ __forceinline__ float powf_int(float beta, int64_t t) {
+    double b = (double)beta, r = 1.0;
+    for (uint64_t e = t > 0 ? (uint64_t)(float)t : 0; e; e >>= 1) {  // ((float)t: the host's rounding of a step past 2^24)
+        if (e & 1) r *= b;
+        b *= b;
+    }
+    return (float)r;
+}
+
+// One workgroup: what the AdamW kernels of a step under a loss scaler read (include/dclip.h: dclip_amp_prepare).  clip_coef_kernel
+// with the scaler's two tensors folded in: the norm is that of the unscaled gradients, the multiplier carries coefficient and
+// 1 / scale in one f32, and a step that found an overflow is counted, so that the bias corrections are those of the steps taken.
+__global__ __launch_bounds__(256) void amp_prepare_kernel(const float* __restrict__ found_inf, const float* __restrict__ grad_scale,
+                                                          const float* __restrict__ partials, int64_t n_partials,
+                                                          const float* __restrict__ extra_sumsq, float max_norm, float b1, float b2,
+                                                          int64_t step, int64_t* __restrict__ skipped, float* __restrict__ rec) {
+    __shared__ double wave_part[4];
+    double sum = sum_partials(partials, n_partials, wave_part);      // (no clipping: n_partials = 0)
+    if (threadIdx.x == 0) {
+        const float gs = grad_scale ? *grad_scale : 1.f;
+        const bool skip = found_inf && *found_inf != 0.f;
+        float norm = 0.f, coef = 1.f;
+        if (partials) {
+            if (extra_sumsq) sum += (double)*extra_sumsq;
+            norm = (float)(sqrt(sum) / (double)gs);
+            coef = clip_coef_of(max_norm, norm);
+        }
+        const int64_t gone = *skipped + (skip ? 1 : 0);
+        *skipped = gone;
+        const int64_t t = step - gone;                               // (>= 1 on every step that is not skipped)
+        rec[DCLIP_AMP_MULT] = coef / gs;
+        rec[DCLIP_AMP_SKIP] = skip ? 1.f : 0.f;
+        rec[DCLIP_AMP_BC1] = 1.f - powf_int(b1, t);
+        rec[DCLIP_AMP_BC2_SQRT] = sqrtf(1.f - powf_int(b2, t));
+        rec[DCLIP_AMP_NORM] = norm;
+        rec[DCLIP_AMP_COEF] = coef;
+        rec[6] = rec[7] = 0.f;
     }
 }
 
@@ -118,16 +171,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 // The loads of the next grid-stride iteration are issued before the stores of the current one: vmcnt retires loads and stores in
 // one in-order queue, so loads that follow stores wait for the stores' acknowledgements as well.
 struct AdamwRanges { float4* p[DCLIP_ADAMW_MAX_RANGES]; float4* g[DCLIP_ADAMW_MAX_RANGES]; float4* m[DCLIP_ADAMW_MAX_RANGES]; float4* v[DCLIP_ADAMW_MAX_RANGES]; int64_t n4[DCLIP_ADAMW_MAX_RANGES]; };
-template <bool SCALED>
+// AMP: gscale points at the record of amp_prepare_kernel, whose first four floats (multiplier, skip flag, the two bias corrections:
+// one 16-byte load, the same for every lane) take the place of *gscale, bc1 and bc2_sqrt.  A skipped step writes no p, m or v and
+// reads nothing; the gradients, which hold an overflow, are still cleared on request.
+enum AdamwMode { ADAMW_PLAIN = 0, ADAMW_SCALED = 1, ADAMW_AMP = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void adamw4_multi_kernel(AdamwRanges r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
                                                            int zero_grad, const float* __restrict__ gscale) {
+    constexpr bool SCALED = MODE != ADAMW_PLAIN;
     const int k = blockIdx.y;
     float4* __restrict__ p = r.p[k]; float4* __restrict__ g = r.g[k]; float4* __restrict__ m = r.m[k]; float4* __restrict__ v = r.v[k];
     const int64_t n4 = r.n4[k];
     const int64_t stride = (int64_t)gridDim.x * 256;
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
-    const float gs = SCALED ? *gscale : 1.f;
+    float gs = MODE == ADAMW_SCALED ? *gscale : 1.f;
+    if constexpr (MODE == ADAMW_AMP) {
+        const float4 c = *(const float4*)gscale;
+        if (c.y != 0.f) {
+            if (zero_grad)
+                for (; i < n4; i += stride) g[i] = float4{0.f, 0.f, 0.f, 0.f};
+            return;
+        }
+        gs = c.x; bc1 = c.z; bc2_sqrt = c.w;
+    }
     float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
     for (;;) {
         const int64_t nx = i + stride;
@@ -146,10 +213,10 @@ __global__ __launch_bounds__(256) void adamw4_multi_kernel(AdamwRanges r, float 
     }
 }
 
-int adamw_multi_launch(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, const float* gscale, void* stream) {
-    DCLIP_REQUIRE(p && g && m && v && n && count > 0 && count <= DCLIP_ADAMW_MAX_RANGES && step >= 1, "%s: bad argument (1..%d ranges)", what, DCLIP_ADAMW_MAX_RANGES);
-    AdamwRanges r;
+// the ranges of a multi-range launch, checked, and its grid
+int adamw_ranges(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, AdamwRanges& r,
+                 dim3& grid) {
+    DCLIP_REQUIRE(p && g && m && v && n && count > 0 && count <= DCLIP_ADAMW_MAX_RANGES, "%s: bad argument (1..%d ranges)", what, DCLIP_ADAMW_MAX_RANGES);
     int64_t longest = 0;
     for (int k = 0; k < count; ++k) {
         DCLIP_REQUIRE(p[k] && g[k] && m[k] && v[k] && n[k] > 0 && n[k] % 4 == 0 && ((((uintptr_t)p[k] | (uintptr_t)g[k] | (uintptr_t)m[k] | (uintptr_t)v[k]) & 15) == 0),
@@ -157,11 +224,21 @@ int adamw_multi_launch(const char* what, float* const* p, float* const* g, float
         r.p[k] = (float4*)p[k]; r.g[k] = (float4*)g[k]; r.m[k] = (float4*)m[k]; r.v[k] = (float4*)v[k]; r.n4[k] = n[k] / 4;
         longest = r.n4[k] > longest ? r.n4[k] : longest;
     }
+    const int per_range = 8192 / count < 256 ? 256 : 8192 / count;          // (grid-stride loop: the longest range sets the width, capped)
+    grid = dim3(grid_for(longest, 256, per_range), (unsigned)count);
+    return DCLIP_OK;
+}
+
+int adamw_multi_launch(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, const float* gscale, void* stream) {
+    DCLIP_REQUIRE(step >= 1, "%s: bad argument (step >= 1)", what);
+    AdamwRanges r;
+    dim3 grid;
+    const int rc = adamw_ranges(what, p, g, m, v, n, count, r, grid);
+    if (rc != DCLIP_OK) return rc;
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
-    const int per_range = 8192 / count < 256 ? 256 : 8192 / count;          // (grid-stride loop: the longest range sets the width, capped)
-    const dim3 grid(grid_for(longest, 256, per_range), (unsigned)count);
-    hipLaunchKernelGGL(gscale ? adamw4_multi_kernel<true> : adamw4_multi_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps,
+    hipLaunchKernelGGL(gscale ? adamw4_multi_kernel<ADAMW_SCALED> : adamw4_multi_kernel<ADAMW_PLAIN>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps,
                        weight_decay, bc1, bc2, zero_grad, gscale);
     return dclip_check_launch(what);
 }
@@ -200,6 +277,28 @@ extern "C" int dclip_adamw_multi_scaled(float* const* p, float* const* g, float*
                                         float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad,
                                         const float* gscale, void* stream) {
     return adamw_multi_launch("dclip_adamw_multi_scaled", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, gscale, stream);
+}
+
+extern "C" int dclip_amp_prepare(const float* found_inf, const float* grad_scale, const float* partials, int64_t n_partials, const float* extra_sumsq,
+                                 float max_norm, float beta1, float beta2, int64_t step, int64_t* skipped, float* record, void* stream) {
+    DCLIP_REQUIRE(record && ((uintptr_t)record & 15) == 0 && skipped && ((uintptr_t)skipped & 7) == 0 && step >= 1,
+                  "dclip_amp_prepare: bad argument (a 16-byte aligned record, an 8-byte aligned counter, step >= 1)");
+    DCLIP_REQUIRE(partials ? n_partials > 0 : (n_partials == 0 && !extra_sumsq), "dclip_amp_prepare: partials and n_partials come together, extra_sumsq only with them");
+    hipLaunchKernelGGL(amp_prepare_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, found_inf, grad_scale, partials, n_partials, extra_sumsq, max_norm,
+                       beta1, beta2, step, skipped, record);
+    return dclip_check_launch("dclip_amp_prepare");
+}
+
+extern "C" int dclip_adamw_multi_amp(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int zero_grad, const float* record, void* stream) {
+    DCLIP_REQUIRE(record && ((uintptr_t)record & 15) == 0, "dclip_adamw_multi_amp: bad argument (a 16-byte aligned record of dclip_amp_prepare)");
+    AdamwRanges r;
+    dim3 grid;
+    const int rc = adamw_ranges("dclip_adamw_multi_amp", p, g, m, v, n, count, r, grid);
+    if (rc != DCLIP_OK) return rc;
+    hipLaunchKernelGGL(adamw4_multi_kernel<ADAMW_AMP>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f,
+                       zero_grad, record);
+    return dclip_check_launch("dclip_adamw_multi_amp");
 }
 
 extern "C" int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

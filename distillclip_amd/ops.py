@@ -321,3 +321,35 @@ def adamw_multi_scaled(items, lr, betas, eps, weight_decay, step, zero_grad=Fals
     lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
     lib().dclip_adamw_multi_scaled(arr(0), arr(1), arr(2), arr(3), lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
                                    1 if zero_grad else 0, _p(gscale), _stream() if stream is None else stream)
+
+
+AMP_RECORD_FLOATS = 8      # DCLIP_AMP_RECORD_FLOATS
+AMP_MULT, AMP_SKIP, AMP_BC1, AMP_BC2_SQRT, AMP_NORM, AMP_COEF = range(6)      # DCLIP_AMP_*
+
+
+def amp_prepare(record, skipped, betas, step, found_inf=None, grad_scale=None, partials=None, max_norm=0.0, extra_sumsq=None, stream=None):
+    """record (8 f32) <- the control record of a step under a loss scaler, skipped (1 int64) += (found_inf != 0): multiplier coef / grad_scale,
+    skip flag, the bias corrections of step - skipped, and with `partials` (of sumsq_multi) the unscaled norm and its clipping coefficient
+    (include/dclip.h: dclip_amp_prepare).  found_inf, grad_scale: 1-element f32 device tensors or None."""
+    _chk(record, skipped, found_inf, grad_scale, partials, extra_sumsq)
+    for t in (found_inf, grad_scale):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+            raise ValueError('amp_prepare: found_inf and grad_scale are 1-element f32 tensors')
+    if record.dtype != torch.float32 or record.numel() < AMP_RECORD_FLOATS or skipped.dtype != torch.int64:
+        raise ValueError('amp_prepare: record is %d f32, skipped one int64' % AMP_RECORD_FLOATS)
+    lib().dclip_amp_prepare(_p(found_inf), _p(grad_scale), _p(partials), 0 if partials is None else partials.numel(), _p(extra_sumsq), float(max_norm),
+                            betas[0], betas[1], step, _p(skipped), _p(record), _stream() if stream is None else stream)
+    return record
+
+
+def adamw_multi_amp(items, lr, betas, eps, weight_decay, zero_grad, record, stream=None):
+    """adamw_multi_scaled with multiplier, skip flag and bias corrections read from `record` of amp_prepare (include/dclip.h: dclip_adamw_multi_amp)"""
+    import ctypes
+    for it in items:
+        _chk(*it)
+    _chk(record)
+    n = len(items)
+    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items])
+    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
+    lib().dclip_adamw_multi_amp(arr(0), arr(1), arr(2), arr(3), lens, n, lr, betas[0], betas[1], eps, weight_decay, 1 if zero_grad else 0,
+                                _p(record), _stream() if stream is None else stream)

@@ -30,8 +30,21 @@ class FusedAdamW:
     exactly the parameters this optimizer was built over, like torch.nn.utils.clip_grad_norm_(params, max_grad_norm) before
     torch.optim.AdamW.step(): coef = min(1, max_grad_norm / (norm + 1e-6)) and the update uses g * coef.  Norm and coefficient
     stay on the device (no host synchronisation); last_grad_norm is a 1-element device tensor holding the norm after step(), None
-    while clipping is off.  A non-finite norm is not special-cased: coef and the update become NaN, as in torch.  Gradients
-    scaled by a loss scaler (precision: 16) must be unscaled before step().  Not optimizer state: state_dict() does not carry it."""
+    while clipping is off.  A non-finite norm is not special-cased: coef and the update become NaN, as in torch.  Not optimizer
+    state: state_dict() does not carry it.
+
+    Under a loss scaler (precision: 16) this is an optimizer torch.amp.GradScaler.step() drives directly (_step_supports_amp_scaling):
+    the scaler sets the device tensors `grad_scale` (None after scaler.unscale_(opt)) and `found_inf` on the optimizer just before
+    step() and deletes them after it.  One preparation kernel (dclip_amp_prepare) then turns them, and the sums of a clipping
+    step, into a device record every update of the step reads (dclip_adamw_multi_amp): the update uses g * coef / grad_scale, the
+    threshold is compared with the norm of the unscaled gradients (last_grad_norm shows that norm), and with found_inf set no
+    parameter and no moment is written, on the device, without a host synchronisation.  A skipped step is counted on the device
+    and does not advance the bias corrections (t = step_count - skipped); state_dict() writes that t.  The gradients themselves
+    are consumed as they are: p.grad is not written back unscaled (torch's fused AdamW does that).  Once steps have been taken
+    through a scaler, keep stepping through it: a plain step() takes its bias corrections from step_count alone.  Not with the
+    sharded data-parallel exchange: there p.grad holds zeros when the scaler looks for overflows, so step() refuses."""
+
+    _step_supports_amp_scaling = True
 
     def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None):
         """extra_params: trainable parameters that live outside the towers' flat buffers — the embedding_projection / hidden_projection
@@ -55,6 +68,7 @@ class FusedAdamW:
         self.max_grad_norm = max_grad_norm
         self.last_grad_norm = None
         self._clip_parts = self._clip_out = None
+        self._amp_rec = self._skipped = None               # the scaler-driven step's device record and its count of skipped steps
 
     def _ranges(self, tw):
         """contiguous [begin, end) element ranges of the parameters this optimizer was built over"""
@@ -92,11 +106,35 @@ class FusedAdamW:
 
     _coef = _coef_hip
 
-    def _adamw_many(self, items, zero_grad, st, gscale=None):
+    def _prepare_hip(self, found_inf, grad_scale, partials, extra, record, skipped, st):
+        """record <- this step's control record, skipped += (found_inf != 0) (ops.amp_prepare); partials None: the step does not clip.
+        (`_prepare` and `_adamw_amp` can be substituted by torch versions like `_adamw`.)"""
+        from . import ops
+        ops.amp_prepare(record, skipped, self.betas, self.step_count, found_inf, grad_scale, partials,
+                        0.0 if partials is None else self.max_grad_norm, extra, st)
+
+    _prepare = _prepare_hip
+
+    def _adamw_amp_hip(self, p, g, m, v, zero_grad, st, record):
+        from . import ops
+        ops.adamw_multi_amp([(p, g, m, v)], self.lr, self.betas, self.eps, self.weight_decay, zero_grad, record, st)
+
+    _adamw_amp = _adamw_amp_hip
+
+    def _adamw_many(self, items, zero_grad, st, gscale=None, record=None):
         """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE multi-range launch per ops.ADAMW_MAX_RANGES ranges (the sharded step
         has one owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower).  A substituted
-        `_adamw`, an odd length or a misaligned pointer: one `_adamw` call per range."""
+        `_adamw`, an odd length or a misaligned pointer: one `_adamw` call per range.  record: the scaler-driven step, every range reads
+        that record instead (an odd length or a misaligned pointer is refused by the kernel's entry)."""
         from . import ops
+        if record is not None:
+            if type(self)._adamw_amp is not FusedAdamW._adamw_amp_hip:
+                for p, g, m, v in items:
+                    self._adamw_amp(p, g, m, v, zero_grad, st, record)
+                return
+            for i in range(0, len(items), ops.ADAMW_MAX_RANGES):
+                ops.adamw_multi_amp(items[i:i + ops.ADAMW_MAX_RANGES], self.lr, self.betas, self.eps, self.weight_decay, zero_grad, record, st)
+            return
         scale = () if gscale is None else (gscale,)
         if type(self)._adamw is not FusedAdamW._adamw_hip or any(p.numel() % 4 or (p.data_ptr() | g.data_ptr() | m.data_ptr() | v.data_ptr()) % 16
                                                                   for p, g, m, v in items):
@@ -243,17 +281,17 @@ class FusedAdamW:
             with GradSync._On(stream):
                 self._pack_autograd_grads(tw)
 
-    def _update(self, job, zero_grad, overlap, main, coef=None):
-        """one tower's AdamW, on g * coef if given, and what follows it on the tower's stream.  Returns the stream the current one has
-        to join, None if there is none."""
+    def _update(self, job, zero_grad, overlap, main, coef=None, record=None):
+        """one tower's AdamW, on g * coef if given or driven by the scaler's record, and what follows it on the tower's stream.  Returns
+        the stream the current one has to join, None if there is none."""
         from .parallel import GradSync
         tw, stream, items, sharded = job
         if sharded:
             return self._step_sharded(tw, coef)              # (its exchange stream waits for the current one: the coefficient)
-        if coef is not None and stream != main:
+        if (coef is not None or record is not None) and stream != main:
             stream.wait_stream(main)
         with GradSync._On(stream):
-            self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef)
+            self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef, record)
             tw.wcache_dirty = True
             tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
             if overlap and self.refresh_cache_in_step:
@@ -265,11 +303,13 @@ class FusedAdamW:
         tw.opt_done.record(stream)
         return stream
 
-    def _clip_coef(self, jobs, extras, main):
+    def _clip_coef(self, jobs, extras, main, amp=None):
         """max_grad_norm is set: (norm, coef) as two 1-element device tensors, ordered by events only:
           1. every tower's sum of squared gradients, on the stream that tower's update runs on (behind its backward / exchange);
           2. on the current stream, after all of them: the extras' sum, the cross-rank sum, ONE clip_coef -> (norm, coef).
         The updates follow the coefficient and read it from the device.
+        amp = (found_inf, grad_scale), the scaler-driven step: 2. ends in ONE amp_prepare instead, which forms the coefficient from
+        the unscaled norm -> (norm, record).
         Data-parallel: a sharded tower contributes the squares of this rank's owned slices of the averaged gradient (tw.gshard), so
         those sums are added over the ranks (one all-reduce of one double); gradients every rank holds whole — the extras after
         their all-reduce, a tower that is not sharded — are identical everywhere and enter once, as clip_coef's extra_sumsq.
@@ -301,6 +341,8 @@ class FusedAdamW:
         st = main.cuda_stream if main is not None else None
         if extras:
             self._sumsq([it[1] for it in extras], parts[at:at + slots[-1]], st)
+        if amp is not None:
+            return self._amp_record(*amp, parts, st)
         n_sharded = sum(n for j, n in zip(jobs, slots) if j[3])
         if any(j[3] for j in jobs):                          # (the same on every rank, whatever this rank owns)
             total = parts[:n_sharded].sum(dtype=torch.float64).view(1)
@@ -310,6 +352,19 @@ class FusedAdamW:
         else:
             self._coef(parts, None, out, st)
         return out[0:1], out[1:2]
+
+    def _amp_record(self, found_inf, grad_scale, partials, st):
+        """ONE preparation launch on the current stream -> (norm or None, record).  The record of the step before may still be read by a
+        tower's un-joined update, which this launch must not overtake: the current stream waits for those first."""
+        from . import ops
+        self.join()
+        if self._amp_rec is None:
+            dev = found_inf.device if found_inf is not None else grad_scale.device
+            self._amp_rec = torch.zeros(ops.AMP_RECORD_FLOATS, dtype=torch.float32, device=dev)
+            self._skipped = torch.zeros(1, dtype=torch.int64, device=dev)
+        one = lambda t: None if t is None else t.detach().reshape(1)
+        self._prepare(one(found_inf), one(grad_scale), partials, None, self._amp_rec, self._skipped, st)
+        return (None if partials is None else self._amp_rec[ops.AMP_NORM:ops.AMP_NORM + 1]), self._amp_rec
 
     @torch.no_grad()
     def step(self, zero_grad=False, overlap=False, join=True):
@@ -324,27 +379,40 @@ class FusedAdamW:
         dependency (backward -> exchange -> update -> next forward of that tower) and the next step's frozen teacher towers
         may start while the last gradient exchange and update are still running; join() orders the current stream after them
         (zero_grad() and state_dict() call it)."""
+        found_inf, grad_scale = getattr(self, 'found_inf', None), getattr(self, 'grad_scale', None)
+        amp = None if found_inf is None and grad_scale is None else (found_inf, grad_scale)
+        if amp is not None and any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
+            raise RuntimeError('FusedAdamW.step: a loss scaler (precision: 16) cannot drive the sharded data-parallel exchange: after '
+                               'backward_and_sync() p.grad holds zeros, so the scaler\'s overflow check sees nothing.  The modes that work '
+                               'under precision: 16 are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
         on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
         main = torch.cuda.current_stream() if on_gpu else None
         jobs = self._jobs(overlap, main, self.max_grad_norm is not None)
+        record = None
         if self.max_grad_norm is None:
             self.last_grad_norm = coef = None
+            if amp is not None:                              # (the record needs no gradient: the updates go on tower by tower)
+                _, record = self._amp_record(*amp, None, main.cuda_stream if main is not None else None)
             joined = []
             for job in jobs:                                 # tower by tower
                 if not job[3]:
                     self._await_grads(job, main)
-                joined.append(self._update(job, zero_grad, overlap, main))
+                joined.append(self._update(job, zero_grad, overlap, main, None, record))
             extras = self._extra_items()
         else:
             jobs.sort(key=lambda j: not j[3])                # (stable) the sharded towers' partial sums lie first
             extras = self._extra_items()
-            self.last_grad_norm, coef = self._clip_coef(jobs, extras, main)
-            joined = [self._update(job, zero_grad, overlap, main, coef) for job in jobs]
+            if amp is None:
+                self.last_grad_norm, coef = self._clip_coef(jobs, extras, main)
+            else:
+                coef = None
+                self.last_grad_norm, record = self._clip_coef(jobs, extras, main, amp)
+            joined = [self._update(job, zero_grad, overlap, main, coef, record) for job in jobs]
         if extras:
             # the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)
-            self._adamw_many(extras, zero_grad, main.cuda_stream if main is not None else None, coef)
+            self._adamw_many(extras, zero_grad, main.cuda_stream if main is not None else None, coef, record)
         if join:
             for stream in joined:
                 if stream is not None:
@@ -422,6 +490,26 @@ class FusedAdamW:
             out.append(where[p.data_ptr()])
         return out
 
+    def _trainable(self):
+        """the parameters behind _slots(), in its order: tower by tower, extras last"""
+        out = []
+        for tw in self.towers:
+            if tw.flat is None:
+                continue
+            rng = self._ranges(tw)
+            out += [p for p, off in zip([p for p in tw._params() if p is not None], tw._offsets) if any(a <= off < b for a, b in rng)]
+        return out + list(self.extras)
+
+    @property
+    def param_groups(self):
+        """what torch.amp.GradScaler iterates to reach the p.grad views (unscale_, its overflow check): one group over the parameters
+        this optimizer was built over.  A read-only picture: the hyper-parameters are the optimizer's attributes (opt.lr is the knob)."""
+        return [{'params': self._trainable(), 'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay}]
+
+    def _steps_taken(self):
+        """step_count less the steps a loss scaler had skipped (one host read of the device counter)"""
+        return self.step_count - (int(self._skipped.item()) if self._skipped is not None else 0)
+
     def state_dict(self, params=None):
         """`params`: the iteration order torch.optim.AdamW would have been built with (reference distil_model.py:161,
         dual_distill_model.py:195: filter(requires_grad, self.parameters())); default = canonical tower order.
@@ -431,17 +519,18 @@ class FusedAdamW:
         self.join()
         slots = self._slots(params)
         state = {}
+        steps = self._steps_taken()
         full = {id(tw): self._full_moments(tw) for tw in self.towers if id(tw) in self._state}
         for i, (tw, off, n, shape) in enumerate(slots):
             if off is None:                               # a parameter outside the tower buffers
                 if id(tw) in self._extra_state:
                     m, v = self._extra_state[id(tw)]
-                    state[i] = {'step': torch.tensor(float(self.step_count)), 'exp_avg': m.view(shape).clone(),
+                    state[i] = {'step': torch.tensor(float(steps)), 'exp_avg': m.view(shape).clone(),
                                 'exp_avg_sq': v.view(shape).clone()}
                 continue
             if id(tw) in full:
                 m, v = full[id(tw)]
-                state[i] = {'step': torch.tensor(float(self.step_count)), 'exp_avg': m[off:off + n].view(shape).clone(),
+                state[i] = {'step': torch.tensor(float(steps)), 'exp_avg': m[off:off + n].view(shape).clone(),
                             'exp_avg_sq': v[off:off + n].view(shape).clone()}
         group = {'lr': self.lr, 'initial_lr': self.base_lr, 'betas': tuple(self.betas), 'eps': self.eps,
                  'weight_decay': self.weight_decay, 'amsgrad': False, 'maximize': False, 'foreach': None,
@@ -486,6 +575,8 @@ class FusedAdamW:
         if len(steps) > 1:
             raise ValueError('FusedAdamW.load_state_dict: parameters with different step counts (one fused step counter here)')
         self.step_count = steps.pop() if steps else 0
+        if self._skipped is not None:
+            self._skipped.zero_()
 
 
 class EpochCosineSchedule:

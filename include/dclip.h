@@ -271,6 +271,35 @@ int dclip_adamw_multi_scaled(float* const* p, float* const* g, float* const* m, 
 #define DCLIP_SUMSQ_PARTIALS 1024
 int dclip_sumsq_multi(const float* const* g, const int64_t* n, int32_t count, float* partials, int64_t n_partials, void* stream);
 int dclip_clip_coef(const float* partials, int64_t n_partials, const float* extra_sumsq, float max_norm, float* out, void* stream);
+/*
+ * The same step under a loss scaler (torch.amp.GradScaler's protocol for an optimizer with _step_supports_amp_scaling: the scaler
+ * hands over its scale and its overflow flag as device tensors, the optimizer unscales in its kernel and skips on the device):
+ *   amp_prepare     : one workgroup, after the sums and before the updates.  Writes the step's control record (DEVICE,
+ *                     DCLIP_AMP_RECORD_FLOATS f32, 16-byte aligned) from
+ *                       found_inf, grad_scale : DEVICE, one f32 each, either may be NULL (no overflow / scale 1) ;
+ *                       partials, n_partials, extra_sumsq, max_norm : as dclip_clip_coef, or NULL, 0, NULL for a step that does not clip ;
+ *                       skipped : DEVICE, one int64 the caller keeps across steps (8-byte aligned, 0 before the first step) ;
+ *                     record[DCLIP_AMP_SKIP] = (*found_inf != 0) ; *skipped += that ;
+ *                     record[DCLIP_AMP_NORM] = (float)(sqrt(sum) / *grad_scale), the norm of the unscaled gradients (0 without clipping) ;
+ *                     record[DCLIP_AMP_COEF] = min(1, max_norm / (norm + 1e-6f)) (1 without clipping) ;
+ *                     record[DCLIP_AMP_MULT] = coef / *grad_scale ;
+ *                     record[DCLIP_AMP_BC1], [DCLIP_AMP_BC2_SQRT] = dclip_adamw_multi's bias corrections 1 - beta1^t and sqrt(1 - beta2^t)
+ *                     for t = step - *skipped, bit for bit what a host step t gives.
+ *   adamw_multi_amp : dclip_adamw_multi_scaled with gscale = record[DCLIP_AMP_MULT] and the record's bias corrections.  With
+ *                     record[DCLIP_AMP_SKIP] set it writes no p, m or v; g is still cleared if zero_grad.  The gradient is never
+ *                     written back unscaled (torch's fused AdamW does that; nothing here reads it afterwards).
+ */
+#define DCLIP_AMP_RECORD_FLOATS 8
+#define DCLIP_AMP_MULT 0
+#define DCLIP_AMP_SKIP 1
+#define DCLIP_AMP_BC1 2
+#define DCLIP_AMP_BC2_SQRT 3
+#define DCLIP_AMP_NORM 4
+#define DCLIP_AMP_COEF 5
+int dclip_amp_prepare(const float* found_inf, const float* grad_scale, const float* partials, int64_t n_partials, const float* extra_sumsq,
+                      float max_norm, float beta1, float beta2, int64_t step, int64_t* skipped, float* record, void* stream);
+int dclip_adamw_multi_amp(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int zero_grad, const float* record, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused distillation loss, forward + backward.
