@@ -353,3 +353,33 @@ def adamw_multi_amp(items, lr, betas, eps, weight_decay, zero_grad, record, stre
     lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
     lib().dclip_adamw_multi_amp(arr(0), arr(1), arr(2), arr(3), lens, n, lr, betas[0], betas[1], eps, weight_decay, 1 if zero_grad else 0,
                                 _p(record), _stream() if stream is None else stream)
+
+
+def clipscore(img, cand, refs=None, ref_offsets=None, *, K=1, w=2.5):
+    """CLIP-S / RefCLIP-S of K candidates per image in ONE launch (include/dclip.h: dclip_clipscore).  img f32 [B, E], cand f32 [B * K, E]
+    (row b * K + k belongs to image b), refs f32 [R, E] with ref_offsets int32 [B + 1] on the device (CSR into refs), or neither: raw,
+    un-normalised embeddings; rows may be strided.  -> (clip_s, ref_s, refclip_s), f32 [B * K] each; the last two None without references."""
+    _chk(img, cand, refs, ref_offsets)
+    if (refs is None) != (ref_offsets is None):
+        raise ValueError('clipscore: refs and ref_offsets come together')
+    for name, t in (('img', img), ('cand', cand), ('refs', refs)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1):
+            raise ValueError(f'clipscore: {name} must be an f32 [rows, E] matrix with unit column stride')
+    B, E = img.shape
+    K = int(K)
+    if K < 1 or cand.shape != (B * K, E) or (refs is not None and refs.shape[1] != E):
+        raise ValueError(f'clipscore: img {tuple(img.shape)} and K={K} need cand [{B * K}, {E}] and refs [R, {E}], got {tuple(cand.shape)}'
+                         + ('' if refs is None else f' and {tuple(refs.shape)}'))
+    R = 0
+    if refs is not None:
+        if ref_offsets.dtype != torch.int32 or ref_offsets.dim() != 1 or ref_offsets.numel() != B + 1 or not ref_offsets.is_contiguous():
+            raise ValueError(f'clipscore: ref_offsets must be a contiguous int32 [{B + 1}] tensor')
+        R = refs.shape[0]
+        if R == 0:
+            refs = img.new_zeros((1, E))           # an empty tensor has no address to hand over; with R = 0 no row of this one is read
+    clip_s = torch.empty(B * K, dtype=torch.float32, device=img.device)
+    ref_s = torch.empty_like(clip_s) if refs is not None else None
+    refclip_s = torch.empty_like(clip_s) if refs is not None else None
+    lib().dclip_clipscore(_p(img), img.stride(0), _p(cand), cand.stride(0), _p(refs), 0 if refs is None else refs.stride(0),
+                          _p(ref_offsets), B, K, R, E, float(w), _p(clip_s), _p(ref_s), _p(refclip_s), _stream())
+    return clip_s, ref_s, refclip_s

@@ -373,6 +373,25 @@ size_t dclip_retrieval_metrics_workspace(int64_t n, int64_t E);
 int dclip_retrieval_metrics(const float* img, const float* txt, int64_t n, int64_t E, const int32_t* ks, int nk,
                             float* out, int32_t* rank_out, void* workspace, size_t ws_bytes, void* stream);
 /*
+ * L-CLIPScore scoring: CLIP-S and RefCLIP-S (Hessel et al. 2021) of K candidate captions per image against the image and against a
+ * ragged set of reference captions, in one launch (score.hip; the metric the reference's students are trained to be — the reference
+ * itself ships no scorer).
+ *   cos(a, b) = a.b / (|a| |b|), 0 when either norm is 0 (never NaN for finite rows whose squared norms are finite in f32)
+ *   clip_s[b K + k]    = w max(cos(img[b], cand[b K + k]), 0)                       (the paper's w = 2.5)
+ *   ref_s[b K + k]     = max(0, max over r in [ref_offsets[b], ref_offsets[b + 1]) of cos(cand[b K + k], refs[r])), 0 for an empty set
+ *   refclip_s[b K + k] = 2 clip_s ref_s / (clip_s + ref_s), 0 when the denominator is 0
+ * img f32 [B, E], cand f32 [B K, E], refs f32 [R, E] or NULL: the towers' raw last_representation rows, un-normalised (the norms are
+ * formed in the kernel); ld_* = row strides in elements, >= E and multiples of 4; the three row pointers 16-byte aligned.
+ * ref_offsets: DEVICE int32 [B + 1], NULL exactly when refs is NULL.  Every offset is clamped into [0, R] by the kernel and
+ * end <= start reads as an empty set, so no table content makes it read outside refs.  E % 4 == 0, 4 <= E <= 1024; B, K >= 1; R >= 0.
+ * clip_s, ref_s, refclip_s: f32 [B K] each, fully overwritten; ref_s and refclip_s may be NULL and must be without refs.
+ * One wave per candidate row; plain stores, no atomics, no workspace: the same call gives the same bits.  Added without a version bump:
+ * no existing signature changed.
+ */
+int dclip_clipscore(const float* img, int64_t ld_img, const float* cand, int64_t ld_cand, const float* refs, int64_t ld_ref,
+                    const int32_t* ref_offsets, int64_t B, int64_t K, int64_t R, int64_t E, float w, float* clip_s, float* ref_s,
+                    float* refclip_s, void* stream);
+/*
  * Row block of the same loss for data-parallel global negatives (Collective 2): the four inputs are the GATHERED
  * [B, E] embeddings of all ranks, this call owns rows [row0, row0 + rows) — its own samples — against all B columns.
  * d_s_img / d_s_txt: [rows, E] gradients of the owned samples (d global loss / d embedding).  out_scalars: this block's share of
