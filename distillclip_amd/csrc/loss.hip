@@ -500,6 +500,10 @@ int run_distill_loss(const float* s_img, const float* t_img, const float* s_txt,
     DCLIP_REQUIRE(rows == B || (a.c.w_hl == 0.f && a.c.w_sl == 0.f) || gathered_stats || stats_out,
                   "%s: hard_label / soft_label need the statistics of every row: call once with stats_out, gather, call again with them", who);
     a.gstats = gathered_stats; a.stats_out = stats_out;
+    const bool cross = a.c.two_tower && (a.c.w_cd != 0.f || a.c.w_hl != 0.f || a.c.w_sl != 0.f || a.c.w_mse != 0.f);
+    // a statistics-only call is the stripe pass A: without a cross-modal term no kernel would write stats_out
+    DCLIP_REQUIRE(!stats_out || gathered_stats || cross,
+                  "%s: stats_out needs two-tower mode with a cross-modal term enabled (nothing would write the statistics)", who);
     DCLIP_REQUIRE((a.c.w_kl == 0.f && a.c.w_sl == 0.f) || a.c.tau > 0.f, "%s: KL terms need temperature > 0", who);
     DCLIP_REQUIRE(ws_bytes >= dclip_distill_loss_workspace(B, E), "%s: workspace too small", who);
     DCLIP_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", who);
@@ -521,7 +525,6 @@ int run_distill_loss(const float* s_img, const float* t_img, const float* s_txt,
     a.inv[0] = (float*)w; a.inv[1] = a.inv[0] + rows; w += align_up((size_t)2 * B * 4);
     a.stats = (float*)w; w += align_up((size_t)a.zs * 6 * B * 4);
     a.scal = (float*)w;
-    const bool cross = a.c.two_tower && (a.c.w_cd != 0.f || a.c.w_hl != 0.f || a.c.w_sl != 0.f || a.c.w_mse != 0.f);
     hipStream_t st = (hipStream_t)stream;
     // algorithmic HBM bytes: read 4*B*E*4 + write 2*rows*E*4 ; the logits contribute none
     TraceScope tr(DCLIP_TRACE_LOSS, 0.0, (a.c.two_tower ? 2.0 : 1.0) * (2.0 * (double)B + (double)rows) * E * 4.0, stream);

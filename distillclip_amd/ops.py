@@ -167,7 +167,8 @@ def distill_loss(s_img, t_img, s_txt=None, t_txt=None, *, weights, temperature=N
     [rows, E] of the owned samples, scalars = this block's share (sum over the blocks = the whole-batch values).
     hard_label / soft_label in row-block mode: first `stats_only=True` -> [6, rows] statistics of the owned rows (natural-log
     log-sum-exps of S, S / tau, T / tau over each row, then over each column); gather all blocks into [6, B] and pass them as
-    `gathered_stats` to the second call."""
+    `gathered_stats` to the second call.  `stats_only` needs both towers and a cross-modal term (ValueError otherwise: no kernel would
+    write the statistics); a statistic of a disabled term is -inf."""
     import ctypes
     _chk(s_img, t_img, s_txt, t_txt)
     B, E = s_img.shape

@@ -400,6 +400,11 @@ int dclip_clipscore(const float* img, int64_t ld_img, const float* cand, int64_t
  * statistics pass runs, no gradients), all-gather the ranks' blocks into [6, B] (statistic-major, rows in rank order), and call again
  * with gathered_stats.  Statistic k of row r is a natural-log log-sum-exp over the B logits of that row (k = 0..2) or column (k = 3..5):
  * log sum_j exp(x_j) for x = S (hard_label), S / tau and T / tau (soft_label); S / T = student / teacher cosine logits, tau = cfg[8].
+ * The statistics-only call (stats_out set, gathered_stats null) writes all six rows of stats_out: statistic 0 / 3 is filled when
+ * hard_label is enabled, 1, 2, 4, 5 when soft_label is; a statistic of a disabled term is -inf (the empty log-sum-exp) in every
+ * element.  It needs two_tower = 1 and at least one cross-modal term (otherwise the pass that writes them does not run: DCLIP_EINVAL),
+ * does not write out_scalars, and leaves the owned [rows, E] of d_s_img / d_s_txt unspecified.  With gathered_stats given, stats_out
+ * is ignored.
  * Both pointers null: only terms without such statistics (cos_diff, logits_mse, tower terms) may be enabled.
  * Same workspace query (with the gathered B).
  */
