@@ -39,6 +39,11 @@ __device__ __forceinline__ u32x4 load_a8(const bf16_t* A, int64_t lda, int N, in
     return u32x4{lo[0], lo[1], hi[0], hi[1]};
 }
 
+// the 16-row tile of sample b that holds its picked row (pick[b] = b * N + n, dclip_pick_index), held inside the sample
+__device__ __forceinline__ int pick_tile(const int32_t* pick, int b, int N) {
+    return min(max((pick[b] - b * N) >> 4, 0), (N - 1) >> 4);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // NT: one wave per (b,h).  HD = head dim (32 or 64).
 // ---------------------------------------------------------------------------------------------------------
@@ -145,8 +150,10 @@ __device__ __forceinline__ void wave_stage_perm4(const bf16_t* __restrict__ G, i
 // ---------------------------------------------------------------------------------------------------------
 // NN: C[(b,i), h*HD + d] = alpha * sum_j A[b,h,i,j] * B[(b,j), h*HD + d]
 // ---------------------------------------------------------------------------------------------------------
-template <int HD>
-__global__ __launch_bounds__(256) void attn_nn_kernel(AttnMM p) {
+// ROWS: only the 16-row tile that holds row pick[b] of each sample is formed (same fragments, same MFMA order: those rows come out
+// bit-equal); with fill_zero the other rows of C are stored as zeros, without it they are left untouched.
+template <int HD, bool ROWS = false>
+__global__ __launch_bounds__(256) void attn_nn_kernel(AttnMM p, const int32_t* pick, int fill_zero) {
     constexpr int ROWB = HD * 2 + 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -172,9 +179,10 @@ __global__ __launch_bounds__(256) void attn_nn_kernel(AttnMM p) {
             dst[ks] = (ks < nks && j0 < p.Np) ? __builtin_bit_cast(bf16x8, load_a8(A, p.lda, p.N, p.a_blocked, ia, j0)) : zero_frag();
         }
     };
-    load_a(0, af);
-    for (int it = 0; it < nt; ++it) {
-        if (it + 1 < nt) load_a(it + 1, afn);
+    const int it0 = ROWS ? pick_tile(pick, b, p.N) : 0, it1 = ROWS ? it0 + 1 : nt;
+    load_a(it0, af);
+    for (int it = it0; it < it1; ++it) {
+        if (it + 1 < it1) load_a(it + 1, afn);
         f32x4 acc[DT];
 #pragma unroll
         for (int d = 0; d < DT; ++d) acc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -196,6 +204,14 @@ __global__ __launch_bounds__(256) void attn_nn_kernel(AttnMM p) {
         }
 #pragma unroll
         for (int ks = 0; ks < KSM; ++ks) af[ks] = afn[ks];
+    }
+    if (ROWS && fill_zero && live) {
+        // this head's HD columns of every row outside the tile, 16 bytes per lane
+        constexpr int CPR = HD / 8;
+        for (int idx = lane; idx < p.N * CPR; idx += 64) {
+            const int i = idx / CPR, c = idx - i * CPR;
+            if ((i >> 4) != it0) *(u32x4*)((bf16_t*)p.C + ((int64_t)b * p.N + i) * p.ldc + h * HD + c * 8) = u32x4{0u, 0u, 0u, 0u};
+        }
     }
 }
 
@@ -225,8 +241,9 @@ struct AttnFused {
 // 12 / 8 waves per CU, and ties go to the split form.  At N = 101 (l_clip at 336 px), hd = 64, that workgroup needs 50 KB (two V tiles
 // of 17.5 KB, four P tiles of 3.75 KB: three workgroups per CU) where four one-wave problems at the N = 128 sizing needed 99 KB and left
 // ONE workgroup per CU.
-template <int HD, int NTM>
-__global__ __launch_bounds__(256, NTM <= 7 ? 3 : 2) void attn_fused_fwd_kernel(AttnFused p) {
+// ROWS (launched with split = 1): a problem's wave forms only the query tile that holds row pick[b], as the full kernel forms it.
+template <int HD, int NTM, bool ROWS = false>
+__global__ __launch_bounds__(256, NTM <= 7 ? 3 : 2) void attn_fused_fwd_kernel(AttnFused p, const int32_t* pick) {
     constexpr int VROWB = HD * 2 + 32;
     constexpr int KS = HD / 32, DT = HD / 16, KSM = (NTM + 1) / 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -257,9 +274,10 @@ __global__ __launch_bounds__(256, NTM <= 7 ? 3 : 2) void attn_fused_fwd_kernel(A
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) kf[jt][ks] = *(const bf16x8*)(K + (int64_t)jb * p.ldq + ks * 32 + fk);
         }
+    const int it0 = ROWS ? pick_tile(pick, b, p.N) : part, it1 = ROWS ? it0 + 1 : nt;
     bf16x8 qf[KS], qn[KS];
     {
-        const int ia = min(part * 16 + fr, p.N - 1);
+        const int ia = min(it0 * 16 + fr, p.N - 1);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const bf16x8*)(Q + (int64_t)ia * p.ldq + ks * 32 + fk);
     }
@@ -270,8 +288,8 @@ __global__ __launch_bounds__(256, NTM <= 7 ? 3 : 2) void attn_fused_fwd_kernel(A
     }
     for (int idx = lane; idx < 16 * prowb / 4; idx += 64) ((unsigned*)pt)[idx] = 0u;
     __syncthreads();
-    for (int it = part; it < nt; it += split) {
-        if (it + split < nt) {
+    for (int it = it0; it < it1; it += split) {
+        if (it + split < it1) {
             const int ia = min((it + split) * 16 + fr, p.N - 1);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) qn[ks] = *(const bf16x8*)(Q + (int64_t)ia * p.ldq + ks * 32 + fk);
@@ -520,8 +538,10 @@ __global__ __launch_bounds__(256, 3) void attn_stream_fwd_kernel(AttnStream p) {
 // ---------------------------------------------------------------------------------------------------------
 
 // MAXJ = output row tiles (16 rows each) the instance holds accumulators for: 4 (N <= 64), 5 (N <= 80) or 8 (N <= 128)
-template <int HD, int MAXJ>
-__global__ __launch_bounds__(256, MAXJ <= 5 ? 2 : 1) void attn_tn_kernel(AttnMM p) {
+// ROWS: the contraction runs over the 16 rows of the tile that holds row pick[b] only: the one 32-row chunk with that tile in it, its
+// other half (and rows >= N) staged as zeros for A and B alike, so nothing outside the tile is read.  Every output row is written.
+template <int HD, int MAXJ, bool ROWS = false>
+__global__ __launch_bounds__(256, MAXJ <= 5 ? 2 : 1) void attn_tn_kernel(AttnMM p, const int32_t* pick) {
     constexpr int BROW = HD * 2 + 32;
     constexpr int DT = HD / 16;
     constexpr int AROW = MAXJ * 32 + 32;            // LDS row of the A chunk [32 x 16 MAXJ] bf16, padded
@@ -539,6 +559,9 @@ __global__ __launch_bounds__(256, MAXJ <= 5 ? 2 : 1) void attn_tn_kernel(AttnMM 
     const int ntj = (p.N + 15) >> 4;
     const int nchunk = (p.N + 31) >> 5;
     const int acpr = p.Np >> 3;                       // A: 16-byte chunks per row
+    const int itp = ROWS ? pick_tile(pick, b, p.N) : 0;
+    const int ch0 = ROWS ? itp >> 1 : 0, ch1 = ROWS ? ch0 + 1 : nchunk;
+    auto row_ok = [&](int i) { return i < p.N && (!ROWS || (i >> 4) == itp); };
     f32x4 acc[MAXJ][DT];
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j)
@@ -556,13 +579,13 @@ __global__ __launch_bounds__(256, MAXJ <= 5 ? 2 : 1) void attn_tn_kernel(AttnMM 
             const int idx = k * 64 + lane;
             const int r = p.a_blocked ? (idx & 31) : idx / acpr, c = p.a_blocked ? (idx >> 5) : idx - r * acpr;
             ra[k] = u32x4{0u, 0u, 0u, 0u};
-            if (r < 32 && c < acpr && ch * 32 + r < p.N) ra[k] = load_a8(A, p.lda, p.N, p.a_blocked, ch * 32 + r, c * 8);
+            if (r < 32 && c < acpr && row_ok(ch * 32 + r)) ra[k] = load_a8(A, p.lda, p.N, p.a_blocked, ch * 32 + r, c * 8);
         }
 #pragma unroll
         for (int k = 0; k < BCH; ++k) {
             const int idx = k * 64 + lane, r = idx / (HD / 8), c = idx % (HD / 8);
             rb[k] = u32x4{0u, 0u, 0u, 0u};
-            if (ch * 32 + r < p.N) rb[k] = *(const u32x4*)(Bm + (int64_t)(ch * 32 + r) * p.ldb + c * 8);
+            if (row_ok(ch * 32 + r)) rb[k] = *(const u32x4*)(Bm + (int64_t)(ch * 32 + r) * p.ldb + c * 8);
         }
     };
     auto store_chunk = [&]() {
@@ -582,13 +605,13 @@ __global__ __launch_bounds__(256, MAXJ <= 5 ? 2 : 1) void attn_tn_kernel(AttnMM 
             *(u32x2*)(bt + r * BROW + (4 * (q1 % DT) + q1 / DT) * 8) = u32x2{rb[k][2], rb[k][3]};
         }
     };
-    load_chunk(0);
-    for (int ch = 0; ch < nchunk; ++ch) {
+    load_chunk(ch0);
+    for (int ch = ch0; ch < ch1; ++ch) {
         __builtin_amdgcn_wave_barrier();
         store_chunk();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        if (ch + 1 < nchunk) load_chunk(ch + 1);
+        if (ch + 1 < ch1) load_chunk(ch + 1);
         bf16x8 bf[DT];
 #pragma unroll
         for (int d = 0; d < DT; ++d) bf[d] = tr_frag<BROW>(bt, 0, d * 16, lane);
@@ -643,45 +666,60 @@ extern "C" int dclip_attn_nt(const void* A, int64_t lda, const void* Bm, int64_t
     return dclip_check_launch("dclip_attn_nt");
 }
 
-extern "C" int dclip_attn_nn(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H,
-                             int64_t N, int64_t Np, int64_t hd, float alpha, int a_blocked, void* stream) {
+namespace {
+
+// pick: null = the full product; else the row-tile form (ROWS instances) with one picked row per sample
+int launch_nn(const char* who, const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t Np,
+              int64_t hd, float alpha, int a_blocked, const int32_t* pick, int fill_zero, void* stream) {
     AttnMM p{A, Np, (const bf16_t*)Bm, ldb, C, ldc, (int)B, (int)H, (int)N, (int)Np, (int)hd, alpha, a_blocked};
-    if (int rc = check_mm(p, "dclip_attn_nn")) return rc;
-    DCLIP_REQUIRE(ldc % 8 == 0 && ((uintptr_t)C % 16) == 0 && ldb % 8 == 0 && ((uintptr_t)Bm % 16) == 0, "dclip_attn_nn: token-major operands must be 16-byte aligned");
-    TraceScope tr(DCLIP_TRACE_ATTN, 2.0 * B * H * N * N * hd, 4.0 * B * H * N * hd + 2.0 * B * H * N * Np, stream, (int)(B * H), (int)N, (int)hd, 2);
+    if (int rc = check_mm(p, who)) return rc;
+    DCLIP_REQUIRE(ldc % 8 == 0 && ((uintptr_t)C % 16) == 0 && ldb % 8 == 0 && ((uintptr_t)Bm % 16) == 0, "%s: token-major operands must be 16-byte aligned", who);
+    const double rows = pick ? 16.0 : (double)N;
+    TraceScope tr(DCLIP_TRACE_ATTN, 2.0 * B * H * rows * N * hd, 2.0 * B * H * (N + rows) * hd + 2.0 * B * H * rows * Np, stream, (int)(B * H), (int)N, (int)hd, 2);
     const dim3 grid((unsigned)((B * H + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
     const size_t n32 = ((size_t)N + 31) & ~(size_t)31;
-    if (hd == 32) hipLaunchKernelGGL((attn_nn_kernel<32>), grid, dim3(256), 4 * n32 * (32 * 2 + 32), st, p);
-    else hipLaunchKernelGGL((attn_nn_kernel<64>), grid, dim3(256), 4 * n32 * (64 * 2 + 32), st, p);
-    return dclip_check_launch("dclip_attn_nn");
+    if (hd == 32) {
+        if (pick) hipLaunchKernelGGL((attn_nn_kernel<32, true>), grid, dim3(256), 4 * n32 * (32 * 2 + 32), st, p, pick, fill_zero);
+        else hipLaunchKernelGGL((attn_nn_kernel<32>), grid, dim3(256), 4 * n32 * (32 * 2 + 32), st, p, nullptr, 0);
+    } else {
+        if (pick) hipLaunchKernelGGL((attn_nn_kernel<64, true>), grid, dim3(256), 4 * n32 * (64 * 2 + 32), st, p, pick, fill_zero);
+        else hipLaunchKernelGGL((attn_nn_kernel<64>), grid, dim3(256), 4 * n32 * (64 * 2 + 32), st, p, nullptr, 0);
+    }
+    return dclip_check_launch(who);
 }
 
-extern "C" int dclip_attn_tn(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H,
-                             int64_t N, int64_t Np, int64_t hd, float alpha, int a_blocked, void* stream) {
+int launch_tn(const char* who, const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t Np,
+              int64_t hd, float alpha, int a_blocked, const int32_t* pick, void* stream) {
     AttnMM p{A, Np, (const bf16_t*)Bm, ldb, C, ldc, (int)B, (int)H, (int)N, (int)Np, (int)hd, alpha, a_blocked};
-    if (int rc = check_mm(p, "dclip_attn_tn")) return rc;
-    DCLIP_REQUIRE(ldc % 8 == 0 && ((uintptr_t)C % 16) == 0 && ldb % 8 == 0 && ((uintptr_t)Bm % 16) == 0, "dclip_attn_tn: token-major operands must be 16-byte aligned");
-    TraceScope tr(DCLIP_TRACE_ATTN, 2.0 * B * H * N * N * hd, 4.0 * B * H * N * hd + 2.0 * B * H * N * Np, stream, (int)(B * H), (int)N, (int)hd, 3);
+    if (int rc = check_mm(p, who)) return rc;
+    DCLIP_REQUIRE(ldc % 8 == 0 && ((uintptr_t)C % 16) == 0 && ldb % 8 == 0 && ((uintptr_t)Bm % 16) == 0, "%s: token-major operands must be 16-byte aligned", who);
+    const double rows = pick ? 16.0 : (double)N;
+    TraceScope tr(DCLIP_TRACE_ATTN, 2.0 * B * H * rows * N * hd, 2.0 * B * H * (N + rows) * hd + 2.0 * B * H * rows * Np, stream, (int)(B * H), (int)N, (int)hd, 3);
     const dim3 grid((unsigned)((B * H + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
     const int ntile = ((int)Np + 15) / 16;
     const int mj = ntile <= 4 ? 4 : (ntile <= 5 ? 5 : 8);
     const size_t lds = (size_t)4 * (32 * (mj * 32 + 32) + 32 * ((int)hd * 2 + 32));
-#define TN_LAUNCH(HDv, NTv) hipLaunchKernelGGL((attn_tn_kernel<HDv, NTv>), grid, dim3(256), lds, st, p)
+#define TN_LAUNCH(HDv, NTv)                                                                                          \
+    do {                                                                                                             \
+        if (pick) hipLaunchKernelGGL((attn_tn_kernel<HDv, NTv, true>), grid, dim3(256), lds, st, p, pick);           \
+        else hipLaunchKernelGGL((attn_tn_kernel<HDv, NTv>), grid, dim3(256), lds, st, p, nullptr);                   \
+    } while (0)
     if (hd == 32) { if (ntile <= 4) TN_LAUNCH(32, 4); else if (ntile <= 5) TN_LAUNCH(32, 5); else TN_LAUNCH(32, 8); }
     else { if (ntile <= 4) TN_LAUNCH(64, 4); else if (ntile <= 5) TN_LAUNCH(64, 5); else TN_LAUNCH(64, 8); }
 #undef TN_LAUNCH
-    return dclip_check_launch("dclip_attn_tn");
+    return dclip_check_launch(who);
 }
 
-extern "C" int dclip_attn_fused_fwd(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
-                                    float scale, int causal, void* stream) {
-    DCLIP_REQUIRE(qkv && ctx && B > 0 && H > 0 && N > 0 && N <= NMAX, "dclip_attn_fused_fwd: bad argument (N <= %d)", NMAX);
-    DCLIP_REQUIRE(hd == 32 || hd == 64, "dclip_attn_fused_fwd: head dim must be 32 or 64 (got %ld)", (long)hd);
-    DCLIP_REQUIRE(ldq % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)ctx % 16) == 0, "dclip_attn_fused_fwd: misaligned buffers");
+int launch_fused(const char* who, const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd, float scale,
+                 int causal, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(qkv && ctx && B > 0 && H > 0 && N > 0 && N <= NMAX, "%s: bad argument (N <= %d)", who, NMAX);
+    DCLIP_REQUIRE(hd == 32 || hd == 64, "%s: head dim must be 32 or 64 (got %ld)", who, (long)hd);
+    DCLIP_REQUIRE(ldq % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)ctx % 16) == 0, "%s: misaligned buffers", who);
     AttnFused p{(const bf16_t*)qkv, ldq, (bf16_t*)ctx, ldc, (int)B, (int)H, (int)N, causal, scale, 1};
-    TraceScope tr(DCLIP_TRACE_ATTN, 4.0 * B * H * N * N * hd, 8.0 * B * H * N * hd, stream, (int)(B * H), (int)N, (int)hd, 4);
+    const double rows = pick ? 16.0 : (double)N;
+    TraceScope tr(DCLIP_TRACE_ATTN, 4.0 * B * H * rows * N * hd, 4.0 * B * H * (N + rows) * hd, stream, (int)(B * H), (int)N, (int)hd, 4);
     hipStream_t st = (hipStream_t)stream;
     const int ntile = ((int)N + 15) / 16;
     // an instance holds registers for NT key tiles; odd tile counts need an instance with the 16-key tail step (NT odd)
@@ -692,16 +730,60 @@ extern "C" int dclip_attn_fused_fwd(const void* qkv, int64_t ldq, void* ctx, int
     // alternate query tiles) wherever there is a second query tile to take.  A search for the shape that puts the most waves on a CU
     // (160 KB of LDS; registers allow 12 / 8 waves: launch bounds; ties to the split form, which also halves the dependent chain of a
     // problem) returns exactly this for every N <= 128 and both head sizes: the four-wave split form already reaches the register cap.
-    const int nw = 4, split = ntile >= 2 ? 2 : 1;
+    // Row-tile form: one wave per problem (there is one query tile to take), in workgroups of as many waves as fit 64 KB of LDS.
+    int nw = 4;
+    const int split = !pick && ntile >= 2 ? 2 : 1;
+    while (pick && nw > 1 && nw * (vtile + ptile) > 64 * 1024) nw >>= 1;
     p.split = split;
     const int ppw = nw / split;
     const dim3 grid((unsigned)((B * H + ppw - 1) / ppw));
     const size_t lds = ppw * vtile + (size_t)nw * ptile;
-#define FUSED_LAUNCH(HDv, NTv) hipLaunchKernelGGL((attn_fused_fwd_kernel<HDv, NTv>), grid, dim3(64 * nw), lds, st, p)
+#define FUSED_LAUNCH(HDv, NTv)                                                                                               \
+    do {                                                                                                                     \
+        if (pick) hipLaunchKernelGGL((attn_fused_fwd_kernel<HDv, NTv, true>), grid, dim3(64 * nw), lds, st, p, pick);        \
+        else hipLaunchKernelGGL((attn_fused_fwd_kernel<HDv, NTv>), grid, dim3(64 * nw), lds, st, p, nullptr);                \
+    } while (0)
     if (hd == 32) { if (NT == 4) FUSED_LAUNCH(32, 4); else if (NT == 5) FUSED_LAUNCH(32, 5); else if (NT == 7) FUSED_LAUNCH(32, 7); else FUSED_LAUNCH(32, 8); }
     else { if (NT == 4) FUSED_LAUNCH(64, 4); else if (NT == 5) FUSED_LAUNCH(64, 5); else if (NT == 7) FUSED_LAUNCH(64, 7); else FUSED_LAUNCH(64, 8); }
 #undef FUSED_LAUNCH
-    return dclip_check_launch("dclip_attn_fused_fwd");
+    return dclip_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int dclip_attn_nn(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H,
+                             int64_t N, int64_t Np, int64_t hd, float alpha, int a_blocked, void* stream) {
+    return launch_nn("dclip_attn_nn", A, Bm, ldb, C, ldc, B, H, N, Np, hd, alpha, a_blocked, nullptr, 0, stream);
+}
+
+extern "C" int dclip_attn_tn(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H,
+                             int64_t N, int64_t Np, int64_t hd, float alpha, int a_blocked, void* stream) {
+    return launch_tn("dclip_attn_tn", A, Bm, ldb, C, ldc, B, H, N, Np, hd, alpha, a_blocked, nullptr, stream);
+}
+
+extern "C" int dclip_attn_fused_fwd(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
+                                    float scale, int causal, void* stream) {
+    return launch_fused("dclip_attn_fused_fwd", qkv, ldq, ctx, ldc, B, H, N, hd, scale, causal, nullptr, stream);
+}
+
+// Row-tile forms for an execution of which only row pick[b] (= b * N + n, a device array) of each sample is read afterwards: the
+// products are formed for the 16-row tile that holds that row alone, by the instructions and operands of the full kernels.
+extern "C" int dclip_attn_nn_rows(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H, int64_t N,
+                                  int64_t Np, int64_t hd, float alpha, int a_blocked, const int32_t* pick, int fill_zero, void* stream) {
+    DCLIP_REQUIRE(pick, "dclip_attn_nn_rows: null pick");
+    return launch_nn("dclip_attn_nn_rows", A, Bm, ldb, C, ldc, B, H, N, Np, hd, alpha, a_blocked, pick, fill_zero, stream);
+}
+
+extern "C" int dclip_attn_tn_rows(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H, int64_t N,
+                                  int64_t Np, int64_t hd, float alpha, int a_blocked, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(pick, "dclip_attn_tn_rows: null pick");
+    return launch_tn("dclip_attn_tn_rows", A, Bm, ldb, C, ldc, B, H, N, Np, hd, alpha, a_blocked, pick, stream);
+}
+
+extern "C" int dclip_attn_fused_fwd_rows(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
+                                         float scale, int causal, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(pick, "dclip_attn_fused_fwd_rows: null pick");
+    return launch_fused("dclip_attn_fused_fwd_rows", qkv, ldq, ctx, ldc, B, H, N, hd, scale, causal, pick, stream);
 }
 
 // Long-sequence companion of dclip_attn_fused_fwd (attn_stream_fwd_kernel): any N >= 1, non-causal, hd = 64.

@@ -12,6 +12,7 @@
 //   dclip_attn_mix_bwd : persistent waves; pass A delta = sum_j P dP (and dW_w), pass B dA, dS (and dW_l); dR = dO v^T formed on
 //                        the fly by the same block-diagonal product.  dS (bf16) is stored; the weight gradients leave as ONE
 //                        partial tile per workgroup and a second launch adds them up (no same-line atomics, run-to-run identical).
+//   dclip_attn_mix_fwd_rows / _bwd_rows : the same kernels (PICK instances) on one item per sample, the tile that holds its picked row.
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
@@ -71,16 +72,23 @@ namespace {
 
 constexpr int BWD_MAX_WG = 256;
 
+// the 16-query tile of sample b that holds its picked row (pick[b] = b * N + n, dclip_pick_index), held inside the sample
+DEVFN int pick_tile(const int32_t* pick, int b, int N) {
+    const int it = (pick[b] - b * N) >> 4;
+    return __builtin_amdgcn_readfirstlane(min(max(it, 0), (N - 1) >> 4));
+}
+
 // OCC = waves per SIMD the register allocation is held to (2: two workgroups per CU hide each other's latencies, at 256 registers)
-template <int H, int HD, int OCC>
-__global__ __launch_bounds__(256, OCC) void attn_mix_fwd_kernel(amix::FwdArgs p) {
+// PICK: one item per sample, the tile that holds row pick[b]; only the item enumeration differs
+template <int H, int HD, int OCC, bool PICK = false>
+__global__ __launch_bounds__(256, OCC) void attn_mix_fwd_kernel(amix::FwdArgs p, const int32_t* pick) {
     using C = amix::Cfg<H, HD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int item = blockIdx.x * 4 + wave;
-    if (item >= p.B * p.QT) return;
-    const int b = item / p.QT, it = item - b * p.QT;
+    if (item >= (PICK ? p.B : p.B * p.QT)) return;
+    const int b = PICK ? item : item / p.QT, it = PICK ? pick_tile(pick, b, p.N) : item - b * p.QT;
     const unsigned long long te = p.stamps ? hw::clock() : 0;
     char* lds = smem + wave * amix::fwd_lds_per_wave<C>();
     amix::zero_block_init<C>(lds, lane);
@@ -94,13 +102,49 @@ __global__ __launch_bounds__(256, OCC) void attn_mix_fwd_kernel(amix::FwdArgs p)
     if (p.stamps && lane == 0) p.stamps[12 * (long)item + 11] = __builtin_amdgcn_s_memrealtime();
 }
 
-template <int H, int HD, bool PASS_B>
-__global__ __launch_bounds__(256) void attn_mix_bwd_kernel(amix::BwdArgs p) {
+// amix::bwd_wave with one item per sample, the tile that holds row pick[b]: the same set-up, per-item code and workgroup partial
+template <class C, bool PASS_B>
+DEVFN void bwd_wave_pick(const amix::BwdArgs& p, const int32_t* pick, int wg, int nwg, int wave, int nwave, int lane, char* lds_all) {
+    using namespace amix;
+    constexpr int RT = C::RT, HP = C::HP;
+    constexpr int PER_WAVE = bwd_lds_per_wave<C>(), TILE_OFF = bwd_tile_off<C>();
+    char* lds = lds_all + wave * PER_WAVE;
+    for (int o = lane * 16; o < 2 * WG_TILE; o += 64 * 16) *(u32x4*)(lds + TILE_OFF + o) = u32x4{0u, 0u, 0u, 0u};
+    zero_block_init<C>(lds, lane);
+    BwdWeights<C> w;
+    bwd_load_weights<C, PASS_B>(p, lane, w);
+    f32x4 acc[RT][RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int u = 0; u < RT; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = wg * nwave + wave; b < p.B; b += nwg * nwave) bwd_item<C, PASS_B>(p, b, pick_tile(pick, b, p.N), lane, w, acc, lds);
+    hw::lds_fence();
+    float* mine = (float*)(lds + TILE_OFF);          // [HP][HP] f32
+    const int c = lane & 15, g4 = lane >> 4;
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int u = 0; u < RT; ++u)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mine[(16 * t + 4 * g4 + r) * HP + 16 * u + c] = acc[t][u][r];
+    hw::block_sync();
+    float* out = p.partial + ((long)wg * 2 + (PASS_B ? 0 : 1)) * HP * HP;
+    for (int idx = wave * 64 + lane; idx < HP * HP; idx += nwave * 64) {
+        float s = 0.f;
+        for (int v = 0; v < nwave; ++v) s += ((const float*)(lds_all + v * PER_WAVE + TILE_OFF))[idx];
+        out[idx] = s;
+    }
+}
+
+template <int H, int HD, bool PASS_B, bool PICK = false>
+__global__ __launch_bounds__(256) void attn_mix_bwd_kernel(amix::BwdArgs p, const int32_t* pick) {
     using C = amix::Cfg<H, HD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    amix::bwd_wave<C, PASS_B>(p, blockIdx.x, gridDim.x, wave, 4, lane, smem);
+    if constexpr (PICK) bwd_wave_pick<C, PASS_B>(p, pick, blockIdx.x, gridDim.x, wave, 4, lane, smem);
+    else amix::bwd_wave<C, PASS_B>(p, blockIdx.x, gridDim.x, wave, 4, lane, smem);
 }
 
 // dW[which][g, h] += sum over the workgroups' partial tiles: one 256-thread block per output element, one partial per thread
@@ -163,48 +207,93 @@ extern "C" size_t dclip_attn_mix_bwd_workspace_bytes(int64_t B, int64_t H, int64
     return partial_bytes(H) + (((size_t)B * H * N * sizeof(float) + 255) & ~(size_t)255);
 }
 
+namespace {
+
+// pick: null = every (sample, tile); else one tile per sample, the one that holds row pick[b]
+int launch_mix_fwd(const char* who, const void* qkv, int64_t ld, const float* Wl, const float* Ww, void* R, float* stats, int64_t B, int64_t H,
+                   int64_t N, int64_t Np, int64_t hd, float scale, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(qkv && Wl && Ww && R && stats && B > 0, "%s: null / empty argument", who);
+    DCLIP_REQUIRE(dclip_attn_mix_supported(H, N, hd), "%s: unsupported shape H=%ld N=%ld hd=%ld", who, (long)H, (long)N, (long)hd);
+    DCLIP_REQUIRE(Np == ((N + 7) & ~(int64_t)7) && ld % 8 == 0 && ld >= 3 * H * hd && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)R % 16) == 0,
+                  "%s: misaligned buffers (Np = round_up(N, 8), 16-byte aligned qkv rows and R)", who);
+    const int QT = (int)((N + 15) / 16);
+    amix::FwdArgs p{(const bf16_t*)qkv, (long)ld, Wl, Ww, (bf16_t*)R, stats, (int)B, (int)N, (int)Np, QT, scale, pick ? nullptr : g_fwd_stamps};
+    const int64_t nitem = pick ? B : B * QT;
+    const dim3 grid((unsigned)((nitem + 3) / 4));
+    const double rows = pick ? 16.0 : (double)N, el = (double)B * H * rows * Np;
+    TraceScope tr(DCLIP_TRACE_ATTN, 4.0 * B * H * rows * N * hd + 8.0 * el * H, 2.0 * el + 2.0 * B * (N + rows) * H * hd, stream, (int)(B * H), (int)N, (int)hd, 7);
+    if (pick) {
+        MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_fwd_kernel<HH, HD_, 2, true>), grid, dim3(256), (size_t)4 * amix::fwd_lds_per_wave<CC>(),
+                                               (hipStream_t)stream, p, pick));
+    } else {
+        MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_fwd_kernel<HH, HD_, 2>), grid, dim3(256), (size_t)4 * amix::fwd_lds_per_wave<CC>(),
+                                               (hipStream_t)stream, p, nullptr));
+    }
+    return dclip_check_launch(who);
+}
+
+int launch_mix_bwd(const char* who, const void* qkv, int64_t ld, const void* dO, int64_t ldo, const float* Wl, const float* Ww, const float* stats,
+                   void* dS, float* dWl, float* dWw, void* workspace, size_t ws_bytes, int64_t B, int64_t H, int64_t N, int64_t Np, int64_t hd,
+                   float scale, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(qkv && dO && Wl && Ww && stats && dS && dWl && dWw && workspace && B > 0, "%s: null / empty argument", who);
+    DCLIP_REQUIRE(dclip_attn_mix_supported(H, N, hd), "%s: unsupported shape H=%ld N=%ld hd=%ld", who, (long)H, (long)N, (long)hd);
+    DCLIP_REQUIRE(Np == ((N + 7) & ~(int64_t)7) && ld % 8 == 0 && ldo % 8 == 0 && ld >= 3 * H * hd && ldo >= H * hd && ((uintptr_t)qkv % 16) == 0 &&
+                      ((uintptr_t)dO % 16) == 0 && ((uintptr_t)dS % 16) == 0 && ((uintptr_t)workspace % 16) == 0,
+                  "%s: misaligned buffers", who);
+    DCLIP_REQUIRE(ws_bytes >= dclip_attn_mix_bwd_workspace_bytes(B, H, N), "%s: workspace too small (%zu < %zu)", who, ws_bytes,
+                  dclip_attn_mix_bwd_workspace_bytes(B, H, N));
+    const int QT = (int)((N + 15) / 16);
+    const int HP = (int)((H + 15) / 16) * 16;
+    const int64_t nitem = pick ? B : B * QT;
+    int blocks = (int)((nitem + 3) / 4);
+    if (blocks > BWD_MAX_WG) blocks = BWD_MAX_WG;        // persistent: one weight-gradient partial per workgroup
+    amix::BwdArgs p{(const bf16_t*)qkv, (long)ld, (const bf16_t*)dO, (long)ldo, Wl, Ww, stats, (bf16_t*)dS, (float*)workspace,
+                    (float*)((char*)workspace + partial_bytes(H)), (int)B, (int)N, (int)Np, QT, scale, pick ? nullptr : g_bwd_stamps[0]};
+    const double rows = pick ? 16.0 : (double)N, el = (double)B * H * rows * Np;
+    TraceScope tr(DCLIP_TRACE_ATTN, 8.0 * B * H * rows * N * hd + 20.0 * el * H, 2.0 * el + 4.0 * B * (N + rows) * H * hd, stream, (int)(B * H), (int)N, (int)hd, 8);
+    // pass A: delta = sum_j P dP, dW_w partials ; pass B: dS, dW_l partials
+    if (pick) {
+        MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_bwd_kernel<HH, HD_, false, true>), dim3(blocks), dim3(256), (size_t)4 * amix::bwd_lds_per_wave<CC>(),
+                                               (hipStream_t)stream, p, pick));
+        MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_bwd_kernel<HH, HD_, true, true>), dim3(blocks), dim3(256), (size_t)4 * amix::bwd_lds_per_wave<CC>(),
+                                               (hipStream_t)stream, p, pick));
+    } else {
+        MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_bwd_kernel<HH, HD_, false>), dim3(blocks), dim3(256), (size_t)4 * amix::bwd_lds_per_wave<CC>(),
+                                               (hipStream_t)stream, p, nullptr));
+        p.stamps = g_bwd_stamps[1];
+        MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_bwd_kernel<HH, HD_, true>), dim3(blocks), dim3(256), (size_t)4 * amix::bwd_lds_per_wave<CC>(),
+                                               (hipStream_t)stream, p, nullptr));
+    }
+    static_assert(BWD_MAX_WG <= 256, "one partial per thread of the reduction block");
+    hipLaunchKernelGGL(attn_mix_wgrad_reduce_kernel, dim3((unsigned)(2 * H * H)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)workspace, blocks, (int)H, HP, dWl, dWw);
+    return dclip_check_launch(who);
+}
+
+}  // namespace
+
 extern "C" int dclip_attn_mix_fwd(const void* qkv, int64_t ld, const float* Wl, const float* Ww, void* R, float* stats, int64_t B,
                                   int64_t H, int64_t N, int64_t Np, int64_t hd, float scale, void* stream) {
-    DCLIP_REQUIRE(qkv && Wl && Ww && R && stats && B > 0, "dclip_attn_mix_fwd: null / empty argument");
-    DCLIP_REQUIRE(dclip_attn_mix_supported(H, N, hd), "dclip_attn_mix_fwd: unsupported shape H=%ld N=%ld hd=%ld", (long)H, (long)N, (long)hd);
-    DCLIP_REQUIRE(Np == ((N + 7) & ~(int64_t)7) && ld % 8 == 0 && ld >= 3 * H * hd && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)R % 16) == 0,
-                  "dclip_attn_mix_fwd: misaligned buffers (Np = round_up(N, 8), 16-byte aligned qkv rows and R)");
-    const int QT = (int)((N + 15) / 16);
-    amix::FwdArgs p{(const bf16_t*)qkv, (long)ld, Wl, Ww, (bf16_t*)R, stats, (int)B, (int)N, (int)Np, QT, scale, g_fwd_stamps};
-    const dim3 grid((unsigned)((B * QT + 3) / 4));
-    const double el = (double)B * H * N * Np;
-    TraceScope tr(DCLIP_TRACE_ATTN, 4.0 * B * H * N * N * hd + 8.0 * el * H, 2.0 * el + 4.0 * B * N * H * hd, stream, (int)(B * H), (int)N, (int)hd, 7);
-    MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_fwd_kernel<HH, HD_, 2>), grid, dim3(256), (size_t)4 * amix::fwd_lds_per_wave<CC>(),
-                                           (hipStream_t)stream, p));
-    return dclip_check_launch("dclip_attn_mix_fwd");
+    return launch_mix_fwd("dclip_attn_mix_fwd", qkv, ld, Wl, Ww, R, stats, B, H, N, Np, hd, scale, nullptr, stream);
 }
 
 extern "C" int dclip_attn_mix_bwd(const void* qkv, int64_t ld, const void* dO, int64_t ldo, const float* Wl, const float* Ww,
                                   const float* stats, void* dS, float* dWl, float* dWw, void* workspace, size_t ws_bytes, int64_t B,
                                   int64_t H, int64_t N, int64_t Np, int64_t hd, float scale, void* stream) {
-    DCLIP_REQUIRE(qkv && dO && Wl && Ww && stats && dS && dWl && dWw && workspace && B > 0, "dclip_attn_mix_bwd: null / empty argument");
-    DCLIP_REQUIRE(dclip_attn_mix_supported(H, N, hd), "dclip_attn_mix_bwd: unsupported shape H=%ld N=%ld hd=%ld", (long)H, (long)N, (long)hd);
-    DCLIP_REQUIRE(Np == ((N + 7) & ~(int64_t)7) && ld % 8 == 0 && ldo % 8 == 0 && ld >= 3 * H * hd && ldo >= H * hd && ((uintptr_t)qkv % 16) == 0 &&
-                      ((uintptr_t)dO % 16) == 0 && ((uintptr_t)dS % 16) == 0 && ((uintptr_t)workspace % 16) == 0,
-                  "dclip_attn_mix_bwd: misaligned buffers");
-    DCLIP_REQUIRE(ws_bytes >= dclip_attn_mix_bwd_workspace_bytes(B, H, N), "dclip_attn_mix_bwd: workspace too small (%zu < %zu)", ws_bytes,
-                  dclip_attn_mix_bwd_workspace_bytes(B, H, N));
-    const int QT = (int)((N + 15) / 16);
-    const int HP = (int)((H + 15) / 16) * 16;
-    int blocks = (int)((B * QT + 3) / 4);
-    if (blocks > BWD_MAX_WG) blocks = BWD_MAX_WG;        // persistent: one weight-gradient partial per workgroup
-    amix::BwdArgs p{(const bf16_t*)qkv, (long)ld, (const bf16_t*)dO, (long)ldo, Wl, Ww, stats, (bf16_t*)dS, (float*)workspace,
-                    (float*)((char*)workspace + partial_bytes(H)), (int)B, (int)N, (int)Np, QT, scale, g_bwd_stamps[0]};
-    const double el = (double)B * H * N * Np;
-    TraceScope tr(DCLIP_TRACE_ATTN, 8.0 * B * H * N * N * hd + 20.0 * el * H, 2.0 * el + 8.0 * B * N * H * hd, stream, (int)(B * H), (int)N, (int)hd, 8);
-    // pass A: delta = sum_j P dP, dW_w partials ; pass B: dS, dW_l partials
-    MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_bwd_kernel<HH, HD_, false>), dim3(blocks), dim3(256), (size_t)4 * amix::bwd_lds_per_wave<CC>(),
-                                           (hipStream_t)stream, p));
-    p.stamps = g_bwd_stamps[1];
-    MIX_DISPATCH(H, hd, hipLaunchKernelGGL((attn_mix_bwd_kernel<HH, HD_, true>), dim3(blocks), dim3(256), (size_t)4 * amix::bwd_lds_per_wave<CC>(),
-                                           (hipStream_t)stream, p));
-    static_assert(BWD_MAX_WG <= 256, "one partial per thread of the reduction block");
-    hipLaunchKernelGGL(attn_mix_wgrad_reduce_kernel, dim3((unsigned)(2 * H * H)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)workspace, blocks, (int)H, HP, dWl, dWw);
-    return dclip_check_launch("dclip_attn_mix_bwd");
+    return launch_mix_bwd("dclip_attn_mix_bwd", qkv, ld, dO, ldo, Wl, Ww, stats, dS, dWl, dWw, workspace, ws_bytes, B, H, N, Np, hd, scale, nullptr, stream);
+}
+
+// Row-tile forms (see dclip_attn_nn_rows): R, stats, delta and dS are written on the rows of each sample's picked tile only; the
+// other rows keep whatever they held.  The debug stamps (indexed by (sample, tile)) stay with the full forms.
+extern "C" int dclip_attn_mix_fwd_rows(const void* qkv, int64_t ld, const float* Wl, const float* Ww, void* R, float* stats, int64_t B,
+                                       int64_t H, int64_t N, int64_t Np, int64_t hd, float scale, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(pick, "dclip_attn_mix_fwd_rows: null pick");
+    return launch_mix_fwd("dclip_attn_mix_fwd_rows", qkv, ld, Wl, Ww, R, stats, B, H, N, Np, hd, scale, pick, stream);
+}
+
+extern "C" int dclip_attn_mix_bwd_rows(const void* qkv, int64_t ld, const void* dO, int64_t ldo, const float* Wl, const float* Ww,
+                                       const float* stats, void* dS, float* dWl, float* dWw, void* workspace, size_t ws_bytes, int64_t B,
+                                       int64_t H, int64_t N, int64_t Np, int64_t hd, float scale, const int32_t* pick, void* stream) {
+    DCLIP_REQUIRE(pick, "dclip_attn_mix_bwd_rows: null pick");
+    return launch_mix_bwd("dclip_attn_mix_bwd_rows", qkv, ld, dO, ldo, Wl, Ww, stats, dS, dWl, dWw, workspace, ws_bytes, B, H, N, Np, hd, scale, pick, stream);
 }

@@ -371,30 +371,51 @@ inline int export_stream(bool h16, const void* src, float* dst, int64_t n, void*
 
 // The score stage of one block execution, on the path its workspace was laid out for: ctx = attention(qkv).
 // wl / ww: the execution's conv_l / conv_w weights (head-mixing students), else null.
-int attn_forward(AttnPath path, const Plan& p, const ExecSave& s, const float* wl, const float* ww, int64_t B, int64_t N, void* st) {
+// pick (nullable): the execution is pruned and only row pick[b] of each sample's ctx is read afterwards.  The row-tile kernels then form
+// that row's 16-query tile alone; R and stats (Mix) and ctx are valid on the tile's rows only, and only row-tile kernels may read them.
+int attn_forward(AttnPath path, const Plan& p, const ExecSave& s, const float* wl, const float* ww, int64_t B, int64_t N, const int32_t* pick,
+                 void* st) {
     const int64_t D = p.D, H = p.H, hd = p.hd, Np = (N + 7) & ~(int64_t)7;
     const float scale = 1.f / sqrtf((float)hd);
     if (path == AttnPath::Fused) {
+        if (N <= 128 && pick) return dclip_attn_fused_fwd_rows(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, p.c.causal, pick, st);
         if (N <= 128) return dclip_attn_fused_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, p.c.causal, st);
         return dclip_attn_stream_fwd(s.qkv, 3 * D, s.ctx, D, B, H, N, hd, scale, st);      // (make_plan: frozen, non-causal, hd = 64)
     }
+    const int blk = path == AttnPath::Mix ? 1 : 0;
     if (path == AttnPath::Mix) {
-        CK(dclip_attn_mix_fwd(s.qkv, 3 * D, wl, ww, s.Rm, s.stats, B, H, N, Np, hd, scale, st));
-        return dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 1, st);
+        if (pick) CK(dclip_attn_mix_fwd_rows(s.qkv, 3 * D, wl, ww, s.Rm, s.stats, B, H, N, Np, hd, scale, pick, st));
+        else CK(dclip_attn_mix_fwd(s.qkv, 3 * D, wl, ww, s.Rm, s.stats, B, H, N, Np, hd, scale, st));
+    } else {
+        CK(dclip_attn_nt(s.qkv, 3 * D, s.qkv + D, 3 * D, s.S, 1, B, H, N, Np, hd, scale, st));
+        CK(dclip_attn_softmax_fwd(s.S, wl, ww, wl ? s.P : nullptr, s.Rm, B, H, N, Np, p.c.causal, st));
     }
-    CK(dclip_attn_nt(s.qkv, 3 * D, s.qkv + D, 3 * D, s.S, 1, B, H, N, Np, hd, scale, st));
-    CK(dclip_attn_softmax_fwd(s.S, wl, ww, wl ? s.P : nullptr, s.Rm, B, H, N, Np, p.c.causal, st));
-    return dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, 0, st);
+    if (pick) return dclip_attn_nn_rows(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, blk, pick, 0, st);
+    return dclip_attn_nn(s.Rm, s.qkv + 2 * D, 3 * D, s.ctx, D, B, H, N, Np, hd, 1.f, blk, st);
 }
 
 // Its backward (Mix or Unfused): dqkv from dctx = dO.  gl / gw: the conv_l / conv_w gradients (+=), null when frozen.
 // mg: the gradients of this execution's exported head-mean maps (null when it has none), added to dS before dQ / dK are formed.
+// pick (nullable): the forward formed the picked tiles only (attn_forward) and dctx is zero outside the picked rows.  Every term the
+// row-tile kernels skip is then an exact zero; dQ is zero-filled outside the tiles, dK and dV are written whole.
 struct MapGrad { const float* d_score; const float* d_prob; void* scratch; size_t scratch_bytes; };
 int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w, const float* wl, const float* ww, float* gl, float* gw,
-                  const bf16_t* dctx, bf16_t* dqkv, int64_t B, const MapGrad* mg, void* st) {
+                  const bf16_t* dctx, bf16_t* dqkv, int64_t B, const MapGrad* mg, const int32_t* pick, void* st) {
     const int64_t D = p.D, H = p.H, hd = p.hd, N = p.N, Np = p.Np;
     const float scale = 1.f / sqrtf((float)hd);
     const int blk = path == AttnPath::Mix ? 1 : 0;                // R and dS of the register-resident score stage are quad-blocked
+    if (pick) {
+        CK(dclip_attn_tn_rows(s.Rm, dctx, D, dqkv + 2 * D, 3 * D, B, H, N, Np, hd, 1.f, blk, pick, st));     // dV = R^T dO
+        if (path == AttnPath::Mix) {
+            CK(dclip_attn_mix_bwd_rows(s.qkv, 3 * D, dctx, D, wl, ww, s.stats, w.dS, gl ? gl : w.wg_dummy, gw ? gw : w.wg_dummy + H * H,
+                                       w.mix_ws, w.mix_ws_bytes, B, H, N, Np, hd, scale, pick, st));
+        } else {                                                      // (all rows: these two read nothing a row-tile forward left stale)
+            CK(dclip_attn_nt(dctx, D, s.qkv + 2 * D, 3 * D, w.dR, 0, B, H, N, Np, hd, 1.f, st));
+            CK(dclip_attn_softmax_bwd(w.dR, s.P, s.S, 0, wl, ww, w.dS, gl, gw, B, H, N, Np, st));
+        }
+        CK(dclip_attn_nn_rows(w.dS, s.qkv + D, 3 * D, dqkv, 3 * D, B, H, N, Np, hd, scale, blk, pick, 1, st));   // dQ = dS K
+        return dclip_attn_tn_rows(w.dS, s.qkv, 3 * D, dqkv + D, 3 * D, B, H, N, Np, hd, scale, blk, pick, st);   // dK = dS^T Q
+    }
     CK(dclip_attn_tn(s.Rm, dctx, D, dqkv + 2 * D, 3 * D, B, H, N, Np, hd, 1.f, blk, st));                    // dV = R^T dO
     if (path == AttnPath::Mix) {
         CK(dclip_attn_mix_bwd(s.qkv, 3 * D, dctx, D, wl, ww, s.stats, w.dS, gl ? gl : w.wg_dummy, gw ? gw : w.wg_dummy + H * H,
@@ -413,7 +434,8 @@ int attn_backward(AttnPath path, const Plan& p, const ExecSave& s, const Work& w
 
 // dclip_encoder_run::flags.  The seeds are the residual-gradient accumulator and the last execution's fc2 operand slot (or, after a
 // pruned forward, the compact accumulator) that a backward starts from: clear_backward_seeds.
-enum : uint32_t { RUN_SEEDS_CLEAR = 1u, RUN_PRUNED = 2u };
+// RUN_PRUNED_ATTN: the pruned execution's attention ran on the picked tiles only, so its backward must read those tiles only.
+enum : uint32_t { RUN_SEEDS_CLEAR = 1u, RUN_PRUNED = 2u, RUN_PRUNED_ATTN = 4u };
 
 struct dclip_encoder { Plan p; };
 
@@ -463,11 +485,11 @@ inline EP exec_params(const Plan& p, const void* const* params, int l, int r) {
 
 // first half of a block execution, on all M rows: LN1 -> QKV -> score stage (s.qkv, s.ctx and the path's saved score tensors)
 int exec_attn(const Plan& p, AttnPath path, const ExecSave& s, const bf16_t* W, int l, const EP& e, bool h16, const void* xin, int64_t B,
-              int64_t N, void* st) {
+              int64_t N, const int32_t* pick, void* st) {
     const int64_t D = p.D, M = B * N;
     CK(ln_stream(h16, xin, D, nullptr, e.n1w, e.n1b, s.h1, D, DCLIP_OUT_BF16, s.mean1, s.rstd1, M, D, st));
     CK(gemm(s.h1, D, W + p.bw[l].qkv, D, s.qkv, 3 * D, M, 3 * D, D, e.bq, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));
-    return attn_forward(path, p, s, e.wl, e.ww, B, N, st);
+    return attn_forward(path, p, s, e.wl, e.ww, B, N, pick, st);
 }
 
 // second half, row-local, on the rows of `rs` (see RowSet): z, if there, receives the saved activation derivative, mean2 / rstd2 the LN2
@@ -504,6 +526,11 @@ size_t llo_scratch(const Plan& p, AttnPath path, bool h16, int64_t B, void* base
 // DCLIP_PRUNE_LAST=0 (read once): every forward runs its last block execution on all rows
 inline bool prune_last_enabled() {
     static const int v = [] { const char* e = getenv("DCLIP_PRUNE_LAST"); return e ? atoi(e) : 1; }();
+    return v != 0;
+}
+// DCLIP_PRUNE_ATTN=0 (read once): a pruned last execution still runs its attention on all rows
+inline bool prune_attn_enabled() {
+    static const int v = [] { const char* e = getenv("DCLIP_PRUNE_ATTN"); return e ? atoi(e) : 1; }();
     return v != 0;
 }
 
@@ -641,9 +668,11 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     // ---- blocks --------------------------------------------------------------------------------------------
     // Only the picked token of each sample (class token / EOT = argmax of the ids) leaves the tower, and after the last execution's
     // attention everything is row-local: unless its hidden state or maps are exported, that execution's out_proj, LN2 and MLP run on
-    // the B picked rows only (its attention still runs on all M rows: the picked queries attend to every key).
+    // the B picked rows only, and its attention forms the picked rows' 16-query tiles only (the QKV projection stays on all M rows: the
+    // picked queries attend to every key).
     CK(dclip_pick_index(p.image ? nullptr : (const int64_t*)input, p.N, w.pick, B, N, st));
     const bool prune = prune_last_enabled() && !(rep_out && rep_out[nex - 1]) && !xm.score[nex - 1] && !xm.prob[nex - 1];
+    const bool prune_attn = prune && prune_attn_enabled() && N <= 128;      // (the streaming forward of longer sequences has no row-tile form)
     for (int ei = 0; ei < nex; ++ei) {
         const int l = ei / p.R, r = ei % p.R;
         const ExecSave& s = w.ex[ei];
@@ -651,7 +680,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
         const bool compact = prune && ei == nex - 1;
         ExecSave sa = s;
         if (compact) sa.ctx = w.ctx_full;
-        CK(exec_attn(p, w.path, sa, W, l, ep, w.h16, w.X[ei], B, N, st));
+        CK(exec_attn(p, w.path, sa, W, l, ep, w.h16, w.X[ei], B, N, compact && prune_attn ? w.pick : nullptr, st));
         // before the next execution reuses the inference set's qkv
         if (xm.score[ei] || xm.prob[ei]) CK(dclip_attn_maps_fwd(s.qkv, 3 * D, ep.wl, xm.score[ei], xm.prob[ei], B, p.H, N, p.hd, 1.f / sqrtf((float)p.hd), p.c.causal, st));
         if (compact) {
@@ -667,7 +696,7 @@ extern "C" int dclip_encoder_forward(const dclip_encoder* e, const void* input, 
     CK(ln_stream(w.h16, prune ? w.compact.xout : w.X[nex], D, prune ? nullptr : w.pick, PF(params, p.head.norm_w), PF(params, p.head.norm_b), w.hf, D,
                  DCLIP_OUT_BF16, w.meanf, w.rstdf, B, D, st));
     CK(gemm(w.hf, D, W + p.w_head, D, last_representation, E, B, E, D, PF(params, p.head.head_b), 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_F32, 0, nullptr, st));
-    *run = dclip_encoder_run{prune ? RUN_PRUNED : 0u, 0, 0, 0};
+    *run = dclip_encoder_run{(prune ? RUN_PRUNED : 0u) | (prune_attn ? RUN_PRUNED_ATTN : 0u), 0, 0, 0};
     if (training) {
         CK(clear_backward_seeds(p, w, M, B, prune, st));
         run->flags |= RUN_SEEDS_CLEAR;
@@ -711,7 +740,7 @@ extern "C" int dclip_encoder_last_layer_output(const dclip_encoder* e, int64_t B
         const int ei = nex - 1, l = ei / p.R;
         llo_scratch(p, w.path, w.h16, B, scratch, w.X[ei], t, rs);
         const EP ep = exec_params(p, params, l, ei % p.R);
-        CK(exec_attn(p, w.path, t, W, l, ep, w.h16, w.X[ei], B, p.N, st));
+        CK(exec_attn(p, w.path, t, W, l, ep, w.h16, w.X[ei], B, p.N, nullptr, st));
         CK(exec_mlp(p, W, l, ep, w.h16, rs, st));
         xlast = rs.xout;
     }
@@ -823,7 +852,8 @@ extern "C" int dclip_encoder_backward(const dclip_encoder* e, const void* input,
             CK(dclip_rows_expand(w.Gc, w.G, w.pick, B, N, D * 4, st));
         }
         const MapGrad mg{gm.score[ei], gm.prob[ei], maps ? maps->scratch : nullptr, maps ? maps->scratch_bytes : 0};
-        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, mg.d_score || mg.d_prob ? &mg : nullptr, st));
+        CK(attn_backward(w.path, p, s, w, wl, ww, gl, gw, dctx, dqkv, B, mg.d_score || mg.d_prob ? &mg : nullptr,
+                         compact && (run->flags & RUN_PRUNED_ATTN) ? w.pick : nullptr, st));
         if (r == 0 && GR(bx.qkvw)) CK(dclip_gemm_tn_acc(w.dqkv, 3 * D, s0.h1, D, GR(bx.qkvw), D, MR, 3 * D, D, wsplits(MR, 3 * D, D), w.tn_ws, w.tn_ws_bytes, st));
         if (r == 0 && params[bx.qkvb] && GR(bx.qkvb)) CK(dclip_colsum_acc(w.dqkv, 3 * D, GR(bx.qkvb), MR, 3 * D, st));
         CK(gemm(dqkv, 3 * D, W + bw.qkv_t, 3 * D, w.dh, D, M, D, 3 * D, nullptr, 0, nullptr, nullptr, nullptr, 0, DCLIP_OUT_BF16, 0, nullptr, st));

@@ -134,6 +134,20 @@ def attn_tn(a, bm, ldb, c, ldc, hd, alpha=1.0):
     lib().dclip_attn_tn(_p(a), _p(bm), ldb, _p(c), ldc, B, H, N, Np, hd, alpha, blocked, _stream())
 
 
+def attn_nn_rows(a, bm, ldb, c, ldc, hd, pick, alpha=1.0, fill_zero=False):
+    """attn_nn on the 16-row tile that holds row pick[b] of each sample (include/dclip.h: row-tile forms); pick: int32 [B]"""
+    _chk(pick)
+    B, H, N, Np, blocked = _score_dims(a)
+    lib().dclip_attn_nn_rows(_p(a), _p(bm), ldb, _p(c), ldc, B, H, N, Np, hd, alpha, blocked, _p(pick), 1 if fill_zero else 0, _stream())
+
+
+def attn_tn_rows(a, bm, ldb, c, ldc, hd, pick, alpha=1.0):
+    """attn_tn contracted over the rows of each sample's picked tile only"""
+    _chk(pick)
+    B, H, N, Np, blocked = _score_dims(a)
+    lib().dclip_attn_tn_rows(_p(a), _p(bm), ldb, _p(c), ldc, B, H, N, Np, hd, alpha, blocked, _p(pick), _stream())
+
+
 def unblock_scores(a):
     """quad-blocked [B,H,Np/4,N,4] -> row-major [B,H,N,Np] (tests / diagnostics)"""
     B, H, nq, N, _ = a.shape
@@ -209,6 +223,14 @@ def attn_fused_fwd(qkv, B, N, H, hd, causal=False):
     return ctx
 
 
+def attn_fused_fwd_rows(qkv, ctx, B, N, H, hd, pick, causal=False):
+    """attn_fused_fwd into the rows of each sample's picked tile of `ctx` [B*N, H*hd] bf16; the other rows are left as they are"""
+    _chk(qkv, ctx, pick)
+    lib().dclip_attn_fused_fwd_rows(_p(qkv), qkv.stride(0), _p(ctx), ctx.stride(0), B, H, N, hd, hd ** -0.5, 1 if causal else 0, _p(pick),
+                                    _stream())
+    return ctx
+
+
 def attn_stream_fwd(qkv, B, N, H, hd):
     """attn_fused_fwd for sequences of any length (the frozen ViT-B/16 / ViT-L/14 teachers), non-causal, hd = 64: keys streamed in chunks
     with a running maximum and sum (include/dclip.h: dclip_attn_stream_fwd); qkv: [B*N, 3*H*hd] bf16."""
@@ -271,6 +293,25 @@ def attn_mix_bwd(qkv, d_ctx, B, N, H, hd, wl, ww, stats, scale, dwl, dww):
     lib().dclip_attn_mix_bwd(_p(qkv), qkv.stride(0), _p(d_ctx), d_ctx.stride(0), _p(wl), _p(ww), _p(stats), _p(ds), _p(dwl), _p(dww),
                              _p(ws), ws.numel(), B, H, N, Np, hd, scale, _stream())
     return ds
+
+
+def attn_mix_fwd_rows(qkv, r, stats, wl, ww, scale, pick):
+    """attn_mix_fwd into the rows of each sample's picked tile of `r` (quad-blocked [B,H,Np/4,N,4]) and `stats` [B,H,N]"""
+    _chk(qkv, r, stats, wl, ww, pick)
+    B, H, N, Np, _ = _score_dims(r)
+    lib().dclip_attn_mix_fwd_rows(_p(qkv), qkv.stride(0), _p(wl), _p(ww), _p(r), _p(stats), B, H, N, Np, qkv.shape[1] // (3 * H), scale,
+                                  _p(pick), _stream())
+
+
+def attn_mix_bwd_rows(qkv, d_ctx, ds, wl, ww, stats, scale, dwl, dww, pick, ws=None):
+    """attn_mix_bwd on each sample's picked tile: dS into those rows of `ds` (quad-blocked), dwl / dww +=; `ws`: the workspace to use
+    (uint8, dclip_attn_mix_bwd_workspace_bytes), by default a fresh one"""
+    _chk(qkv, d_ctx, ds, wl, ww, stats, dwl, dww, pick)
+    B, H, N, Np, _ = _score_dims(ds)
+    if ws is None:
+        ws = torch.empty(lib().dclip_attn_mix_bwd_workspace_bytes(B, H, N), dtype=torch.uint8, device=qkv.device)
+    lib().dclip_attn_mix_bwd_rows(_p(qkv), qkv.stride(0), _p(d_ctx), d_ctx.stride(0), _p(wl), _p(ww), _p(stats), _p(ds), _p(dwl), _p(dww),
+                                  _p(ws), ws.numel(), B, H, N, Np, qkv.shape[1] // (3 * H), scale, _p(pick), _stream())
 
 
 def cast_transpose_multi(ws, want_b=True, want_t=True):

@@ -186,6 +186,31 @@ int dclip_attn_mix_bwd(const void* qkv, int64_t ld, const void* dO, int64_t ldo,
                        const float* stats, void* dS, float* dWl, float* dWw, void* workspace, size_t ws_bytes, int64_t B, int64_t H,
                        int64_t N, int64_t Np, int64_t hd, float scale, void* stream);
 /*
+ * Row-tile forms, for a block execution of which only ONE row per sample is read afterwards (the class token / EOT row of a tower's last
+ * execution).  pick: device int32 [B], pick[b] = b * N + n (dclip_pick_index).  Each works on the 16-row tile
+ * it = (pick[b] - b * N) >> 4 of every sample alone, with the fragments, rings and MFMA order of its full form, so what it writes is
+ * bit-equal to the full form's (weight gradients: up to the order in which per-workgroup partials are summed).
+ *   nn_rows       : the tile's rows of C; the other rows are stored as zeros (fill_zero != 0) or left untouched (0).
+ *   tn_rows       : contracts over the tile's rows only; rows of A and Bm outside the tile are never read.  All N rows of C are written.
+ *   fused_fwd_rows: the tile's rows of ctx; other rows untouched.
+ *   mix_fwd_rows  : the tile's rows of R and stats; other rows untouched.
+ *   mix_bwd_rows  : reads stats and writes dS (and the delta rows of the workspace) on the tile's rows only; dWl / dWw += as the full form.
+ * Rows outside the tiles of R, stats and dS therefore hold stale data after these calls: only row-tile forms may consume them.
+ * The backward forms equal the full backward when dO is zero outside the picked rows.  Added without a version bump: no existing
+ * signature changed.
+ */
+int dclip_attn_nn_rows(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t Np,
+                       int64_t hd, float alpha, int a_blocked, const int32_t* pick, int fill_zero, void* stream);
+int dclip_attn_tn_rows(const void* A, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t Np,
+                       int64_t hd, float alpha, int a_blocked, const int32_t* pick, void* stream);
+int dclip_attn_fused_fwd_rows(const void* qkv, int64_t ldq, void* ctx, int64_t ldc, int64_t B, int64_t H, int64_t N, int64_t hd,
+                              float scale, int causal, const int32_t* pick, void* stream);
+int dclip_attn_mix_fwd_rows(const void* qkv, int64_t ld, const float* Wl, const float* Ww, void* R, float* stats, int64_t B, int64_t H,
+                            int64_t N, int64_t Np, int64_t hd, float scale, const int32_t* pick, void* stream);
+int dclip_attn_mix_bwd_rows(const void* qkv, int64_t ld, const void* dO, int64_t ldo, const float* Wl, const float* Ww,
+                            const float* stats, void* dS, float* dWl, float* dWw, void* workspace, size_t ws_bytes, int64_t B, int64_t H,
+                            int64_t N, int64_t Np, int64_t hd, float scale, const int32_t* pick, void* stream);
+/*
  * Head-mean attention maps (attn_maps.hip; the attention_score_mse / attention_probs_mse terms, reference
  * model/loss_component/attention_score_mse.py, attention_probs_mse.py, which only ever read sum(dim=1) / H of a map).
  * maps_fwd : score_map = mean_h S_h, prob_map = mean_h softmax(conv_l(S))_h, f32 [B, N, N] each (nullable), from the packed qkv rows
