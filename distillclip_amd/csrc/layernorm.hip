@@ -213,9 +213,14 @@ __global__ __launch_bounds__(512) void ln_bwd_kernel(const void* __restrict__ dy
 static int ln_fwd_launch(const void* x, int x_f16, int64_t ldx, const int32_t* row_index, const float* gamma, const float* beta, void* y,
                          int64_t ldy, int out, float* mean, float* rstd, int64_t M, int64_t D, float eps, void* stream, const char* who) {
     DCLIP_REQUIRE(x && gamma && beta && y, "%s: null operand", who);
-    DCLIP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "%s: need 0 < D <= 1024, D %% 4 == 0 (D=%ld)", who, (long)D);
-    DCLIP_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)x % (x_f16 ? 8 : 16)) == 0, "%s: row strides must be multiples of 4, rows 8- (fp16) / 16-byte aligned", who);
+    DCLIP_REQUIRE(M > 0, "%s: need M > 0 (M=%ld)", who, (long)M);
+    DCLIP_REQUIRE(D > 0 && D % 4 == 0 && D <= 1024, "%s: need 0 < D <= 1024, D %% 4 == 0 (D=%ld)", who, (long)D);
     DCLIP_REQUIRE(out >= 0 && out <= 2 && (out != 2 || x_f16), "%s: output dtype 0 bf16 / 1 f32 (/ 2 f16 with f16 input)", who);
+    // the kernel moves 4 columns per access: float4 of f32, 8 bytes of fp16 / bf16
+    DCLIP_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "%s: row strides must be multiples of 4 (ldx=%ld, ldy=%ld)", who, (long)ldx, (long)ldy);
+    DCLIP_REQUIRE(((uintptr_t)x % (x_f16 ? 8 : 16)) == 0, "%s: x must be %d-byte aligned", who, x_f16 ? 8 : 16);
+    DCLIP_REQUIRE(((uintptr_t)y % (out == 1 ? 16 : 8)) == 0, "%s: y must be %d-byte aligned", who, out == 1 ? 16 : 8);
+    DCLIP_REQUIRE((uintptr_t)gamma % 16 == 0 && (uintptr_t)beta % 16 == 0, "%s: gamma and beta must be 16-byte aligned", who);
     const int nv = (int)((D + 255) / 256);
     const dim3 grid((unsigned)((M + 3) / 4));
     hipStream_t st = (hipStream_t)stream;
@@ -231,7 +236,8 @@ static int ln_fwd_launch(const void* x, int x_f16, int64_t ldx, const int32_t* r
 extern "C" int dclip_layernorm_fwd(const float* x, int64_t ldx, const int32_t* row_index, const float* gamma,
                                    const float* beta, void* y, int64_t ldy, int out_f32, float* mean, float* rstd,
                                    int64_t M, int64_t D, float eps, void* stream) {
-    return ln_fwd_launch(x, 0, ldx, row_index, gamma, beta, y, ldy, out_f32 ? 1 : 0, mean, rstd, M, D, eps, stream, "dclip_layernorm_fwd");
+    // out_f32 is handed on as the output dtype code, so that 2 (f16) from f32 rows is refused and not read as "true"
+    return ln_fwd_launch(x, 0, ldx, row_index, gamma, beta, y, ldy, out_f32, mean, rstd, M, D, eps, stream, "dclip_layernorm_fwd");
 }
 
 extern "C" int dclip_layernorm_fwd_f16(const void* x, int64_t ldx, const int32_t* row_index, const float* gamma,
@@ -245,7 +251,14 @@ extern "C" int dclip_layernorm_bwd(const void* dy, int64_t lddy, int dy_f32, con
                                    float* dx_acc, int64_t lddx, void* dx_bf16, int64_t lddb, float* dgamma, float* dbeta,
                                    float* colsum_acc, int64_t M, int64_t D, void* stream) {
     DCLIP_REQUIRE(dy && x && gamma && mean && rstd && dx_acc, "dclip_layernorm_bwd: null operand");
-    DCLIP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "dclip_layernorm_bwd: need 0 < D <= 1024, D %% 4 == 0 (D=%ld)", (long)D);
+    DCLIP_REQUIRE(M > 0, "dclip_layernorm_bwd: need M > 0 (M=%ld)", (long)M);
+    DCLIP_REQUIRE(D > 0 && D % 4 == 0 && D <= 1024, "dclip_layernorm_bwd: need 0 < D <= 1024, D %% 4 == 0 (D=%ld)", (long)D);
+    // the kernel moves 4 columns per access: float4 of dy (f32), x, dx_acc and gamma, 8 bytes of dy (bf16) and dx_bf16
+    DCLIP_REQUIRE(lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!dx_bf16 || lddb % 4 == 0),
+                  "dclip_layernorm_bwd: row strides must be multiples of 4 (lddy=%ld, ldx=%ld, lddx=%ld, lddb=%ld)", (long)lddy, (long)ldx, (long)lddx, (long)lddb);
+    DCLIP_REQUIRE(((uintptr_t)dy % (dy_f32 ? 16 : 8)) == 0, "dclip_layernorm_bwd: dy must be %d-byte aligned", dy_f32 ? 16 : 8);
+    DCLIP_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)dx_acc % 16 == 0 && (uintptr_t)gamma % 16 == 0, "dclip_layernorm_bwd: x, dx_acc and gamma must be 16-byte aligned");
+    DCLIP_REQUIRE((uintptr_t)dx_bf16 % 8 == 0, "dclip_layernorm_bwd: dx_bf16 must be 8-byte aligned");
     const int nv = (int)((D + 255) / 256);
     // persistent grid of 8-wave blocks, one per CU (the kernel's registers allow 2 waves per SIMD): every block ends with 3 x D
     // float atomics onto the same 3 D / 32 cache lines, so fewer, fatter blocks are cheaper — as long as every CU has one
