@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void attn_softmax_bwd_plain_kernel(SoftmaxBwd 
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int j = lane + 64 * s;
-                if (j < p.Np) p.dS[base + h * hs + j] = f2bf(pv[s] * (dr[s] - rs));
+                if (j < p.Np) p.dS[base + h * hs + j] = f2bf(j < p.N ? pv[s] * (dr[s] - rs) : 0.f);     // pad columns [N, Np) +0 at every Np, the towers' round_up(N, 8) included: 0 * (0 - rs) gave -0 there for rs > 0
             }
         }
     }
@@ -595,11 +595,11 @@ extern "C" int dclip_trace_attn_stamps(void* buf) { g_attn_stamps = (unsigned lo
 
 extern "C" int dclip_attn_softmax_fwd(const float* S, const float* Wl, const float* Ww, void* P, void* R, int64_t B, int64_t H,
                                       int64_t N, int64_t Np, int causal, void* stream) {
-    DCLIP_REQUIRE(S && R && B > 0 && N > 0 && N <= NMAX && Np % 8 == 0 && Np >= N, "dclip_attn_softmax_fwd: bad argument");
+    DCLIP_REQUIRE(S && R && B > 0 && N > 0 && N <= NMAX && Np % 8 == 0 && Np >= N && Np <= NMAX, "dclip_attn_softmax_fwd: bad argument");
     DCLIP_REQUIRE((Wl == nullptr) == (Ww == nullptr), "dclip_attn_softmax_fwd: conv_l and conv_w come together");
     SoftmaxFwd p{S, Wl, Ww, (bf16_t*)P, (bf16_t*)R, (int)B, (int)N, (int)Np, causal, (int)H};
     TraceScope tr(DCLIP_TRACE_ATTN, Wl ? 4.0 * B * H * H * N * N : 0.0, (4.0 + 2.0 + (P ? 2.0 : 0.0)) * B * H * N * Np, stream, (int)(B * H), (int)N, (int)H, 5);
-    const int ns = N > 64 ? 2 : 1;
+    const int ns = Np > 64 ? 2 : 1;      // 64-key slots of a row, pad columns included: any multiple of 8 with N <= Np <= 128
     hipStream_t st = (hipStream_t)stream;
     if (Wl && !causal && H > 12) {     // H <= 12: the 144-FMA register mix is faster than 32-row MFMA tiles (measured)
         int blocks = (int)((B * N + 3) / 4);
@@ -619,14 +619,14 @@ extern "C" int dclip_attn_softmax_fwd(const float* S, const float* Wl, const flo
 
 extern "C" int dclip_attn_softmax_bwd(const void* dR, const void* P, const void* S, int scores_bf16, const float* Wl, const float* Ww,
                                       void* dS, float* dWl, float* dWw, int64_t B, int64_t H, int64_t N, int64_t Np, void* stream) {
-    DCLIP_REQUIRE(dR && P && dS && B > 0 && N > 0 && N <= NMAX && Np % 8 == 0 && Np >= N, "dclip_attn_softmax_bwd: bad argument");
+    DCLIP_REQUIRE(dR && P && dS && B > 0 && N > 0 && N <= NMAX && Np % 8 == 0 && Np >= N && Np <= NMAX, "dclip_attn_softmax_bwd: bad argument");
     DCLIP_REQUIRE((Wl == nullptr) == (Ww == nullptr), "dclip_attn_softmax_bwd: conv_l and conv_w come together");
     DCLIP_REQUIRE(!Wl || S, "dclip_attn_softmax_bwd: raw scores needed for dW_l");
     SoftmaxBwd p{(const bf16_t*)dR, (const bf16_t*)P, (const float*)S, scores_bf16, Wl, Ww, (bf16_t*)dS, dWl, dWw, (int)B, (int)N, (int)Np, g_attn_stamps, (int)H};
     TraceScope tr(DCLIP_TRACE_ATTN, Wl ? 8.0 * B * H * H * N * N : 0.0, (2.0 + 2.0 + 2.0 + (Wl ? (scores_bf16 ? 2.0 : 4.0) : 0.0)) * B * H * N * Np, stream, (int)(B * H), (int)N, (int)H, 6);
     int blocks = (int)((B * N + 3) / 4);
     if (blocks > 2048) blocks = 2048;
-    const int ns = N > 64 ? 2 : 1;
+    const int ns = Np > 64 ? 2 : 1;      // 64-key slots of a row, pad columns included: any multiple of 8 with N <= Np <= 128
     hipStream_t st = (hipStream_t)stream;
     if (Wl) {
         // ~280 registers -> one resident workgroup per CU: launch one persistent workgroup per CU so the per-workgroup

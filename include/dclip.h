@@ -121,8 +121,11 @@ int dclip_layernorm_bwd(const void* dy, int64_t lddy, int dy_f32, const float* x
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Attention building blocks.  q/k/v/ctx are token-major bf16 (row = b*N + n, column = head*hd + d, row stride ld*);
- * score-like tensors are [B,H,N,Np], Np = round_up(N, 8) in the towers (the product entries take any multiple of 8 with
- * N <= Np <= 128 and refuse others), pad columns [N, Np) zero: nt writes them as +0, nn / tn require them of A.
+ * score-like tensors are [B,H,N,Np], Np = round_up(N, 8) in the towers (the product entries and softmax_fwd / softmax_bwd take any
+ * multiple of 8 with N <= Np <= 128 and refuse others with DCLIP_EINVAL, nothing launched; dclip_attn_mix_* take Np = round_up(N, 8)
+ * alone), pad columns [N, Np) zero: nt and softmax_fwd / softmax_bwd write them as +0 (P, R, dS), nn / tn require them of A and
+ * softmax_bwd of dR and P (the mix backward forms dA = P (dP - rs) on the pad columns inside a real 32-key tile and copies the
+ * pad tiles of dR to dS).
  * hd in {32, 64}, N <= 128 (dclip_attn_stream_fwd alone takes longer sequences).
  *   reference teacher: _common.py:73-89 ; student: weight_share_model.py:101-125 (scale, QK^T, conv_l, softmax,
  *   conv_w, PV) ; causal mask: text_encoder.py:54-60.

@@ -127,6 +127,7 @@ def test_attention_products(B, N, H, hd):
                                               (2, 101, 12, False, False), (2, 21, 3, False, True), (3, 128, 1, False, True),
                                               (2, 65, 6, False, False), (1, 50, 16, False, False)])
 def test_attention_softmax_stage(B, N, H, mix, causal):
+    """(element by element, exact probes and wide Np: tests/test_score_exact_gpu.py)"""
     from distillclip_amd import ops
     Np = (N + 7) // 8 * 8
     s = torch.zeros(B, H, N, Np, device='cuda')
@@ -205,7 +206,8 @@ def test_register_resident_mixed_attention_fwd_bwd(B, N, H, hd):
     (H = 24 / hd = 32 / N = 50 and 101; H = 12 / hd = 64 / N = 77) and a batch that needs more than one persistent round.
     Forward R and the softmax statistics against an fp32 graph on the same bf16 q, k; backward dS, dW_l, dW_w against autograd of
     that graph with dR = dO v^T; and the whole attention (ctx, dq, dk, dv through the unchanged nn / tn products) against the
-    unfused three-kernel path on the same inputs."""
+    unfused three-kernel path on the same inputs.  (Element by element, rows that move the running reference:
+    tests/test_score_exact_gpu.py.)"""
     from distillclip_amd import ops
     D = H * hd
     Np = (N + 7) // 8 * 8
