@@ -1,6 +1,9 @@
 """Validation retrieval metrics: what the reference's `log_acc` / `log_diag_score` compute from a
 logits matrix (dual_distill_model.py:204-224, distil_model.py:171-191), from the embeddings, on the HIP kernel
-`dclip_retrieval_metrics` — the [n, n] logits never reach HBM and torchmetrics is not needed."""
+`dclip_retrieval_metrics` — the [n, n] logits never reach HBM and torchmetrics is not needed.
+
+`retrieval_recall` is the MS-COCO protocol the reference's one-caption validation cannot express: Recall@K with several captions per
+image, both directions, on `dclip_retrieval_recall`."""
 import ctypes
 
 import torch
@@ -35,6 +38,82 @@ def retrieval_metrics(rows, cols, k_list=K_LIST, return_ranks=False):
     res['mean_score'] = out[len(ks) + 1]
     if return_ranks:
         res['ranks'] = ranks
+    return res
+
+
+RECALL_K_LIST = (1, 5, 10)              # the cut-offs MS-COCO retrieval is reported at
+MAX_CUTOFFS = 8                         # include/dclip.h: nk <= 8
+
+
+def caption_offsets(counts, n_img, n_txt):
+    """counts: host list or CPU tensor of n_img non-negative caption counts that sum to n_txt (image i owns the next counts[i] caption
+    rows) -> the n_img + 1 offsets as a list.  Needs no GPU; every complaint is a ValueError."""
+    if torch.is_tensor(counts):
+        if counts.is_cuda:
+            raise ValueError('retrieval_recall: counts is a host list or CPU tensor (reading a device tensor would wait for the device)')
+        counts = counts.reshape(-1).tolist()
+    counts = [int(c) for c in counts]
+    if len(counts) != n_img:
+        raise ValueError(f'retrieval_recall: {len(counts)} caption counts for {n_img} images')
+    if any(c < 0 for c in counts):
+        raise ValueError('retrieval_recall: a caption count is negative')
+    if sum(counts) != n_txt:
+        raise ValueError(f'retrieval_recall: the caption counts sum to {sum(counts)}, text_rows has {n_txt} rows')
+    offs = [0]
+    for c in counts:
+        offs.append(offs[-1] + c)
+    return offs
+
+
+def _check_recall_shapes(image_rows, text_rows, k_list):
+    if image_rows.dim() != 2 or text_rows.dim() != 2 or image_rows.shape[1] != text_rows.shape[1]:
+        raise ValueError(f'retrieval_recall: need [n_img, E] and [n_txt, E] matrices, got {tuple(image_rows.shape)} and '
+                         f'{tuple(text_rows.shape)}')
+    n_img, E = image_rows.shape
+    n_txt = text_rows.shape[0]
+    if E < 16 or E % 16:
+        raise ValueError(f'retrieval_recall: E={E} must be a positive multiple of 16')
+    if not (1 <= n_img < 2 ** 24 and 1 <= n_txt < 2 ** 24):
+        raise ValueError(f'retrieval_recall: need 1 <= n_img, n_txt < 2^24 (n_img={n_img}, n_txt={n_txt})')
+    ks = [int(k) for k in k_list]
+    if len(ks) > MAX_CUTOFFS:
+        raise ValueError(f'retrieval_recall: {len(ks)} cut-offs, at most {MAX_CUTOFFS} per call')
+    return n_img, n_txt, E, ks
+
+
+def retrieval_recall(image_rows, text_rows, counts, k_list=RECALL_K_LIST, return_ranks=False):
+    """Recall@K of image -> text and text -> image retrieval with several captions per image.  image_rows [n_img, E], text_rows [n_txt, E]:
+    un-normalised embeddings (any float dtype); counts: host list or CPU tensor, image i owns the next counts[i] rows of text_rows.
+    An image hits at k when ANY of its captions is among its k best; a caption hits when its image is among the caption's k best; ties
+    favour the target (include/dclip.h: dclip_retrieval_recall).  Images without captions are left out of the image -> text figures.
+    -> {'i2t_recall@{k}', 't2i_recall@{k}', 'i2t_mean_rank', 't2i_mean_rank'} as 0-dim CUDA tensors (views of one result vector; no host
+    sync); with return_ranks also 'i2t_ranks' [n_img] and 't2i_ranks' [n_txt], int32, 0-based, -1 for an image without captions.
+    Every ValueError is raised before any launch."""
+    n_img, n_txt, E, ks = _check_recall_shapes(image_rows, text_rows, k_list)
+    offs = caption_offsets(counts, n_img, n_txt)
+    if not image_rows.is_cuda or not text_rows.is_cuda:
+        raise RuntimeError('distillclip_amd has no CPU path: retrieval_recall needs CUDA (HIP) tensors')
+    dev = image_rows.device
+    img = image_rows.detach().float().contiguous()
+    txt = text_rows.detach().float().contiguous()
+    offsets = torch.tensor(offs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)     # (pageable memory would make the host wait)
+    out = torch.empty(2 * len(ks) + 2, dtype=torch.float32, device=dev)
+    rank_i = torch.empty(n_img, dtype=torch.int32, device=dev) if return_ranks else None
+    rank_t = torch.empty(n_txt, dtype=torch.int32, device=dev) if return_ranks else None
+    ws = torch.empty(max(lib().dclip_retrieval_recall_workspace(n_img, n_txt, E), 16), dtype=torch.uint8, device=dev)
+    karr = (ctypes.c_int32 * max(len(ks), 1))(*ks)
+    lib().dclip_retrieval_recall(img.data_ptr(), txt.data_ptr(), offsets.data_ptr(), n_img, n_txt, E, karr, len(ks), out.data_ptr(),
+                                 rank_i.data_ptr() if return_ranks else None, rank_t.data_ptr() if return_ranks else None,
+                                 ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    res = {}
+    for d, name in enumerate(('i2t', 't2i')):
+        for i, k in enumerate(ks):
+            res[f'{name}_recall@{k}'] = out[d * len(ks) + i]
+    res['i2t_mean_rank'] = out[2 * len(ks)]
+    res['t2i_mean_rank'] = out[2 * len(ks) + 1]
+    if return_ranks:
+        res['i2t_ranks'] = rank_i
+        res['t2i_ranks'] = rank_t
     return res
 
 

@@ -401,6 +401,46 @@ size_t dclip_retrieval_metrics_workspace(int64_t n, int64_t E);
 int dclip_retrieval_metrics(const float* img, const float* txt, int64_t n, int64_t E, const int32_t* ks, int nk,
                             float* out, int32_t* rank_out, void* workspace, size_t ws_bytes, void* stream);
 /*
+ * Recall@K retrieval with several captions per image, both directions, in one call (recall.hip): the MS-COCO protocol (5 000 images x
+ * 25 010 captions on the 5k test split).  The reference's validation pairs each image with one caption (dclip_retrieval_metrics above);
+ * its data set (data/component/ms_coco.py) carries the several captions ranked here.
+ * Logits
+ *   L[i, c] = cos(img_i, txt_c) on raw, un-normalised f32 rows [n_img, E] and [n_txt, E].
+ *   The cosine is 0 when either norm is 0.  This is dclip_clipscore's convention: never NaN for finite rows.
+ * Offsets
+ *   txt_offsets is a DEVICE int32 [n_img + 1] table.
+ *   Caption c belongs to image i iff txt_offsets[i] <= c < txt_offsets[i+1].
+ *   The Python layer validates the counts on the host.
+ *   The kernel clamps every offset into [0, n_txt] and reads end <= start as an empty group.  No table content makes it read or write
+ *   outside its buffers.
+ * Ranks
+ *   rank_i2t[i] is the number of captions not owned by i with L[i, c] > max over i's own captions of L[i, c'].  It is -1 for an image
+ *   without captions.
+ *   rank_t2i[c] is the number of images j != owner(c) with L[j, c] > L[owner(c), c].  It is -1 for a caption no group covers, which can
+ *   only happen with a malformed table.  (owner(c) is the last image i with txt_offsets[i] <= c, when c < txt_offsets[i+1].)
+ *   Comparison is strict: a tie never counts against the target.
+ *   Both sides of a comparison come from the same instruction sequence on the same rows.  Bit-equal rows then give bit-equal logits.
+ * Outputs
+ *   ks is a HOST array of nk <= 8 cut-offs.
+ *   out is device f32 [2 nk + 2]:
+ *     out[0..nk)   = image->text recall@ks over the images that have captions.
+ *     out[nk..2nk) = text->image recall@ks over the covered captions.  A recall is the fraction with 0 <= rank < k.
+ *     out[2nk] and out[2nk+1] = the two mean 0-based ranks over the same sets.
+ *   Hits and rank sums are accumulated as integers.  Each output is the one-time correctly rounded quotient: divided in double, cast once
+ *   (0 for an empty set, which only a malformed table produces).
+ *   rank_i2t (device int32 [n_img]) and rank_t2i (device int32 [n_txt]) are nullable.
+ * Determinism
+ *   The [n_img, n_txt] logits never reach HBM.  No atomics.  The same call gives the same bits.
+ * Limits, refused on the host with a message (DCLIP_EINVAL, nothing launched)
+ *   E must be a positive multiple of 16.  1 <= n_img, n_txt < 2^24.  0 <= nk <= 8.  img, txt and workspace must be 16-byte aligned.
+ *   Null operands and a workspace smaller than dclip_retrieval_recall_workspace(n_img, n_txt, E) are refused.
+ * Added without a version bump: no existing signature changed.
+ */
+size_t dclip_retrieval_recall_workspace(int64_t n_img, int64_t n_txt, int64_t E);
+int dclip_retrieval_recall(const float* img, const float* txt, const int32_t* txt_offsets, int64_t n_img, int64_t n_txt, int64_t E,
+                           const int32_t* ks, int nk, float* out, int32_t* rank_i2t, int32_t* rank_t2i, void* workspace, size_t ws_bytes,
+                           void* stream);
+/*
  * L-CLIPScore scoring: CLIP-S and RefCLIP-S (Hessel et al. 2021) of K candidate captions per image against the image and against a
  * ragged set of reference captions, in one launch (score.hip; the metric the reference's students are trained to be — the reference
  * itself ships no scorer).
