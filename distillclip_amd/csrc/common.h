@@ -72,6 +72,21 @@ static inline int grid_for(int64_t work, int per_block = 256, int cap = 2048 * 4
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// workspaces: every piece starts on a 256-byte boundary; rows read 16 bytes per lane need 16-byte aligned operands
+static inline size_t dclip_up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline bool dclip_aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+// carves a workspace front to back: take<T>(n) is the next piece of n elements, off the bytes handed out so far.  A null base
+// only counts (the workspace-size queries).
+struct Bump {
+    char* base; size_t off;
+    explicit Bump(void* b) : base((char*)b), off(0) {}
+    template <class T> T* take(size_t n) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += dclip_up256(n * sizeof(T));
+        return p;
+    }
+};
+
 __device__ __forceinline__ float bf2f(bf16_t x) { return (float)x; }
 __device__ __forceinline__ bf16_t f2bf(float x) { return (bf16_t)x; }   // v_cvt_pk_bf16_f32: RNE, NaN-preserving
 

@@ -29,18 +29,6 @@ namespace {
         if (_rc != DCLIP_OK) return _rc; \
     } while (0)
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Bump {
-    char* base; size_t off;
-    explicit Bump(void* b) : base((char*)b), off(0) {}
-    template <class T> T* take(size_t n) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += up256(n * sizeof(T));
-        return p;
-    }
-};
-
 // canonical parameter order (see include/dclip.h)
 enum { P_PER_TBLOCK = 12, P_PER_SBLOCK = 8, P_PER_SREPEAT = 6 };
 
@@ -449,7 +437,7 @@ extern "C" dclip_encoder* dclip_encoder_create(const dclip_encoder_cfg* cfg) {
 
 extern "C" void dclip_encoder_destroy(dclip_encoder* e) { delete e; }
 extern "C" int64_t dclip_encoder_num_params(const dclip_encoder* e) { return e ? e->p.n_params : -1; }
-extern "C" size_t dclip_encoder_wcache_bytes(const dclip_encoder* e) { return e ? up256((size_t)e->p.w_total * 2) : 0; }
+extern "C" size_t dclip_encoder_wcache_bytes(const dclip_encoder* e) { return e ? dclip_up256((size_t)e->p.w_total * 2) : 0; }
 
 extern "C" size_t dclip_encoder_workspace_bytes(const dclip_encoder* e, int64_t B, int training) {
     if (!e || B <= 0) return 0;

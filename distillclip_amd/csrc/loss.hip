@@ -14,7 +14,7 @@
 // Every softmax statistic is a natural-log log-sum-exp with the row's true maximum: a running (max, sum) per lane while pass A walks
 // its column tiles, merged across lanes, waves and column slices with the usual rescale (slices in order: deterministic).  A fixed
 // maximum of 1 / tau (cosines are bounded by 1) would underflow the whole row sum once the row's largest cosine sits ~87 tau below 1.
-#include "common.h"
+#include "sim_tiles.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -173,23 +173,9 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------------------
-// stripe kernels.  Tile of X = Xa[rows] . Xb[cols]^T on v_mfma_f32_16x16x4_f32.  The contraction index is permuted
-// so that a lane reads float4s: lane (r = l&15, g = l>>4) covers k = 16*o + 4*g + t at MFMA step t.
+// stripe kernels.  Tile of X = Xa[rows] . Xb[cols]^T on v_mfma_f32_16x16x4_f32: dot_tile() of sim_tiles.h.
 // C layout: acc[q] = X[row 4*g + q][col l & 15].
 // -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ f32x4 logits_tile(const float* __restrict__ xa, const float* __restrict__ xb, int E, int lane) {
-    const float* pa = xa + (int64_t)(lane & 15) * E + (lane >> 4) * 4;
-    const float* pb = xb + (int64_t)(lane & 15) * E + (lane >> 4) * 4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int o = 0; o < E; o += 16) {
-        const float4 av = *(const float4*)(pa + o), bv = *(const float4*)(pb + o);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, acc, 0, 0, 0);
-    }
-    return acc;
-}
 
 // log(exp(a) + exp(b)); -inf stands for an empty sum
 __device__ __forceinline__ float log_add_exp(float a, float b) {
@@ -225,17 +211,17 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
     const float* sa = a.nrm[dir], *sb = a.nrm[1 - dir];           // student rows / cols
     const float* ta = a.nrm[2 + dir], *tb = a.nrm[3 - dir];       // teacher rows / cols
     const float itau = a.c.w_sl != 0.f ? 1.f / a.c.tau : 1.f;
-    const int ia = min(i0 + (lane & 15), B - 1) - (lane & 15);    // clamp the row panel inside the matrix
+    const int64_t ia = (int64_t)min(i0 + (lane & 15), B - 1) * E;   // this lane's row of the panel, clamped inside the matrix
     RunLse r1[4], rs[4], rt[4];
     float pos = 0.f, neg = 0.f, mse = 0.f, diag = 0.f;
     const int ntile = (B + 15) / 16;
     const int z = blockIdx.z, t0 = (int)((int64_t)ntile * z / a.zs), t1 = (int)((int64_t)ntile * (z + 1) / a.zs);   // this slice's column tiles
     for (int jt = t0 + wave; jt < t1; jt += 4) {
         const int j0 = jt * 16;
-        const int jb = min(j0 + (lane & 15), B - 1) - (lane & 15);
-        const f32x4 S = logits_tile(sa + (int64_t)ia * E, sb + (int64_t)jb * E, E, lane);
-        const f32x4 T = logits_tile(ta + (int64_t)ia * E, tb + (int64_t)jb * E, E, lane);
         const int col = j0 + (lane & 15);
+        const int64_t jb = (int64_t)min(col, B - 1) * E;
+        const f32x4 S = dot_tile(sa + ia, sb + jb, E, lane);
+        const f32x4 T = dot_tile(ta + ia, tb + jb, E, lane);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int row = i0 + (lane >> 4) * 4 + q;
@@ -330,7 +316,7 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
     // with gathered statistics: row k of direction d is a.gstats[(d * 3 + k) * B + global index]
     const float* grow = a.gstats ? a.gstats + (int64_t)dir * 3 * B : nullptr;
     const float* gcol = a.gstats ? a.gstats + (int64_t)(1 - dir) * 3 * B : nullptr;
-    const int ia = min(i0 + (lane & 15), B - 1) - (lane & 15);
+    const int64_t ia = (int64_t)min(i0 + (lane & 15), B - 1) * E;
     float rr1[4], rrs[4], rrt[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -346,10 +332,10 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
     float klacc = 0.f;
     for (int jt = t0 + wave; jt < t1; jt += 4) {
         const int j0 = jt * 16;
-        const int jb = min(j0 + (lane & 15), B - 1) - (lane & 15);
-        const f32x4 S = logits_tile(sa + (int64_t)ia * E, sb + (int64_t)jb * E, E, lane);
-        const f32x4 T = logits_tile(ta + (int64_t)ia * E, tb + (int64_t)jb * E, E, lane);
         const int col = j0 + (lane & 15);
+        const int64_t jb = (int64_t)min(col, B - 1) * E;
+        const f32x4 S = dot_tile(sa + ia, sb + jb, E, lane);
+        const f32x4 T = dot_tile(ta + ia, tb + jb, E, lane);
         const int cc = min(col, B - 1);
         const bool cstat = a.c.w_hl != 0.f || a.c.w_sl != 0.f;      // only then (and only with every row owned) are they read
         float c1 = 0.f, cs = 0.f, ct = 0.f;
@@ -470,15 +456,12 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(LossArgs a) {
 }
 __global__ __launch_bounds__(64) void loss_total_kernel(LossArgs a) { loss_write_total(a); }
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-// arrival counters behind the scalar accumulators: one for the call, one per (direction, 16-row stripe)
-
 }  // namespace
 
 extern "C" size_t dclip_distill_loss_workspace(int64_t B, int64_t E) {
-    const size_t be = align_up((size_t)B * E * sizeof(float));
-    const size_t zs = 8;                                     // upper bound of loss_slices() for any row block
-    return (4 + 2 * zs) * be + align_up((size_t)2 * B * 4) + align_up(zs * 6 * B * 4) + align_up((size_t)NREP * SCSTRIDE * 4);
+    const size_t be = dclip_up256((size_t)B * E * sizeof(float));
+    const size_t zs = 8;                                     // upper bound of the column slices for any row block
+    return (4 + 2 * zs) * be + dclip_up256((size_t)2 * B * 4) + dclip_up256(zs * 6 * B * 4) + dclip_up256((size_t)NREP * SCSTRIDE * 4);
 }
 
 namespace {
@@ -509,9 +492,8 @@ int run_distill_loss(const float* s_img, const float* t_img, const float* s_txt,
     DCLIP_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", who);
     a.s[0] = s_img; a.s[1] = s_txt; a.t[0] = t_img; a.t[1] = t_txt; a.ds[0] = d_s_img; a.ds[1] = d_s_txt;
     a.B = (int)B; a.E = (int)E; a.r0 = (int)row0; a.Bl = (int)rows; a.out = out_scalars;
-    char* w = (char*)workspace;
-    const size_t be = align_up((size_t)B * E * sizeof(float));
-    for (int i = 0; i < 4; ++i) { a.nrm[i] = (float*)w; w += be; }
+    Bump w(workspace);
+    for (int i = 0; i < 4; ++i) a.nrm[i] = w.take<float>(B * E);
     // column slices: enough workgroups for the chip from the owned row stripes
     {
         const int rtile = (int)((rows + 15) / 16), ctile = (int)((B + 15) / 16);
@@ -521,16 +503,17 @@ int run_distill_loss(const float* s_img, const float* t_img, const float* s_txt,
         while (zs < 8 && (size_t)16 * (((ctile + zs - 1) / zs) * 16 + 4) * sizeof(float) > 144 * 1024) ++zs;   // LDS stripe budget
         a.zs = zs;
     }
-    for (int i = 0; i < 2; ++i) { a.dsh[i] = (float*)w; w += (size_t)a.zs * be; }
-    a.inv[0] = (float*)w; a.inv[1] = a.inv[0] + rows; w += align_up((size_t)2 * B * 4);
-    a.stats = (float*)w; w += align_up((size_t)a.zs * 6 * B * 4);
-    a.scal = (float*)w;
+    const size_t be = dclip_up256((size_t)B * E * sizeof(float));
+    for (int i = 0; i < 2; ++i) a.dsh[i] = (float*)w.take<char>(a.zs * be);     // one padded [B, E] per slice
+    a.inv[0] = w.take<float>(2 * B); a.inv[1] = a.inv[0] + rows;
+    a.stats = w.take<float>((size_t)a.zs * 6 * B);
+    a.scal = w.take<float>(NREP * SCSTRIDE);
     hipStream_t st = (hipStream_t)stream;
     // algorithmic HBM bytes: read 4*B*E*4 + write 2*rows*E*4 ; the logits contribute none
     TraceScope tr(DCLIP_TRACE_LOSS, 0.0, (a.c.two_tower ? 2.0 : 1.0) * (2.0 * (double)B + (double)rows) * E * 4.0, stream);
     // launches of a call: this fill (the replicated scalar accumulators), rows, and with cross-modal terms stripe A, stripe B
     // and the normalisation backward, whose extra workgroup writes the 16 scalars (round 3: a fifth launch)
-    if (hipMemsetAsync(a.scal, 0, align_up((size_t)NREP * SCSTRIDE * sizeof(float)), st) != hipSuccess) {
+    if (hipMemsetAsync(a.scal, 0, dclip_up256((size_t)NREP * SCSTRIDE * sizeof(float)), st) != hipSuccess) {
         dclip_set_error("%s: memset failed", who);
         return DCLIP_ELAUNCH;
     }

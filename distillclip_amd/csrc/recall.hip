@@ -14,11 +14,12 @@
 //   recall_t2i_kernel     16 captions per workgroup: the target tile (rows = the captions, columns = their owners, diagonal read) first,
 //                         then every image tile; the logits are computed a second time
 //   recall_finalize_kernel  one workgroup: integer hits and rank sums, each output one double division cast once
-// Every logit comes from dot_tile(): v_mfma_f32_16x16x4_f32 is bit for bit an fmaf chain in k order, the order below depends on the row
-// pair only, so bit-equal rows give bit-equal logits wherever they sit, and a tie never counts against the target.
+// Every logit comes from dot_tile() of sim_tiles.h, the tile routine of the loss and of metrics.hip: v_mfma_f32_16x16x4_f32 is bit for bit
+// an fmaf chain in k order, the order there depends on the row pair only, so bit-equal rows give bit-equal logits wherever they sit, and a
+// tie never counts against the target.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "sim_tiles.h"
 
 namespace {
 
@@ -47,17 +48,7 @@ __global__ __launch_bounds__(256) void recall_norm_kernel(RecallArgs a) {
     if (row >= (int64_t)a.n_img + a.n_txt) return;                  // wave-uniform
     const float* src = row < a.n_img ? a.img + row * a.E : a.txt + (row - a.n_img) * a.E;
     float* dst = row < a.n_img ? a.nimg + row * a.E : a.ntxt + (row - a.n_img) * a.E;
-    float s = 0.f;
-    for (int c = lane * 4; c < a.E; c += 256) {
-        const float4 v = *(const float4*)(src + c);
-        s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-    }
-    s = wave_sum(s);
-    const float inv = (s > 0.f && s < __builtin_inff()) ? 1.f / sqrtf(s) : 0.f;
-    for (int c = lane * 4; c < a.E; c += 256) {
-        const float4 v = *(const float4*)(src + c);
-        *(float4*)(dst + c) = float4{v.x * inv, v.y * inv, v.z * inv, v.w * inv};
-    }
+    normalize_row<true>(src, dst, a.E, lane);
 }
 
 // owner[c] = the last image i with off[i] <= c, when c < off[i + 1]; -1 otherwise.  On a well-formed table that is the one group that
@@ -72,23 +63,6 @@ __global__ __launch_bounds__(256) void recall_owner_kernel(RecallArgs a) {
         if (clamped_off(a, mid) <= c) lo = mid; else hi = mid - 1;
     }
     a.owner[c] = (clamped_off(a, lo) <= c && c < clamped_off(a, lo + 1)) ? lo : -1;
-}
-
-// One 16 x 16 tile of dot products.  pa / pb: THIS LANE's row of the A / B panel (row lane & 15; the 16 rows need not be neighbours).
-// Lane (r = l & 15, g = l >> 4) feeds column 16 o + 4 g + t at MFMA step t ; acc[q] = X[A row 4 g + q][B row l & 15].  Each element is the
-// fmaf chain over k = 16 o + 4 g + t in the order (o, t, g): a function of the two rows only.
-__device__ __forceinline__ f32x4 dot_tile(const float* __restrict__ pa, const float* __restrict__ pb, int E, int lane) {
-    pa += (lane >> 4) * 4;
-    pb += (lane >> 4) * 4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int o = 0; o < E; o += 16) {
-        const float4 av = *(const float4*)(pa + o), bv = *(const float4*)(pb + o);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, acc, 0, 0, 0);
-    }
-    return acc;
 }
 
 // grid = ceil(n_img / 16) ; the four waves split the caption tiles
@@ -125,19 +99,10 @@ __global__ __launch_bounds__(256) void recall_i2t_kernel(RecallArgs a) {
         for (int q = 0; q < 4; ++q)
             if (col >= st[q] && col < en[q]) best[q] = fmaxf(best[q], S[q]);      // (en <= n_txt: a clamped column is never inside)
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float b = best[q];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) b = fmaxf(b, __shfl_xor(b, o));
-        if ((lane & 15) == 0) red_b[wave][4 * g + q] = b;
-    }
+    stripe_put(red_b, best, lane, wave, StripeMax());
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int r = 4 * g + q;
-        best[q] = fmaxf(fmaxf(red_b[0][r], red_b[1][r]), fmaxf(red_b[2][r], red_b[3][r]));
-    }
+    for (int q = 0; q < 4; ++q) best[q] = stripe_get(red_b, 4 * g + q, StripeMax());
     int cnt[4] = {0, 0, 0, 0};
     const int ntile = (n_txt + 15) / 16;
     for (int jt = wave; jt < ntile; jt += 4) {
@@ -149,18 +114,11 @@ __global__ __launch_bounds__(256) void recall_i2t_kernel(RecallArgs a) {
             cnt[q] += (col < n_txt && !own && S[q] > best[q]) ? 1 : 0;
         }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int c = cnt[q];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) c += __shfl_xor(c, o);
-        if ((lane & 15) == 0) red_c[wave][4 * g + q] = c;
-    }
+    stripe_put(red_c, cnt, lane, wave, StripeSum());
     __syncthreads();
     if (threadIdx.x < 16 && i0 + threadIdx.x < n_img) {
         const int r = threadIdx.x;
-        const int c = (red_c[0][r] + red_c[1][r]) + (red_c[2][r] + red_c[3][r]);
-        a.rank_i[i0 + r] = s_start[r] < s_end[r] ? c : -1;
+        a.rank_i[i0 + r] = s_start[r] < s_end[r] ? stripe_get(red_c, r, StripeSum()) : -1;
     }
 }
 
@@ -179,6 +137,8 @@ __global__ __launch_bounds__(256) void recall_t2i_kernel(RecallArgs a) {
     const float* pa = a.ntxt + (int64_t)min(c0 + (lane & 15), n_txt - 1) * E;
     // the target tile: column r is the owner of caption r, the diagonal holds L[owner(c), c] (an unowned caption borrows image 0; its
     // rank is not kept)
+    // (this kernel keeps its own spelling of tile_diag() and of the stripe reduction: written with the shared helpers it compiled to
+    // two more VGPRs and measured 1.5 % slower at 5 000 x 25 010 x 512, the k-loop being instruction for instruction the same)
     float d[4];
     {
         const f32x4 S = dot_tile(pa, a.nimg + (int64_t)max(s_owner[lane & 15], 0) * E, E, lane);
@@ -254,8 +214,6 @@ __global__ __launch_bounds__(256) void recall_finalize_kernel(RecallArgs a) {
     }
 }
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 inline bool size_ok(int64_t n_img, int64_t n_txt, int64_t E) {
     return n_img >= 1 && n_txt >= 1 && n_img < (1LL << 24) && n_txt < (1LL << 24) && E > 0 && E % 16 == 0 && E < (1LL << 24);
 }
@@ -264,7 +222,8 @@ inline bool size_ok(int64_t n_img, int64_t n_txt, int64_t E) {
 
 extern "C" size_t dclip_retrieval_recall_workspace(int64_t n_img, int64_t n_txt, int64_t E) {
     if (!size_ok(n_img, n_txt, E)) return 0;
-    return up256((size_t)n_img * E * 4) + up256((size_t)n_txt * E * 4) + up256((size_t)n_img * 4) + 2 * up256((size_t)n_txt * 4);
+    return dclip_up256((size_t)n_img * E * 4) + dclip_up256((size_t)n_txt * E * 4) + dclip_up256((size_t)n_img * 4) +
+           2 * dclip_up256((size_t)n_txt * 4);
 }
 
 extern "C" int dclip_retrieval_recall(const float* img, const float* txt, const int32_t* txt_offsets, int64_t n_img, int64_t n_txt, int64_t E,
@@ -277,19 +236,16 @@ extern "C" int dclip_retrieval_recall(const float* img, const float* txt, const 
     DCLIP_REQUIRE(nk >= 0 && nk <= MAXK && (nk == 0 || ks), "dclip_retrieval_recall: 0 <= nk <= %d cut-offs in a host array (nk=%d)", MAXK, nk);
     DCLIP_REQUIRE(ws_bytes >= dclip_retrieval_recall_workspace(n_img, n_txt, E), "dclip_retrieval_recall: workspace too small (%zu < %zu)",
                   ws_bytes, dclip_retrieval_recall_workspace(n_img, n_txt, E));
-    DCLIP_REQUIRE(aligned16(img) && aligned16(txt) && aligned16(ws) && ((uintptr_t)txt_offsets % 4) == 0 && ((uintptr_t)out % 4) == 0 &&
-                  ((uintptr_t)rank_i2t % 4) == 0 && ((uintptr_t)rank_t2i % 4) == 0,
+    DCLIP_REQUIRE(dclip_aligned16(img) && dclip_aligned16(txt) && dclip_aligned16(ws) && ((uintptr_t)txt_offsets % 4) == 0 &&
+                  ((uintptr_t)out % 4) == 0 && ((uintptr_t)rank_i2t % 4) == 0 && ((uintptr_t)rank_t2i % 4) == 0,
                   "dclip_retrieval_recall: img, txt and workspace must be 16-byte aligned (offsets, out and ranks 4-byte)");
     RecallArgs a;
     a.img = img; a.txt = txt; a.off = txt_offsets;
     a.n_img = (int)n_img; a.n_txt = (int)n_txt; a.E = (int)E; a.nk = nk;
     for (int k = 0; k < MAXK; ++k) a.ks[k] = k < nk ? ks[k] : 0;
-    char* p = (char*)ws;
-    a.nimg = (float*)p; p += up256((size_t)n_img * E * 4);
-    a.ntxt = (float*)p; p += up256((size_t)n_txt * E * 4);
-    a.rank_i = (int*)p; p += up256((size_t)n_img * 4);
-    a.rank_t = (int*)p; p += up256((size_t)n_txt * 4);
-    a.owner = (int*)p;
+    Bump w(ws);
+    a.nimg = w.take<float>(n_img * E); a.ntxt = w.take<float>(n_txt * E);
+    a.rank_i = w.take<int>(n_img); a.rank_t = w.take<int>(n_txt); a.owner = w.take<int>(n_txt);
     a.out = out; a.rank_i2t = rank_i2t; a.rank_t2i = rank_t2i;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(recall_norm_kernel, dim3((unsigned)((n_img + n_txt + 3) / 4)), dim3(256), 0, st, a);

@@ -98,8 +98,6 @@ __global__ __launch_bounds__(256) void clipscore_kernel(ScoreArgs a) {
     }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace
 
 extern "C" int dclip_clipscore(const float* img, int64_t ld_img, const float* cand, int64_t ld_cand, const float* refs, int64_t ld_ref,
@@ -115,8 +113,8 @@ extern "C" int dclip_clipscore(const float* img, int64_t ld_img, const float* ca
     DCLIP_REQUIRE(ld_img >= E && ld_img % 4 == 0 && ld_cand >= E && ld_cand % 4 == 0 && (!refs || (ld_ref >= E && ld_ref % 4 == 0)),
                   "dclip_clipscore: row stride below E=%ld or not a multiple of 4 (ld_img=%ld ld_cand=%ld ld_ref=%ld)", (long)E, (long)ld_img,
                   (long)ld_cand, (long)ld_ref);
-    DCLIP_REQUIRE(aligned16(img) && aligned16(cand) && aligned16(refs) && ((uintptr_t)ref_offsets % 4) == 0 && ((uintptr_t)clip_s % 4) == 0 &&
-                  ((uintptr_t)ref_s % 4) == 0 && ((uintptr_t)refclip_s % 4) == 0,
+    DCLIP_REQUIRE(dclip_aligned16(img) && dclip_aligned16(cand) && dclip_aligned16(refs) && ((uintptr_t)ref_offsets % 4) == 0 &&
+                  ((uintptr_t)clip_s % 4) == 0 && ((uintptr_t)ref_s % 4) == 0 && ((uintptr_t)refclip_s % 4) == 0,
                   "dclip_clipscore: misaligned pointer (img, cand and refs rows are read 16 bytes at a time)");
     ScoreArgs a;
     a.img = img; a.cand = cand; a.refs = refs; a.off = ref_offsets;

@@ -8,6 +8,7 @@ import ctypes
 
 import torch
 
+from ._groups import group_offsets
 from ._lib import lib
 
 K_LIST = (1, 3, 5, 10, 20, 50)          # reference dual_distill_model.py:87, distil_model.py:65
@@ -48,21 +49,7 @@ MAX_CUTOFFS = 8                         # include/dclip.h: nk <= 8
 def caption_offsets(counts, n_img, n_txt):
     """counts: host list or CPU tensor of n_img non-negative caption counts that sum to n_txt (image i owns the next counts[i] caption
     rows) -> the n_img + 1 offsets as a list.  Needs no GPU; every complaint is a ValueError."""
-    if torch.is_tensor(counts):
-        if counts.is_cuda:
-            raise ValueError('retrieval_recall: counts is a host list or CPU tensor (reading a device tensor would wait for the device)')
-        counts = counts.reshape(-1).tolist()
-    counts = [int(c) for c in counts]
-    if len(counts) != n_img:
-        raise ValueError(f'retrieval_recall: {len(counts)} caption counts for {n_img} images')
-    if any(c < 0 for c in counts):
-        raise ValueError('retrieval_recall: a caption count is negative')
-    if sum(counts) != n_txt:
-        raise ValueError(f'retrieval_recall: the caption counts sum to {sum(counts)}, text_rows has {n_txt} rows')
-    offs = [0]
-    for c in counts:
-        offs.append(offs[-1] + c)
-    return offs
+    return group_offsets(counts, n_img, n_txt, 'retrieval_recall', 'caption', 'text_rows')
 
 
 def _check_recall_shapes(image_rows, text_rows, k_list):

@@ -14,9 +14,8 @@ included, and is the hook for it.
 """
 import torch
 
+from ._groups import encode_rows, flatten_groups, tower_pair
 from .metrics import RECALL_K_LIST, MAX_CUTOFFS, caption_offsets, retrieval_recall
-from .model.component.clip_model import CLIPModel
-from .model.component.output import ControlOutput
 
 
 class RetrievalEvaluator:
@@ -38,20 +37,11 @@ class RetrievalEvaluator:
     @classmethod
     def from_model(cls, model, **kw):
         """model: a two-tower distillation model (DualDistillModel: its student is evaluated) or a CLIPModel (student or teacher)"""
-        clip = model if isinstance(model, CLIPModel) else getattr(model, 'student', None)
-        if not isinstance(clip, CLIPModel):
-            raise ValueError(f'RetrievalEvaluator.from_model: {type(model).__name__} has no image and text tower pair (a CLIPModel, or a '
-                             f'two-tower distillation model whose student is one)')
-        return cls(clip.image_encoder, clip.text_encoder, **kw)
+        return cls(*tower_pair(model, 'RetrievalEvaluator'), **kw)
 
     def reset(self):
         """forget the stored rows"""
         self._img, self._txt, self._counts = [], [], []
-
-    def _encode(self, encoder, x):
-        """last_representation [rows, E] of x, in chunks of at most max_batch rows"""
-        parts = [encoder(x[s:s + self.max_batch], ControlOutput()).last_representation for s in range(0, x.shape[0], self.max_batch)]
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
     @torch.no_grad()
     def update(self, images, captions, counts=None):
@@ -60,22 +50,9 @@ class RetrievalEvaluator:
         if images.dim() != 4 or images.shape[0] < 1:
             raise ValueError(f'RetrievalEvaluator: images must be [B, C, H, W] with B >= 1, got {tuple(images.shape)}')
         B = images.shape[0]
-        if captions.dim() == 3:
-            if captions.shape[0] != B:
-                raise ValueError(f'RetrievalEvaluator: dense captions must be [B, Kper, L] with B={B}, got {tuple(captions.shape)}')
-            dense = [captions.shape[1]] * B
-            offs = caption_offsets(dense if counts is None else counts, B, B * captions.shape[1])
-            if [b - a for a, b in zip(offs, offs[1:])] != dense:
-                raise ValueError('RetrievalEvaluator: counts disagrees with the dense [B, Kper, L] captions')
-            captions = captions.reshape(B * captions.shape[1], captions.shape[2])
-        elif captions.dim() == 2:
-            if counts is None:
-                raise ValueError('RetrievalEvaluator: captions [M, L] need counts')
-            offs = caption_offsets(counts, B, captions.shape[0])
-        else:
-            raise ValueError(f'RetrievalEvaluator: captions must be [M, L] or [B, Kper, L], got {tuple(captions.shape)}')
-        img = self._encode(self.image_encoder, images)
-        txt = self._encode(self.text_encoder, captions) if captions.shape[0] else None
+        captions, offs = flatten_groups(captions, counts, B, 'RetrievalEvaluator', caption_offsets, 'captions', 'counts', 'M', 'Kper')
+        img = encode_rows(self.image_encoder, images, self.max_batch)
+        txt = encode_rows(self.text_encoder, captions, self.max_batch) if captions.shape[0] else None
         self._img.append(img)                                       # (stored together: a tower that raised leaves nothing behind)
         if txt is not None:
             self._txt.append(txt)

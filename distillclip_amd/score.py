@@ -16,8 +16,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .model.component.clip_model import CLIPModel
-from .model.component.output import ControlOutput
+from ._groups import encode_rows, flatten_groups, group_offsets, tower_pair
 
 
 class ScoreOutput(NamedTuple):
@@ -27,19 +26,8 @@ class ScoreOutput(NamedTuple):
 
 
 def _counts(ref_counts, B, R):
-    """host list of B non-negative reference counts that sum to R"""
-    if torch.is_tensor(ref_counts):
-        if ref_counts.is_cuda:
-            raise ValueError('LCLIPScore: ref_counts is a host list or CPU tensor (reading a device tensor would wait for the device)')
-        ref_counts = ref_counts.reshape(-1).tolist()
-    counts = [int(c) for c in ref_counts]
-    if len(counts) != B:
-        raise ValueError(f'LCLIPScore: {len(counts)} reference counts for {B} images')
-    if any(c < 0 for c in counts):
-        raise ValueError('LCLIPScore: a reference count is negative')
-    if sum(counts) != R:
-        raise ValueError(f'LCLIPScore: the reference counts sum to {sum(counts)}, references has {R} rows')
-    return counts
+    """host list or CPU tensor of B non-negative reference counts that sum to R -> the B + 1 offsets as a list"""
+    return group_offsets(ref_counts, B, R, 'LCLIPScore', 'reference', 'references', 'ref_counts')
 
 
 class LCLIPScore(nn.Module):
@@ -58,16 +46,7 @@ class LCLIPScore(nn.Module):
     @classmethod
     def from_model(cls, model, **kw):
         """model: a two-tower distillation model (DualDistillModel: its student is scored) or a CLIPModel (student or teacher)"""
-        clip = model if isinstance(model, CLIPModel) else getattr(model, 'student', None)
-        if not isinstance(clip, CLIPModel):
-            raise ValueError(f'LCLIPScore.from_model: {type(model).__name__} has no image and text tower pair (a CLIPModel, or a two-tower '
-                             f'distillation model whose student is one)')
-        return cls(clip.image_encoder, clip.text_encoder, **kw)
-
-    def _encode(self, encoder, x):
-        """last_representation [rows, E] of x, in chunks of at most max_batch rows"""
-        parts = [encoder(x[s:s + self.max_batch], ControlOutput()).last_representation for s in range(0, x.shape[0], self.max_batch)]
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        return cls(*tower_pair(model, 'LCLIPScore'), **kw)
 
     @torch.no_grad()
     def forward(self, images, candidates, references=None, ref_counts=None) -> ScoreOutput:
@@ -85,32 +64,16 @@ class LCLIPScore(nn.Module):
         text = candidates.reshape(B * K, L)
         offsets = None
         if references is not None:
-            if references.dim() == 3:
-                if references.shape[0] != B:
-                    raise ValueError(f'LCLIPScore: dense references must be [B, Rper, L] with B={B}, got {tuple(references.shape)}')
-                dense = [references.shape[1]] * B
-                counts = dense if ref_counts is None else _counts(ref_counts, B, B * references.shape[1])
-                if counts != dense:
-                    raise ValueError('LCLIPScore: ref_counts disagrees with the dense [B, Rper, L] references')
-                references = references.reshape(B * references.shape[1], references.shape[2])
-            elif references.dim() == 2:
-                if ref_counts is None:
-                    raise ValueError('LCLIPScore: references [R, L] need ref_counts')
-                counts = _counts(ref_counts, B, references.shape[0])
-            else:
-                raise ValueError(f'LCLIPScore: references must be [R, L] or [B, Rper, L], got {tuple(references.shape)}')
+            references, offs = flatten_groups(references, ref_counts, B, 'LCLIPScore', _counts, 'references', 'ref_counts', 'R', 'Rper')
             if references.shape[1] != L:
                 raise ValueError(f'LCLIPScore: candidates have {L} tokens, references {references.shape[1]}')
-            offs = [0]
-            for c in counts:
-                offs.append(offs[-1] + c)
             offsets = torch.tensor(offs, dtype=torch.int32)
             if references.shape[0]:
                 text = torch.cat([text, references.to(text.dtype)], dim=0)      # one row set through the text tower
         elif ref_counts is not None:
             raise ValueError('LCLIPScore: ref_counts without references')
-        img = self._encode(self.image_encoder, images)
-        txt = self._encode(self.text_encoder, text)
+        img = encode_rows(self.image_encoder, images, self.max_batch)
+        txt = encode_rows(self.text_encoder, text, self.max_batch)
         refs = None
         if offsets is not None:
             refs = txt[B * K:]

@@ -56,6 +56,28 @@ def test_metrics_val_set_size_properties():
     assert abs(same['mean_score'].item() - 1.0) < 1e-5
 
 
+@pytest.mark.parametrize('n', [1, 17, 33])
+@pytest.mark.parametrize('E', [16, 48])
+def test_one_caption_recall_ranks_equal_metric_ranks(n, E):
+    """dclip_retrieval_metrics and dclip_retrieval_recall count, with strict >, the logits above a target that the same tile routine
+    (csrc/sim_tiles.h: dot_tile) formed from the same operand order: with one caption per image their ranks are equal element for
+    element, ties included.  n: one partial tile, a tile + 1, two tiles + 1 (the clamped panel rows are live); E: the shortest k-loops.
+    Caption rows 3 and 20 copy caption row 5, image row 2 copies image row 7: ties on both sides.  No zero rows (metrics keeps the
+    reference's NaN there)."""
+    from distillclip_amd.metrics import retrieval_metrics, retrieval_recall
+    g = torch.Generator().manual_seed(4000 + 100 * n + E)
+    img, txt = torch.randn(n, E, generator=g), torch.randn(n, E, generator=g)
+    for dup in (3, 20):
+        if n > max(dup, 5):
+            txt[dup] = txt[5]
+    if n > 7:
+        img[2] = img[7]
+    img, txt = img.cuda(), txt.cuda()
+    recall = retrieval_recall(img, txt, [1] * n, return_ranks=True)
+    assert torch.equal(retrieval_metrics(img, txt, return_ranks=True)['ranks'], recall['i2t_ranks'])
+    assert torch.equal(retrieval_metrics(txt, img, return_ranks=True)['ranks'], recall['t2i_ranks'])
+
+
 def test_metrics_argument_errors():
     from distillclip_amd.metrics import retrieval_metrics
     x = torch.randn(8, 24, device='cuda')
