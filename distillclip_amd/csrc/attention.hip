@@ -9,8 +9,8 @@
 //   NT  C[i,j] = a * sum_d A[i,d] B[j,d]     scores S = QK^T ; dR = dO V^T        (fragments straight from HBM/L2)
 //   NN  C[i,d] = a * sum_j A[i,j] B[j,d]     O = R V ; dQ = dS K                  (B through LDS + tr16 reads)
 //   TN  C[j,d] = a * sum_i A[i,j] B[i,d]     dV = R^T dO ; dK = dS^T Q            (A and B through LDS + tr16 reads)
-// The softmax / head-mix stage between NT and NN is attn_softmax.hip; attn_tiles.h holds what the two files share (NMAX, tr_frag) and
-// the output epilogue.  The V / B column permutation (wave_stage_perm4), the Q / K fragment load, the S^T exponent step and the P.V step
+// The softmax / head-mix stage between NT and NN is attn_softmax.hip; attn_tiles.h holds what the two files share (NMAX) and
+// the output epilogue; tr_frag, shared with the wgrad GEMM too, is in common.h.  The V / B column permutation (wave_stage_perm4), the Q / K fragment load, the S^T exponent step and the P.V step
 // are still written out per kernel: hipcc optimises a helper's body before it inlines it and there loses what the kernel knows about
 // its arguments (non-negative indices, the lane range), and every helper form tried changed main-loop code or register counts.
 //

@@ -171,6 +171,23 @@ __device__ __forceinline__ float dg_unpack(unsigned w, int byte) {      // byte:
     return fmaf((float)((w >> (8 * byte)) & 0xffu), DCLIP_DG_STEP, DCLIP_DG_LO);
 }
 
+// bf16x8 MFMA fragment from its two 4-element halves (the two ds_read_b64_tr_b16 of a transposed read)
+__device__ __forceinline__ bf16x8 frag_halves(s16x4 lo, s16x4 hi) {
+    union { struct { s16x4 lo, hi; } s; bf16x8 v; } u;
+    u.s.lo = lo; u.s.hi = hi;
+    return u.v;
+}
+
+// k-major LDS tile fragment (16 columns from x0, 32 rows from r0; rows of ROWB bytes): two ds_read_b64_tr_b16.
+// Lane l gets column x0 + (l & 15), contraction rows r0 + 8 (l >> 4) + (0..7).
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+template <int ROWB>
+__device__ __forceinline__ bf16x8 tr_frag(const char* tile, int r0, int x0, int lane) {
+    const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+    const char* a0 = tile + (r0 + 8 * g + q) * ROWB + (x0 + 4 * pp) * 2;
+    return frag_halves(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0), __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * ROWB)));
+}
+
 // XCD-aware, bijective remap of a linear workgroup id: blocks that share an XCD (same id % 8 under the
 // observed round-robin placement) get a contiguous chunk of the tile space, so neighbouring tiles share an L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -1,4 +1,5 @@
-// gemm.hip (128^2 / 192- / 256- / 320-row kernels): the launch descriptor, the sub-tile swizzle and the per-unit epilogue (8 consecutive output columns of one row, straight from registers).
+// What gemm_nt.hip (forward / dgrad) and gemm_tn.hip (wgrad) share: the forward launch descriptor and its per-unit epilogue (8 consecutive
+// output columns of one row), the sub-tile swizzle, and the tile primitives of both families, each written down once.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -9,6 +10,10 @@ namespace dgemm {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int SUB = 1024;                       // bytes of one [16 x 32] bf16 sub-tile
+constexpr int HT = 16384;                       // bytes of a half-tile of the 256-row pipelines: 128 x 64 bf16, either way round
+
+// profiling stamps of the next launches (dclip_trace_gemm_stamps sets it, both families read it): 6 x u64 per workgroup, or null
+inline unsigned long long* g_gemm_stamps = nullptr;
 
 struct GemmNT {
     const bf16_t* A; int64_t lda;
@@ -60,7 +65,9 @@ __device__ __forceinline__ void epilogue_load_side(const GemmNT& p, int64_t o, i
 // about 40 % of the issue slots of a plain bf16 epilogue, which is issue-bound).  MODE 1 / 2: the launch has no positional table, no
 // residual and no saved pre-activation (ACT 5 / 6 always save their derivative), without / with bias-gradient column sums — the
 // combinations the step's bf16 GEMMs use; the tests are compiled out.
-template <int ACT, int OUT, int MODE = 0>
+// CSUM_ALWAYS: csum takes every unit's output whatever OUT and p.colsum are (gemm_nt_kernel, which launch_nt gives every launch that wants
+// column sums with f32 / f16 output, and which tests p.colsum once per tile); the 256-row kernels leave it off and sum with bf16 output only.
+template <int ACT, int OUT, int MODE = 0, bool CSUM_ALWAYS = false>
 __device__ __forceinline__ void epilogue_vec8(const GemmNT& p, float (&v)[8], int row, int col, int64_t o, int64_t orr,
                                               const float (&bias)[8], float (&csum)[8], const EpiSide& sd) {
     constexpr bool LEAN = MODE != 0;            // MODE 3: f32 / f16 output with the (in-place) residual, nothing else optional
@@ -146,7 +153,7 @@ __device__ __forceinline__ void epilogue_vec8(const GemmNT& p, float (&v)[8], in
         for (int e = 0; e < 8; ++e) ov[e] = f2bf(v[e]);
         *(bf16x8*)((bf16_t*)p.C + o) = ov;
     }
-    if (OUT == 0 && (MODE == 2 || (MODE == 0 && p.colsum))) {
+    if (CSUM_ALWAYS || (OUT == 0 && (MODE == 2 || (MODE == 0 && p.colsum)))) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) csum[e] += v[e];
     }
@@ -154,5 +161,62 @@ __device__ __forceinline__ void epilogue_vec8(const GemmNT& p, float (&v)[8], in
 
 #define WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+
+// workgroup stamp k (off unless dclip_trace_gemm_stamps armed it): s_memtime at 0 start / 1 first operands landed / 2 main loop done /
+// 3 epilogue done (stores acknowledged); slots 4 and 5 take s_memrealtime at start and end.  (Arguments by reference, as a lambda would
+// capture them: by value, hipcc forms gemm_tn256_kernel's wave index and first source addresses differently.)
+__device__ __forceinline__ void wg_stamp(unsigned long long* const& stamps, const int& tid, int k) {
+    if (stamps && tid == 0) {
+        if (k == 3) WAIT_VMCNT(0);
+        stamps[6 * (int64_t)blockIdx.x + k] = __builtin_readcyclecounter();
+        if (k == 0) stamps[6 * (int64_t)blockIdx.x + 4] = __builtin_amdgcn_s_memrealtime();
+        if (k == 3) stamps[6 * (int64_t)blockIdx.x + 5] = __builtin_amdgcn_s_memrealtime();
+    }
+}
+
+// the 128^2 kernels' wave tile: acc[i][j] += a[i] b[j]^T over one 32-wide k block, 4 x 4 tiles of 16 x 16
+__device__ __forceinline__ void mfma_4x4(f32x4 (&acc)[4][4], const bf16x8 (&a)[4], const bf16x8 (&b)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+}
+
+// One phase of the 256-row pipelines between its two barriers: row tiles R0 .. R0 + RT - 1 of the wave x its four column tiles
+// (fragments b0: columns 0, 1; b1: columns 2, 3) x both k halves, at raised priority.  SWAP: the row fragment is the MFMA's second
+// operand (C^T = B A^T, gemm_nt256_kernel).  The caller has retired its own LDS reads (lgkmcnt(0)) before it.
+// A macro, not a function: with the fragment and accumulator arrays handed to a function by reference (forced inline or not, a
+// generic lambda too), hipcc moves 20 of a phase's 32 MFMAs behind the closing barrier, among the next phase's LDS reads — every
+// instruction count stays the same, only the order shows it (tools/diag/isa_compare.py).
+template <bool SWAP>
+__device__ __forceinline__ f32x4 mfma_rc(bf16x8 rowf, bf16x8 colf, f32x4 c) {
+    return SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(colf, rowf, c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowf, colf, c, 0, 0, 0);
+}
+#define PHASE_MFMA(SWAP, acc, R0, RT, af, b0, b1)                                                                         \
+    do {                                                                                                                  \
+        __builtin_amdgcn_s_barrier();                                                                                     \
+        __builtin_amdgcn_s_setprio(1);                                                                                    \
+        _Pragma("unroll") for (int kb_ = 0; kb_ < 2; ++kb_)                                                               \
+            _Pragma("unroll") for (int i_ = 0; i_ < (RT); ++i_) {                                                         \
+                _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                          \
+                    acc[(R0) + i_][j_] = mfma_rc<SWAP>(af[i_][kb_], b0[j_][kb_], acc[(R0) + i_][j_]);                     \
+                _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                          \
+                    acc[(R0) + i_][2 + j_] = mfma_rc<SWAP>(af[i_][kb_], b1[j_][kb_], acc[(R0) + i_][2 + j_]);             \
+            }                                                                                                             \
+        __builtin_amdgcn_s_setprio(0);                                                                                    \
+        __builtin_amdgcn_s_barrier();                                                                                     \
+    } while (0)
+
+// accumulator tiles -> f32 LDS image with rows of LD floats: NI row tiles x 4 column tiles of a wave, from (row0, col0).  acc[i][j][r]
+// is element (i * 16 + (lane >> 4) * 4 + r, j * 16 + (lane & 15)), so storing from registers would mean scattered 4-byte accesses.
+template <int NI, int LD>
+__device__ __forceinline__ void stage_acc(float* cs, const f32x4 (*acc)[4], int row0, int col0, int lane) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) cs[(row0 + i * 16 + (lane >> 4) * 4 + r) * LD + col0 + j * 16 + (lane & 15)] = acc[i][j][r];
+}
 
 }  // namespace dgemm
