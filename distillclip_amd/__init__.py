@@ -6,3 +6,4 @@
 
 from .score import LCLIPScore, ScoreOutput      # noqa: E402,F401  (the scorer: CLIP-S / RefCLIP-S from a trained tower pair)
 from .retrieval import RetrievalEvaluator       # noqa: E402,F401  (Recall@K with several captions per image, both directions)
+from .correlation import HumanCorrelation       # noqa: E402,F401  (Kendall tau-b / tau-c of the scores against human ratings)

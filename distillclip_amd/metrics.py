@@ -3,7 +3,10 @@ logits matrix (dual_distill_model.py:204-224, distil_model.py:171-191), from the
 `dclip_retrieval_metrics` — the [n, n] logits never reach HBM and torchmetrics is not needed.
 
 `retrieval_recall` is the MS-COCO protocol the reference's one-caption validation cannot express: Recall@K with several captions per
-image, both directions, on `dclip_retrieval_recall`."""
+image, both directions, on `dclip_retrieval_recall`.
+
+`kendall_tau` is what a caption metric itself is judged by: Kendall tau-b / tau-c of its scores against human ratings, on
+`dclip_kendall_tau`."""
 import ctypes
 
 import torch
@@ -101,6 +104,49 @@ def retrieval_recall(image_rows, text_rows, counts, k_list=RECALL_K_LIST, return
     if return_ranks:
         res['i2t_ranks'] = rank_i
         res['t2i_ranks'] = rank_t
+    return res
+
+
+KENDALL_MAX_ITEMS = 262144             # include/dclip.h: dclip_kendall_tau takes 2 <= n <= 262 144 ...
+KENDALL_MAX_VECTORS = 4                 # ... and 1 <= C <= 4 score vectors
+KENDALL_COUNTS = ('con', 'dis', 'tie_x', 'tie_y', 'tie_xy', 'distinct_x', 'distinct_y', 'nan')
+
+
+def kendall_tau(scores, human, return_counts=False):
+    """Kendall tau-b and tau-c of a metric's scores against human ratings, as scipy.stats.kendalltau defines them, on
+    `dclip_kendall_tau`: one pass over all pairs with integer counters, so the result is exact and the same call gives the same bits.
+    scores [n] or [C, n] (C <= 4 score vectors, all correlated with the same ratings in one pass), human [n]: device tensors of any
+    float or integer dtype, taken to f32 (equal inputs give equal f32 values, so ties survive).
+    -> {'tau_b', 'tau_c'}: float64 device tensors of shape [] or [C], views of one result buffer; with return_counts also 'counts',
+    int64 [8] or [C, 8] in the order of KENDALL_COUNTS.  A NaN in a score vector makes that vector's taus NaN, a NaN in human all of them.
+    Every ValueError is raised before any launch; nothing waits for the device."""
+    if not torch.is_tensor(scores) or not torch.is_tensor(human) or scores.dim() not in (1, 2) or human.dim() != 1:
+        raise ValueError(f'kendall_tau: need scores [n] or [C, n] and human [n], got {tuple(getattr(scores, "shape", ()))} and '
+                         f'{tuple(getattr(human, "shape", ()))}')
+    many = scores.dim() == 2
+    C, n = (scores.shape[0], scores.shape[1]) if many else (1, scores.shape[0])
+    if human.shape[0] != n:
+        raise ValueError(f'kendall_tau: {n} scores per vector against {human.shape[0]} ratings')
+    if not 2 <= n <= KENDALL_MAX_ITEMS:
+        raise ValueError(f'kendall_tau: need 2 <= n <= {KENDALL_MAX_ITEMS} items (n={n})')
+    if not 1 <= C <= KENDALL_MAX_VECTORS:
+        raise ValueError(f'kendall_tau: need 1 <= C <= {KENDALL_MAX_VECTORS} score vectors per call (C={C})')
+    if not scores.is_cuda or not human.is_cuda:
+        raise ValueError('kendall_tau: scores and human are device tensors (distillclip_amd has no CPU path)')
+    if scores.device != human.device:
+        raise ValueError(f'kendall_tau: scores on {scores.device}, human on {human.device}')
+    dev = scores.device
+    x = scores.detach().float().contiguous()
+    y = human.detach().float().contiguous()
+    tau = torch.empty(C, 2, dtype=torch.float64, device=dev)
+    counts = torch.empty(C, 8, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(lib().dclip_kendall_tau_workspace(n, C), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib().dclip_kendall_tau(x.data_ptr(), n, C, y.data_ptr(), n, tau.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                torch.cuda.current_stream().cuda_stream)
+    res = {'tau_b': tau[:, 0] if many else tau[0, 0], 'tau_c': tau[:, 1] if many else tau[0, 1]}
+    if return_counts:
+        res['counts'] = counts if many else counts[0]
     return res
 
 

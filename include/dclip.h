@@ -460,6 +460,41 @@ int dclip_clipscore(const float* img, int64_t ld_img, const float* cand, int64_t
                     const int32_t* ref_offsets, int64_t B, int64_t K, int64_t R, int64_t E, float w, float* clip_s, float* ref_s,
                     float* refclip_s, void* stream);
 /*
+ * Kendall tau-b and tau-c of C score vectors against one vector of human ratings, in one call (kendall.hip): the rank correlation a
+ * caption metric is judged by (tau-c on Flickr8k-Expert and Composite, tau-b on Flickr8k-CF).  The reference ships no such evaluation.
+ * Inputs
+ *   scores: C vectors of n f32, vector c at scores + c ld, ld >= n.  human: n f32 ratings.  All C vectors are correlated with human in
+ *   the same pass.
+ * Counts
+ *   Over the n0 = n (n - 1) / 2 unordered pairs i < j, with IEEE f32 comparisons (-0 == +0, +-inf order normally, a NaN compares false).
+ *   out_counts is device int64 [C][8]:
+ *     0 con        (x_i - x_j) and (y_i - y_j) have the same non-zero sign
+ *     1 dis        they have opposite non-zero signs
+ *     2 tie_x      x_i == x_j
+ *     3 tie_y      y_i == y_j
+ *     4 tie_xy     both
+ *     5 distinct_x the number of distinct values in x: an element counts when no earlier element equals it
+ *     6 distinct_y the same for y
+ *     7 nan        the number of i for which x_i or y_i is a NaN
+ *   Without a NaN, con + dis + tie_x + tie_y - tie_xy == n0.  Slots 3 and 6 are the same for every c.
+ * Results
+ *   out_tau is device f64 [C][2], formed once in double from the integers as scipy.stats.kendalltau defines them (clipped to [-1, 1]):
+ *     tau_b = (con - dis) / sqrt(n0 - tie_x) / sqrt(n0 - tie_y), NaN when either factor is 0.  It is evaluated with one root,
+ *             (con - dis) / sqrt((n0 - tie_x) (n0 - tie_y)), which makes it exactly 1 for x = y and -1 for x = -y
+ *     tau_c = 2 (con - dis) / (n^2 (m - 1) / m) with m = min(distinct_x, distinct_y), NaN when m == 1
+ *   Both are NaN for a column whose slot 7 is non-zero.  A NaN in one score vector leaves the other columns as they are; a NaN in human
+ *   makes every column NaN.
+ * Determinism
+ *   Integer counters only, no atomics: the same call gives the same bits.  No n makes the kernels read or write outside their buffers.
+ * Limits, refused on the host with a message (DCLIP_EINVAL, nothing launched, nothing written)
+ *   2 <= n <= 262144.  1 <= C <= 4.  ld >= n.  Null operands.  scores and human 4-byte, out_tau and out_counts 8-byte, workspace 16-byte
+ *   aligned.  A workspace smaller than dclip_kendall_tau_workspace(n, C), which is 0 for a refused shape.
+ * Added without a version bump: no existing signature changed.
+ */
+size_t dclip_kendall_tau_workspace(int64_t n, int64_t C);
+int dclip_kendall_tau(const float* scores, int64_t ld, int64_t C, const float* human, int64_t n, double* out_tau, int64_t* out_counts,
+                      void* workspace, size_t ws_bytes, void* stream);
+/*
  * Row block of the same loss for data-parallel global negatives (Collective 2): the four inputs are the GATHERED
  * [B, E] embeddings of all ranks, this call owns rows [row0, row0 + rows) — its own samples — against all B columns.
  * d_s_img / d_s_txt: [rows, E] gradients of the owned samples (d global loss / d embedding).  out_scalars: this block's share of
