@@ -18,7 +18,10 @@ def cosine_with_warmup(step, warm, total):
 
 class FusedAdamW:
     """AdamW over the contiguous trainable ranges of each tower's flat buffer: one multi-range launch (dclip_adamw_multi_scaled) per
-    tower and 24 ranges; a range of odd length or off a 16-byte boundary gets a dclip_adamw launch of its own.
+    tower and 24 ranges; a range of odd length or off a 16-byte boundary gets a dclip_adamw launch of its own.  That holds for the plain
+    step only: a step that clips (max_grad_norm set) or that a loss scaler drives has float4 kernels alone, and step() raises ValueError
+    naming such a range (a tower range or an `extra_params` tensor whose length is no multiple of 4 or which is off a 16-byte boundary)
+    before the step counter advances and before anything is launched or written.
 
     The trainable set is fixed when the optimizer is built, like the reference's AdamW(filter(requires_grad, parameters()))
     (dual_distill_model.py:195, distil_model.py:161): parameters unfrozen later (unfreeze_embed) do not enter it.
@@ -125,7 +128,7 @@ class FusedAdamW:
         """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE multi-range launch per ops.ADAMW_MAX_RANGES ranges (the sharded step
         has one owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower).  A substituted
         `_adamw`, an odd length or a misaligned pointer: one `_adamw` call per range.  record: the scaler-driven step, every range reads
-        that record instead (an odd length or a misaligned pointer is refused by the kernel's entry)."""
+        that record instead (step() has refused an odd length or a misaligned pointer before it began: _refuse_scalar_ranges)."""
         from . import ops
         if record is not None:
             if type(self)._adamw_amp is not FusedAdamW._adamw_amp_hip:
@@ -366,6 +369,29 @@ class FusedAdamW:
         self._prepare(one(found_inf), one(grad_scale), partials, None, self._amp_rec, self._skipped, st)
         return (None if partials is None else self._amp_rec[ops.AMP_NORM:ops.AMP_NORM + 1]), self._amp_rec
 
+    def _refuse_scalar_ranges(self, clip, amp):
+        """A clipping step and a scaler-driven step have float4 kernels only (dclip_sumsq_multi, dclip_adamw_multi_scaled,
+        dclip_adamw_multi_amp): a range of a length that is no multiple of 4, or off a 16-byte boundary, is refused here, on the host,
+        before the step counter moves and before anything is launched, not by a kernel's entry half-way through the step.  (The
+        moments start on an allocation's boundary and share the parameters' offsets.)  A substituted torch version takes any range."""
+        cls = type(self)
+        if not ((clip and (cls._sumsq is FusedAdamW._sumsq_hip or (not amp and cls._adamw is FusedAdamW._adamw_hip)))
+                or (amp and cls._adamw_amp is FusedAdamW._adamw_amp_hip)):
+            return
+        found = []
+        for i, tw in enumerate(self.towers):
+            if tw.flat is None or self._sharded(tw):         # (a sharded tower's owned slices are cut by the plan of parallel.GradSync)
+                continue
+            found += [(f'tower {i} range [{a}, {e})', e - a, tw.flat.data_ptr() + 4 * a, tw.flat_grad.data_ptr() + 4 * a, 4 * a)
+                      for a, e in self._ranges(tw)]
+        found += [(f'extra parameter {i} ({tuple(p.shape)})', p.numel(), p.data_ptr(), p.grad.data_ptr(), 0)
+                  for i, p in enumerate(self.extras) if p.grad is not None]
+        for what, n, *ptrs in found:
+            if n % 4 or any(x % 16 for x in ptrs):
+                raise ValueError(f'FusedAdamW.step: {what} has {n} elements at {ptrs[0]:#x} (gradient at {ptrs[1]:#x}); a step that clips '
+                                 'the gradient norm or is driven by a loss scaler needs every range to be a multiple of 4 elements on a '
+                                 '16-byte boundary.  Only the plain step has an element-wise kernel (dclip_adamw)')
+
     @torch.no_grad()
     def step(self, zero_grad=False, overlap=False, join=True):
         """zero_grad=True: the kernel clears each gradient element once it has consumed it (saves the separate 306 MB fill that
@@ -385,6 +411,7 @@ class FusedAdamW:
             raise RuntimeError('FusedAdamW.step: a loss scaler (precision: 16) cannot drive the sharded data-parallel exchange: after '
                                'backward_and_sync() p.grad holds zeros, so the scaler\'s overflow check sees nothing.  The modes that work '
                                'under precision: 16 are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
+        self._refuse_scalar_ranges(self.max_grad_norm is not None, amp is not None)
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
         on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
