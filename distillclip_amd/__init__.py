@@ -7,3 +7,4 @@
 from .score import LCLIPScore, ScoreOutput      # noqa: E402,F401  (the scorer: CLIP-S / RefCLIP-S from a trained tower pair)
 from .retrieval import RetrievalEvaluator       # noqa: E402,F401  (Recall@K with several captions per image, both directions)
 from .correlation import HumanCorrelation       # noqa: E402,F401  (Kendall tau-b / tau-c of the scores against human ratings)
+from .zeroshot import ZeroShotClassifier        # noqa: E402,F401  (zero-shot top-k accuracy over class prompt ensembles)

@@ -6,7 +6,10 @@ logits matrix (dual_distill_model.py:204-224, distil_model.py:171-191), from the
 image, both directions, on `dclip_retrieval_recall`.
 
 `kendall_tau` is what a caption metric itself is judged by: Kendall tau-b / tau-c of its scores against human ratings, on
-`dclip_kendall_tau`."""
+`dclip_kendall_tau`.
+
+`topk_search` asks the opposite question of the recall figures, which gallery rows are a query's best, on `dclip_topk_search`;
+`group_mean_rows` forms class embeddings from prompt ensembles on `dclip_group_mean_rows` (zeroshot.ZeroShotClassifier uses both)."""
 import ctypes
 
 import torch
@@ -148,6 +151,75 @@ def kendall_tau(scores, human, return_counts=False):
     if return_counts:
         res['counts'] = counts if many else counts[0]
     return res
+
+
+TOPK_MAX_K = 64                         # include/dclip.h: dclip_topk_search takes 1 <= k <= 64
+
+
+def topk_search(query_rows, gallery_rows, k, return_scores=True):
+    """The k best gallery rows of every query by cosine, on `dclip_topk_search`.  query_rows [nq, E], gallery_rows [ng, E]: un-normalised
+    embeddings (any float dtype).  -> (idx int32 [nq, k], score f32 [nq, k], or None without return_scores): row i holds the first k
+    gallery indices in the total order (cosine descending, index ascending) and their cosines; equal cosines come in index order, a row
+    that is zero or holds an inf or a NaN has cosine 0 with everything, and with k > ng the trailing entries are idx -1, score -inf
+    (include/dclip.h).  The [nq, ng] logits never reach HBM, and a cosine is bit for bit the one `retrieval_recall` compares.
+    Out of scope: approximate search and k > 64.  Every ValueError is raised before any launch; nothing waits for the device."""
+    if not torch.is_tensor(query_rows) or not torch.is_tensor(gallery_rows) or query_rows.dim() != 2 or gallery_rows.dim() != 2 or \
+            query_rows.shape[1] != gallery_rows.shape[1]:
+        raise ValueError(f'topk_search: need [nq, E] and [ng, E] matrices, got {tuple(getattr(query_rows, "shape", ()))} and '
+                         f'{tuple(getattr(gallery_rows, "shape", ()))}')
+    nq, E = query_rows.shape
+    ng = gallery_rows.shape[0]
+    k = int(k)
+    if E < 16 or E % 16:
+        raise ValueError(f'topk_search: E={E} must be a positive multiple of 16')
+    if not (1 <= nq < 2 ** 24 and 1 <= ng < 2 ** 24):
+        raise ValueError(f'topk_search: need 1 <= nq, ng < 2^24 (nq={nq}, ng={ng})')
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f'topk_search: need 1 <= k <= {TOPK_MAX_K} (k={k})')
+    if not query_rows.is_cuda or not gallery_rows.is_cuda:
+        raise ValueError('topk_search: query_rows and gallery_rows are device tensors (distillclip_amd has no CPU path)')
+    if query_rows.device != gallery_rows.device:
+        raise ValueError(f'topk_search: query_rows on {query_rows.device}, gallery_rows on {gallery_rows.device}')
+    dev = query_rows.device
+    q = query_rows.detach().float().contiguous()
+    g = gallery_rows.detach().float().contiguous()
+    idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    score = torch.empty(nq, k, dtype=torch.float32, device=dev) if return_scores else None
+    ws = torch.empty(max(lib().dclip_topk_search_workspace(nq, ng, E, k), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib().dclip_topk_search(q.data_ptr(), g.data_ptr(), nq, ng, E, k, idx.data_ptr(), score.data_ptr() if return_scores else None,
+                                ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    return idx, score
+
+
+GROUP_MEAN_MAX_E = 4096                 # include/dclip.h: dclip_group_mean_rows takes E <= 4096
+
+
+def group_mean_rows(rows, counts):
+    """The mean of the normalised rows of each group, on `dclip_group_mean_rows`: class embeddings from prompt ensembles.  rows [n_rows, E]:
+    un-normalised embeddings (any float dtype); counts: host list or CPU tensor, group c owns the next counts[c] rows.
+    -> f32 [n_groups, E]: out[c] = mean over the group of x / |x| (a zero or non-finite row adds nothing, an empty group gives the zero
+    row), rows added in index order without atomics, so the same call gives the same bits.  Every ValueError is raised before any
+    launch; nothing waits for the device."""
+    if not torch.is_tensor(rows) or rows.dim() != 2:
+        raise ValueError(f'group_mean_rows: need an [n_rows, E] matrix, got {tuple(getattr(rows, "shape", ()))}')
+    n_rows, E = rows.shape
+    n_groups = len(counts) if not torch.is_tensor(counts) else counts.numel()
+    offs = group_offsets(counts, n_groups, n_rows, 'group_mean_rows', 'row', 'rows')
+    if E < 16 or E % 16 or E > GROUP_MEAN_MAX_E:
+        raise ValueError(f'group_mean_rows: E={E} must be a positive multiple of 16, at most {GROUP_MEAN_MAX_E}')
+    if not (1 <= n_groups < 2 ** 24 and 1 <= n_rows < 2 ** 24):
+        raise ValueError(f'group_mean_rows: need 1 <= n_groups, n_rows < 2^24 (n_groups={n_groups}, n_rows={n_rows})')
+    if not rows.is_cuda:
+        raise ValueError('group_mean_rows: rows is a device tensor (distillclip_amd has no CPU path)')
+    dev = rows.device
+    x = rows.detach().float().contiguous()
+    offsets = torch.tensor(offs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)     # (pageable memory would make the host wait)
+    out = torch.empty(n_groups, E, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        lib().dclip_group_mean_rows(x.data_ptr(), offsets.data_ptr(), n_groups, n_rows, E, out.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+    return out
 
 
 def gather_rows(x, group=None):

@@ -441,6 +441,49 @@ int dclip_retrieval_recall(const float* img, const float* txt, const int32_t* tx
                            const int32_t* ks, int nk, float* out, int32_t* rank_i2t, int32_t* rank_t2i, void* workspace, size_t ws_bytes,
                            void* stream);
 /*
+ * Top-K search over embeddings (topk.hip): for every query row the k best gallery rows by cosine, with their logits.  It answers what
+ * the entries above cannot: zero-shot classification over class prompts, the k best images for a caption, k-NN, hard negatives.
+ * Logits
+ *   L[i, j] = cos(q_i, g_j) on raw, un-normalised f32 rows [nq, E] and [ng, E].
+ *   It is 0 when either row's squared norm is 0 or not a positive finite number (dclip_retrieval_recall's and dclip_clipscore's
+ *   convention).  A row that holds an inf or a NaN is such a row: it is treated as the zero row.
+ *   Rows are normalised once into the workspace.  Every logit comes from the tile routine of dclip_retrieval_recall, on rows from the
+ *   same normaliser: bit-equal rows give bit-equal logits, and a logit here is bit for bit the one the recall kernels compare.
+ * Order
+ *   Row i of idx holds the first k gallery indices in the total order (L descending, index ascending).
+ *   score[i, p] = L[i, idx[i, p]], exactly as the tile routine produced it (a -0 is reported as +0).
+ *   -0 and +0 compare equal: a zero gallery row ties with any other 0 logit and the lower index wins.
+ *   The order is total, so the result is a function of the logits alone: the same bits on every call, and the result for k1 < k2 is
+ *   the prefix of the result for k2.
+ *   When k > ng, the trailing k - ng entries of a row are idx = -1, score = -inf.
+ * Outputs
+ *   idx is device int32 [nq, k].  score is device f32 [nq, k] and may be NULL.  Both are fully overwritten, with plain stores.
+ * Determinism
+ *   The [nq, ng] logits never reach HBM.  No atomics.  Nothing waits for the device.
+ * Limits, refused on the host with a message (DCLIP_EINVAL, nothing launched)
+ *   1 <= k <= 64.  1 <= nq, ng < 2^24.  E must be a positive multiple of 16.  queries, gallery and workspace must be 16-byte aligned,
+ *   idx and score 4-byte.  Null queries, gallery, idx or workspace, and a workspace smaller than
+ *   dclip_topk_search_workspace(nq, ng, E, k), which is 0 for arguments the search refuses.
+ * Added without a version bump: no existing signature changed.
+ */
+size_t dclip_topk_search_workspace(int64_t nq, int64_t ng, int64_t E, int k);
+int dclip_topk_search(const float* queries, const float* gallery, int64_t nq, int64_t ng, int64_t E, int k, int32_t* idx, float* score,
+                      void* workspace, size_t ws_bytes, void* stream);
+/*
+ * Mean of the normalised rows of each group (topk.hip): class embeddings from prompt ensembles.
+ *   out[c] = (1 / n_c) sum over r in [offsets[c], offsets[c + 1]) of x_r / |x_r|, n_c the number of rows of the group.
+ *   x / |x| is the normaliser of the search above: a row whose squared norm is 0 or not a positive finite number adds nothing.
+ *   An empty group gives the zero row.  The mean is not normalised again: the search normalises its gallery.
+ * offsets is a DEVICE int32 [n_groups + 1] table.  Every offset is clamped into [0, n_rows] by the kernel and end <= start reads as an
+ * empty group, so no table content makes it read outside rows.  The Python layer validates the counts on the host.
+ * rows f32 [n_rows, E], out f32 [n_groups, E], fully overwritten.  One wave per group adds its rows in index order: no atomics, the
+ * same call gives the same bits.
+ * Limits, refused on the host (DCLIP_EINVAL, nothing launched): 1 <= n_groups, n_rows < 2^24.  E a positive multiple of 16, at most
+ * 4096.  Null operands.  rows and out 16-byte, offsets 4-byte aligned.  Added without a version bump.
+ */
+int dclip_group_mean_rows(const float* rows, const int32_t* offsets, int64_t n_groups, int64_t n_rows, int64_t E, float* out,
+                          void* stream);
+/*
  * L-CLIPScore scoring: CLIP-S and RefCLIP-S (Hessel et al. 2021) of K candidate captions per image against the image and against a
  * ragged set of reference captions, in one launch (score.hip; the metric the reference's students are trained to be — the reference
  * itself ships no scorer).
