@@ -396,6 +396,9 @@ int dclip_resize_center_crop(const uint8_t* packed, const dclip_resize_desc* des
  * among the ks[i] highest logits of the row; strict comparison, a tie with the diagonal counts for the diagonal),
  * out[nk] = mean_i softmax(logits_i)[i], out[nk + 1] = mean_i logits_ii.  rank_out (device int32 [n], nullable) receives
  * the number of captions that beat the matching one.  Other pairings (student image x teacher text, ...) are further calls.
+ * A zero row is NaN after the division, and so is every logit it enters: out[nk] and out[nk + 1] are then NaN.  A NaN logit beats
+ * nothing and is beaten by nothing: a zero image row has rank 0 and leaves the other rows' ranks alone, a zero caption row counts for
+ * no row (its own row has rank 0), and the accuracies stay the exact fractions of these ranks (tests/test_metrics_exact_gpu.py).
  */
 size_t dclip_retrieval_metrics_workspace(int64_t n, int64_t E);
 int dclip_retrieval_metrics(const float* img, const float* txt, int64_t n, int64_t E, const int32_t* ks, int nk,
