@@ -18,7 +18,8 @@ SCORE_NAMES = ('clip_s', 'ref_s', 'refclip_s')
 
 
 class HumanCorrelation:
-    """scorer: an LCLIPScore (its towers' parameters, requires_grad and train / eval flags are left alone)."""
+    """scorer: an LCLIPScore (its towers' parameters, requires_grad and train / eval flags are left alone).  The towers run on the weights
+    they hold at the call: `with opt.ema_weights():` (FusedAdamW) around the calls scores the averaged student instead of the last iterate."""
 
     def __init__(self, scorer):
         if not callable(scorer):

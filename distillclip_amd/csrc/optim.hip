@@ -2,10 +2,13 @@
 // torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) with the norm and the coefficient staying on the device.  AdamW
 // (dclip_adamw, dclip_adamw_multi, dclip_adamw_multi_scaled): torch.optim.AdamW on f32 ranges, optionally on g * that coefficient.
 // Under a loss scaler (dclip_amp_prepare, dclip_adamw_multi_amp): the same step driven by a device record that also carries the
-// scaler's 1 / scale, its overflow flag and the bias corrections of the steps that were not skipped.
+// scaler's 1 / scale, its overflow flag and the bias corrections of the steps that were not skipped.  An exponential moving average of the
+// parameters kept by the same kernel (dclip_adamw_multi_ema), and the exchange of parameters and average in place (dclip_swap_multi).
 #include "common.h"
 
 #include <math.h>
+
+#include <type_traits>
 
 namespace {
 
@@ -175,12 +178,26 @@ struct AdamwRanges { float4* p[DCLIP_ADAMW_MAX_RANGES]; float4* g[DCLIP_ADAMW_MA
 // one 16-byte load, the same for every lane) take the place of *gscale, bc1 and bc2_sqrt.  A skipped step writes no p, m or v and
 // reads nothing; the gradients, which hold an overflow, are still cleared on request.
 enum AdamwMode { ADAMW_PLAIN = 0, ADAMW_SCALED = 1, ADAMW_AMP = 2 };
-template <int MODE>
-__global__ __launch_bounds__(256) void adamw4_multi_kernel(AdamwRanges r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                           int zero_grad, const float* __restrict__ gscale) {
+// EMA: a fifth stream e per range, the exponential moving average of the parameters, advanced with weight w = 1 - decay from the p this
+// launch writes (include/dclip.h: dclip_adamw_multi_ema).  The ranges of these instantiations are a struct of their own, which also
+// carries w, so that the kernel arguments of the others stay what they were.  e travels with p, m, v: loaded with the next trip's
+// loads, stored with the current trip's stores, neither read nor written by a skipped step.
+struct AdamwEmaRanges : AdamwRanges { float4* e[DCLIP_ADAMW_MAX_RANGES]; float w; };
+// e <- e + w (p - e): the difference rounded once, then one fmaf, two roundings in all.  p == e gives a difference of 0 and e back as it
+// is (the select keeps the sign of a zero, which 0 + (-0) would lose).
+__device__ __forceinline__ void ema_elem(float& ei, float pi, float w) {
+    const float d = pi - ei;
+    ei = d == 0.f ? ei : fmaf(w, d, ei);
+}
+template <int MODE, bool EMA = false>
+__global__ __launch_bounds__(256) void adamw4_multi_kernel(std::conditional_t<EMA, AdamwEmaRanges, AdamwRanges> r, float lr, float b1, float b2, float eps,
+                                                           float wd, float bc1, float bc2_sqrt, int zero_grad, const float* __restrict__ gscale) {
     constexpr bool SCALED = MODE != ADAMW_PLAIN;
     const int k = blockIdx.y;
     float4* __restrict__ p = r.p[k]; float4* __restrict__ g = r.g[k]; float4* __restrict__ m = r.m[k]; float4* __restrict__ v = r.v[k];
+    float4* __restrict__ e = nullptr;
+    float w = 0.f;
+    if constexpr (EMA) { e = r.e[k]; w = r.w; }
     const int64_t n4 = r.n4[k];
     const int64_t stride = (int64_t)gridDim.x * 256;
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -196,20 +213,49 @@ __global__ __launch_bounds__(256) void adamw4_multi_kernel(AdamwRanges r, float 
         gs = c.x; bc1 = c.z; bc2_sqrt = c.w;
     }
     float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
+    float4 ei = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) ei = e[i];
     for (;;) {
         const int64_t nx = i + stride;
         const bool more = nx < n4;
-        float4 pn = pi, gn = gi, mn = mi, vn = vi;
-        if (more) { pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx]; }
+        float4 pn = pi, gn = gi, mn = mi, vn = vi, en = ei;
+        if (more) {
+            pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx];
+            if constexpr (EMA) en = e[nx];
+        }
         if (SCALED) { gi.x *= gs; gi.y *= gs; gi.z *= gs; gi.w *= gs; }
         adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
         adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
         adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
         adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        if constexpr (EMA) { ema_elem(ei.x, pi.x, w); ema_elem(ei.y, pi.y, w); ema_elem(ei.z, pi.z, w); ema_elem(ei.w, pi.w, w); }
         p[i] = pi; m[i] = mi; v[i] = vi;
+        if constexpr (EMA) e[i] = ei;
         if (zero_grad) g[i] = float4{0.f, 0.f, 0.f, 0.f};
         if (!more) break;
-        i = nx; pi = pn; gi = gn; mi = mn; vi = vn;
+        i = nx; pi = pn; gi = gn; mi = mn; vi = vn; ei = en;
+    }
+}
+
+// Pairs of ranges exchanged word for word (include/dclip.h: dclip_swap_multi).  128-bit integer loads and stores and nothing between
+// them: no value is ever interpreted as a float.  The grid and the order of loads and stores are those of adamw4_multi_kernel.
+struct SwapRanges { uint4* a[DCLIP_ADAMW_MAX_RANGES]; uint4* b[DCLIP_ADAMW_MAX_RANGES]; int64_t n4[DCLIP_ADAMW_MAX_RANGES]; };
+__global__ __launch_bounds__(256) void swap4_multi_kernel(SwapRanges r) {
+    const int k = blockIdx.y;
+    uint4* a = r.a[k]; uint4* b = r.b[k];                // (no __restrict__: a range may be exchanged with itself)
+    const int64_t n4 = r.n4[k];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    uint4 ai = a[i], bi = b[i];
+    for (;;) {
+        const int64_t nx = i + stride;
+        const bool more = nx < n4;
+        uint4 an = ai, bn = bi;
+        if (more) { an = a[nx]; bn = b[nx]; }
+        a[i] = bi; b[i] = ai;
+        if (!more) break;
+        i = nx; ai = an; bi = bn;
     }
 }
 
@@ -241,6 +287,14 @@ int adamw_multi_launch(const char* what, float* const* p, float* const* g, float
     hipLaunchKernelGGL(gscale ? adamw4_multi_kernel<ADAMW_SCALED> : adamw4_multi_kernel<ADAMW_PLAIN>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps,
                        weight_decay, bc1, bc2, zero_grad, gscale);
     return dclip_check_launch(what);
+}
+
+// dclip_adamw_multi_ema's launch: the instantiation of `mode`, with the average (R = AdamwEmaRanges) or without (R = AdamwRanges)
+template <bool EMA, class R>
+void adamw_ema_launch(int mode, dim3 grid, hipStream_t stream, const R& r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, int zero_grad,
+                      const float* dev) {
+    auto kernel = mode == ADAMW_PLAIN ? adamw4_multi_kernel<ADAMW_PLAIN, EMA> : mode == ADAMW_SCALED ? adamw4_multi_kernel<ADAMW_SCALED, EMA> : adamw4_multi_kernel<ADAMW_AMP, EMA>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, r, lr, b1, b2, eps, wd, bc1, bc2, zero_grad, dev);
 }
 
 }  // namespace
@@ -299,6 +353,51 @@ extern "C" int dclip_adamw_multi_amp(float* const* p, float* const* g, float* co
     hipLaunchKernelGGL(adamw4_multi_kernel<ADAMW_AMP>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f,
                        zero_grad, record);
     return dclip_check_launch("dclip_adamw_multi_amp");
+}
+
+extern "C" int dclip_adamw_multi_ema(float* const* p, float* const* g, float* const* m, float* const* v, float* const* e, const int64_t* n, int32_t count,
+                                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, float ema_weight,
+                                     const float* gscale, const float* record, void* stream) {
+    const char* what = "dclip_adamw_multi_ema";
+    DCLIP_REQUIRE(e, "%s: bad argument (e is NULL)", what);
+    DCLIP_REQUIRE(!(gscale && record), "%s: gscale (a clipped step) and record (a scaler-driven step) exclude each other", what);
+    DCLIP_REQUIRE(ema_weight >= 0.f && ema_weight <= 1.f, "%s: ema_weight = 1 - decay must lie in [0, 1] (got %g)", what, (double)ema_weight);   // (a NaN fails both)
+    DCLIP_REQUIRE(record ? ((uintptr_t)record & 15) == 0 : step >= 1, "%s: bad argument (a 16-byte aligned record of dclip_amp_prepare, or step >= 1)", what);
+    AdamwEmaRanges r;
+    dim3 grid;
+    const int rc = adamw_ranges(what, p, g, m, v, n, count, r, grid);
+    if (rc != DCLIP_OK) return rc;
+    for (int k = 0; k < count; ++k) {
+        DCLIP_REQUIRE(e[k] && ((uintptr_t)e[k] & 15) == 0, "%s: e of range %d must be non-NULL and 16-byte aligned", what, k);
+        r.e[k] = (float4*)e[k];
+    }
+    r.w = ema_weight;
+    const int mode = record ? ADAMW_AMP : gscale ? ADAMW_SCALED : ADAMW_PLAIN;
+    const float bc1 = record ? 0.f : 1.f - powf(beta1, (float)step);
+    const float bc2 = record ? 0.f : sqrtf(1.f - powf(beta2, (float)step));
+    const float* dev = record ? record : gscale;
+    if (ema_weight == 0.f)                                   // the average stands still: the step alone, e neither read nor written
+        adamw_ema_launch<false>(mode, grid, (hipStream_t)stream, (const AdamwRanges&)r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad, dev);
+    else
+        adamw_ema_launch<true>(mode, grid, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad, dev);
+    return dclip_check_launch(what);
+}
+
+extern "C" int dclip_swap_multi(float* const* a, float* const* b, const int64_t* n, int32_t count, void* stream) {
+    DCLIP_REQUIRE(a && b && n && count > 0 && count <= DCLIP_ADAMW_MAX_RANGES, "dclip_swap_multi: bad argument (1..%d ranges)", DCLIP_ADAMW_MAX_RANGES);
+    SwapRanges r;
+    int64_t longest = 0;
+    for (int k = 0; k < count; ++k) {
+        DCLIP_REQUIRE(a[k] && b[k] && n[k] > 0 && n[k] % 4 == 0 && ((((uintptr_t)a[k] | (uintptr_t)b[k]) & 15) == 0),
+                      "dclip_swap_multi: range %d must be non-empty, a multiple of 4 elements and 16-byte aligned", k);
+        const uintptr_t lo = (uintptr_t)a[k] < (uintptr_t)b[k] ? (uintptr_t)a[k] : (uintptr_t)b[k], hi = (uintptr_t)a[k] ^ (uintptr_t)b[k] ^ lo;
+        DCLIP_REQUIRE(lo == hi || hi - lo >= (uintptr_t)n[k] * sizeof(float), "dclip_swap_multi: the two sides of range %d overlap without being the same range", k);
+        r.a[k] = (uint4*)a[k]; r.b[k] = (uint4*)b[k]; r.n4[k] = n[k] / 4;
+        longest = r.n4[k] > longest ? r.n4[k] : longest;
+    }
+    const int per_pair = 8192 / count < 256 ? 256 : 8192 / count;            // (adamw_ranges' grid)
+    hipLaunchKernelGGL(swap4_multi_kernel, dim3(grid_for(longest, 256, per_pair), (unsigned)count), dim3(256), 0, (hipStream_t)stream, r);
+    return dclip_check_launch("dclip_swap_multi");
 }
 
 extern "C" int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

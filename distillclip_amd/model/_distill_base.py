@@ -56,6 +56,14 @@ def pair_attention_maps(student, teacher):
 
 
 class DistillBase(nn.Module):
+    # Plain attributes, set on the module before configure_optimizers() / validation (the reference has neither: the defaults are its
+    # behaviour).  ema_decay: handed to FusedAdamW, which then keeps an exponential moving average of the student weights inside its
+    # step.  validate_with_ema: the validation loop runs on that average (on_validation_start / on_validation_end).
+    ema_decay = None
+    validate_with_ema = False
+    _optimizer = None              # the optimizer configure_optimizers() built
+    _ema_context = None            # the entered FusedAdamW.ema_weights() of a validation loop
+
     def towers(self):
         """the student towers (HipTower), in the order the optimizer and the gradient exchange see them"""
         raise NotImplementedError
@@ -99,10 +107,24 @@ class DistillBase(nn.Module):
             tw.materialize(dev)
         extras = [p for tw in towers                             # a plain CLIP student's projection linears (tw.module: its encoder)
                   for p in getattr(tw.module, 'extra_parameters', lambda: [])()]
-        opt = FusedAdamW(towers, lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras)
+        opt = FusedAdamW(towers, lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras, ema_decay=self.ema_decay)
+        self._optimizer = opt
         sched = EpochCosineSchedule(opt, self.hparams.warm_steps, self.hparams.total_steps)
         self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with
         return [opt], [sched]
+
+    def on_validation_start(self):
+        """validate_with_ema and an average exists (FusedAdamW.ema_decay): the student towers hold the averaged weights until
+        on_validation_end.  Otherwise nothing happens and validation scores the last iterate, as the reference does."""
+        opt = self._optimizer
+        if self.validate_with_ema and opt is not None and opt._has_ema() and self._ema_context is None:
+            self._ema_context = opt.ema_weights()
+            self._ema_context.__enter__()
+
+    def on_validation_end(self):
+        ctx, self._ema_context = self._ema_context, None
+        if ctx is not None:
+            ctx.__exit__(None, None, None)
 
     def configure_gradient_clipping(self, optimizer, *args, gradient_clip_val=None, gradient_clip_algorithm=None, **kw):
         """Lightning's hook for the trainer keys gradient_clip_val / gradient_clip_algorithm: called before every optimizer step as

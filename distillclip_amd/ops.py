@@ -397,6 +397,34 @@ def adamw_multi_amp(items, lr, betas, eps, weight_decay, zero_grad, record, stre
                                 _p(record), _stream() if stream is None else stream)
 
 
+def adamw_multi_ema(items, lr, betas, eps, weight_decay, step, zero_grad, ema_weight, gscale=None, record=None, stream=None):
+    """AdamW on at most 24 ranges [(p, g, m, v, e)] in ONE launch, e <- e + ema_weight * (p' - e) on the parameters it writes
+    (include/dclip.h: dclip_adamw_multi_ema).  gscale: adamw_multi_scaled's multiplier; record: adamw_multi_amp's record (`step` is then
+    not read); not both.  ema_weight: float(numpy.float32(1.0 - decay)), the subtraction in double."""
+    import ctypes
+    for it in items:
+        _chk(*it)
+    _chk(gscale, record)
+    n = len(items)
+    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items])
+    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
+    lib().dclip_adamw_multi_ema(arr(0), arr(1), arr(2), arr(3), arr(4), lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
+                                1 if zero_grad else 0, ema_weight, _p(gscale), _p(record), _stream() if stream is None else stream)
+
+
+def swap_multi(pairs, stream=None):
+    """a <-> b, bit for bit, for at most 24 pairs [(a, b)] of equally long 1-D f32 tensors in ONE launch (include/dclip.h: dclip_swap_multi)"""
+    import ctypes
+    for a, b in pairs:
+        _chk(a, b)
+        if a.numel() != b.numel():
+            raise ValueError('swap_multi: the two sides of a pair have %d and %d elements' % (a.numel(), b.numel()))
+    n = len(pairs)
+    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in pairs])
+    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in pairs])
+    lib().dclip_swap_multi(arr(0), arr(1), lens, n, _stream() if stream is None else stream)
+
+
 def clipscore(img, cand, refs=None, ref_offsets=None, *, K=1, w=2.5):
     """CLIP-S / RefCLIP-S of K candidates per image in ONE launch (include/dclip.h: dclip_clipscore).  img f32 [B, E], cand f32 [B * K, E]
     (row b * K + k belongs to image b), refs f32 [R, E] with ref_offsets int32 [B + 1] on the device (CSR into refs), or neither: raw,

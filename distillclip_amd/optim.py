@@ -1,7 +1,9 @@
 """Fused AdamW over the towers' flat parameter buffers (reference distil_model.py:160-169,
 dual_distill_model.py:194-202: AdamW over every requires_grad parameter in one group + HF cosine-with-warmup
 stepped per epoch)."""
+import contextlib
 import math
+import struct
 
 import torch
 
@@ -45,11 +47,24 @@ class FusedAdamW:
     and does not advance the bias corrections (t = step_count - skipped); state_dict() writes that t.  The gradients themselves
     are consumed as they are: p.grad is not written back unscaled (torch's fused AdamW does that).  Once steps have been taken
     through a scaler, keep stepping through it: a plain step() takes its bias corrections from step_count alone.  Not with the
-    sharded data-parallel exchange: there p.grad holds zeros when the scaler looks for overflows, so step() refuses."""
+    sharded data-parallel exchange: there p.grad holds zeros when the scaler looks for overflows, so step() refuses.
+
+    ema_decay (None = off; a plain attribute, may change between steps): the step also keeps an exponential moving average of the
+    parameters it updates, e <- e + (1 - ema_decay) * (p' - e) with p' the parameter the step has just written, in the same kernel
+    (dclip_adamw_multi_ema): one more f32 buffer per tower in the layout of m / v and one per extra parameter, allocated by the first
+    step() that finds a decay set and filled from the parameters as they are before that step; no launch more per step after it, no
+    host synchronisation, and a step that a loss scaler skips leaves the average where it is.  1 - ema_decay is formed in double and
+    rounded once.  The usual warm-up, so that the average does not stay at the initial weights for the first 1 / (1 - d) steps, is
+    host arithmetic before each step: `opt.ema_decay = min(d, (1 + t) / (10 + t))` with t = opt.step_count.  Back to None freezes the
+    average and keeps it.  An EMA step has float4 kernels only (an odd or misaligned range is refused like a clipping step's), and
+    step() refuses it under the sharded data-parallel exchange, where every rank holds 1/W of the optimizer state
+    (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off work).  `with opt.ema_weights():` runs the towers on the average;
+    ema_state_dict() exports it; state_dict() carries it under 'ema', next to 'state' and 'param_groups', which stay what
+    torch.optim.AdamW loads."""
 
     _step_supports_amp_scaling = True
 
-    def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None):
+    def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None, ema_decay=None):
         """extra_params: trainable parameters that live outside the towers' flat buffers — the embedding_projection / hidden_projection
         linears of a plain CLIP encoder in the student role (reference image_encoder.py:23-25, text_encoder.py:45-47): four small tensors
         whose gradients autograd produces; they are updated together, like one more tower's ranges (after an all-reduce of each gradient
@@ -72,6 +87,10 @@ class FusedAdamW:
         self.last_grad_norm = None
         self._clip_parts = self._clip_out = None
         self._amp_rec = self._skipped = None               # the scaler-driven step's device record and its count of skipped steps
+        self.ema_decay = ema_decay
+        self._ema = {}                                     # id(tower) -> the average, in the tower's flat layout ; id(extra parameter) -> 1-D
+        self._ema_unseeded = set()                         # keys of _ema allocated by the step in flight, not yet filled from the parameters
+        self._ema_in_use = False                           # inside ema_weights(): parameters and average have changed places
 
     def _ranges(self, tw):
         """contiguous [begin, end) element ranges of the parameters this optimizer was built over"""
@@ -124,12 +143,30 @@ class FusedAdamW:
 
     _adamw_amp = _adamw_amp_hip
 
-    def _adamw_many(self, items, zero_grad, st, gscale=None, record=None):
+    def _adamw_ema_hip(self, items, zero_grad, st, ema_weight, gscale, record):
+        """items: at most ops.ADAMW_MAX_RANGES of (p, g, m, v, e).  (`_adamw_ema` and `_swap` can be substituted by torch versions like `_adamw`.)"""
+        from . import ops
+        ops.adamw_multi_ema(items, self.lr, self.betas, self.eps, self.weight_decay, self.step_count, zero_grad, ema_weight, gscale, record, st)
+
+    _adamw_ema = _adamw_ema_hip
+
+    def _swap_hip(self, pairs, st):
+        from . import ops
+        ops.swap_multi(pairs, st)
+
+    _swap = _swap_hip
+
+    def _adamw_many(self, items, zero_grad, st, gscale=None, record=None, ema_weight=None):
         """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE multi-range launch per ops.ADAMW_MAX_RANGES ranges (the sharded step
         has one owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower).  A substituted
         `_adamw`, an odd length or a misaligned pointer: one `_adamw` call per range.  record: the scaler-driven step, every range reads
-        that record instead (step() has refused an odd length or a misaligned pointer before it began: _refuse_scalar_ranges)."""
+        that record instead (step() has refused an odd length or a misaligned pointer before it began: _refuse_scalar_ranges).
+        ema_weight: items are [(p, g, m, v, e)] and every launch is dclip_adamw_multi_ema, whichever of the three steps it is."""
         from . import ops
+        if ema_weight is not None:                           # items: [(p, g, m, v, e)], plain, clipped or scaler-driven alike
+            for i in range(0, len(items), ops.ADAMW_MAX_RANGES):
+                self._adamw_ema(items[i:i + ops.ADAMW_MAX_RANGES], zero_grad, st, ema_weight, gscale, record)
+            return
         if record is not None:
             if type(self)._adamw_amp is not FusedAdamW._adamw_amp_hip:
                 for p, g, m, v in items:
@@ -253,9 +290,18 @@ class FusedAdamW:
             tw.opt_done.record(s)
         return s
 
-    def _jobs(self, overlap, main, clip):
+    def _ema_of(self, key, like):
+        """the average kept under `key`, in the layout of the f32 tensor `like`; a new one is filled by the step that asked for it"""
+        e = self._ema.get(key)
+        if e is None:
+            e = self._ema[key] = torch.empty(like.numel(), dtype=torch.float32, device=like.device)
+            self._ema_unseeded.add(key)
+        return e
+
+    def _jobs(self, overlap, main, clip, ema=False):
         """[(tower, stream, items, sharded)] of the materialised towers, in tower order: the stream the tower's update runs on and the
-        [(p, g, m, v)] ranges it updates (a sharded tower's: only for the sums of a clipping step, _step_sharded takes its own)"""
+        [(p, g, m, v)] ranges it updates (a sharded tower's: only for the sums of a clipping step, _step_sharded takes its own);
+        ema: [(p, g, m, v, e)]"""
         from .model.component._tower import autograd_params_mode
         jobs = []
         for tw in self.towers:
@@ -267,7 +313,11 @@ class FusedAdamW:
                 continue
             # (gradients that went through autograd may have been written by anybody's stream — a DDP reducer's —: take them on `main`)
             stream = tw.bwd_stream if (overlap and not autograd_params_mode(tw) and getattr(tw, 'bwd_stream', None) is not None) else main
-            jobs.append((tw, stream, [(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)], False))
+            items = [(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)]
+            if ema:
+                avg = self._ema_of(id(tw), tw.flat)
+                items = [it + (avg[b:e],) for it, (b, e) in zip(items, self._ranges(tw))]
+            jobs.append((tw, stream, items, False))
         return jobs
 
     def _await_grads(self, job, main):
@@ -284,9 +334,10 @@ class FusedAdamW:
             with GradSync._On(stream):
                 self._pack_autograd_grads(tw)
 
-    def _update(self, job, zero_grad, overlap, main, coef=None, record=None):
+    def _update(self, job, zero_grad, overlap, main, coef=None, record=None, ema_weight=None):
         """one tower's AdamW, on g * coef if given or driven by the scaler's record, and what follows it on the tower's stream.  Returns
-        the stream the current one has to join, None if there is none."""
+        the stream the current one has to join, None if there is none.  ema_weight: the step keeps the average; a new average is
+        first filled from the whole flat buffer (frozen ranges too: they never change), on the same stream."""
         from .parallel import GradSync
         tw, stream, items, sharded = job
         if sharded:
@@ -294,7 +345,10 @@ class FusedAdamW:
         if (coef is not None or record is not None) and stream != main:
             stream.wait_stream(main)
         with GradSync._On(stream):
-            self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef, record)
+            if id(tw) in self._ema_unseeded:
+                self._ema[id(tw)].copy_(tw.flat)
+                self._ema_unseeded.discard(id(tw))
+            self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef, record, ema_weight)
             tw.wcache_dirty = True
             tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
             if overlap and self.refresh_cache_in_step:
@@ -369,14 +423,18 @@ class FusedAdamW:
         self._prepare(one(found_inf), one(grad_scale), partials, None, self._amp_rec, self._skipped, st)
         return (None if partials is None else self._amp_rec[ops.AMP_NORM:ops.AMP_NORM + 1]), self._amp_rec
 
-    def _refuse_scalar_ranges(self, clip, amp):
-        """A clipping step and a scaler-driven step have float4 kernels only (dclip_sumsq_multi, dclip_adamw_multi_scaled,
-        dclip_adamw_multi_amp): a range of a length that is no multiple of 4, or off a 16-byte boundary, is refused here, on the host,
+    def _refuse_scalar_ranges(self, clip, amp, ema=False):
+        """A clipping step, a scaler-driven step and a step that keeps an EMA have float4 kernels only (dclip_sumsq_multi,
+        dclip_adamw_multi_scaled, dclip_adamw_multi_amp, dclip_adamw_multi_ema): a range of a length that is no multiple of 4, or off a 16-byte boundary, is refused here, on the host,
         before the step counter moves and before anything is launched, not by a kernel's entry half-way through the step.  (The
-        moments start on an allocation's boundary and share the parameters' offsets.)  A substituted torch version takes any range."""
+        moments and the average start on an allocation's boundary and share the parameters' offsets.)  A substituted torch version
+        takes any range."""
         cls = type(self)
-        if not ((clip and (cls._sumsq is FusedAdamW._sumsq_hip or (not amp and cls._adamw is FusedAdamW._adamw_hip)))
-                or (amp and cls._adamw_amp is FusedAdamW._adamw_amp_hip)):
+        if ema:
+            if cls._adamw_ema is not FusedAdamW._adamw_ema_hip and not (clip and cls._sumsq is FusedAdamW._sumsq_hip):
+                return
+        elif not ((clip and (cls._sumsq is FusedAdamW._sumsq_hip or (not amp and cls._adamw is FusedAdamW._adamw_hip)))
+                  or (amp and cls._adamw_amp is FusedAdamW._adamw_amp_hip)):
             return
         found = []
         for i, tw in enumerate(self.towers):
@@ -389,8 +447,8 @@ class FusedAdamW:
         for what, n, *ptrs in found:
             if n % 4 or any(x % 16 for x in ptrs):
                 raise ValueError(f'FusedAdamW.step: {what} has {n} elements at {ptrs[0]:#x} (gradient at {ptrs[1]:#x}); a step that clips '
-                                 'the gradient norm or is driven by a loss scaler needs every range to be a multiple of 4 elements on a '
-                                 '16-byte boundary.  Only the plain step has an element-wise kernel (dclip_adamw)')
+                                 'the gradient norm, is driven by a loss scaler or keeps an EMA (ema_decay) needs every range to be a multiple '
+                                 'of 4 elements on a 16-byte boundary.  Only the plain step has an element-wise kernel (dclip_adamw)')
 
     @torch.no_grad()
     def step(self, zero_grad=False, overlap=False, join=True):
@@ -411,12 +469,19 @@ class FusedAdamW:
             raise RuntimeError('FusedAdamW.step: a loss scaler (precision: 16) cannot drive the sharded data-parallel exchange: after '
                                'backward_and_sync() p.grad holds zeros, so the scaler\'s overflow check sees nothing.  The modes that work '
                                'under precision: 16 are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
-        self._refuse_scalar_ranges(self.max_grad_norm is not None, amp is not None)
+        if self._ema_in_use:
+            raise RuntimeError('FusedAdamW.step: inside ema_weights() the towers hold the averaged weights; leave the context first')
+        ema_w = self._ema_weight()
+        if ema_w is not None and any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
+            raise RuntimeError('FusedAdamW.step: ema_decay is not kept under the sharded data-parallel exchange: every rank updates and '
+                               'holds the state of 1/W of each gradient bucket only, and an average in shards would have to be gathered '
+                               'to be used.  The modes that keep an EMA are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
+        self._refuse_scalar_ranges(self.max_grad_norm is not None, amp is not None, ema_w is not None)
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
         on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
         main = torch.cuda.current_stream() if on_gpu else None
-        jobs = self._jobs(overlap, main, self.max_grad_norm is not None)
+        jobs = self._jobs(overlap, main, self.max_grad_norm is not None, ema_w is not None)
         record = None
         if self.max_grad_norm is None:
             self.last_grad_norm = coef = None
@@ -426,20 +491,20 @@ class FusedAdamW:
             for job in jobs:                                 # tower by tower
                 if not job[3]:
                     self._await_grads(job, main)
-                joined.append(self._update(job, zero_grad, overlap, main, None, record))
-            extras = self._extra_items()
+                joined.append(self._update(job, zero_grad, overlap, main, None, record, ema_w))
+            extras = self._extra_items(ema_w is not None)
         else:
             jobs.sort(key=lambda j: not j[3])                # (stable) the sharded towers' partial sums lie first
-            extras = self._extra_items()
+            extras = self._extra_items(ema_w is not None)
             if amp is None:
                 self.last_grad_norm, coef = self._clip_coef(jobs, extras, main)
             else:
                 coef = None
                 self.last_grad_norm, record = self._clip_coef(jobs, extras, main, amp)
-            joined = [self._update(job, zero_grad, overlap, main, coef, record) for job in jobs]
+            joined = [self._update(job, zero_grad, overlap, main, coef, record, ema_w) for job in jobs]
         if extras:
             # the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)
-            self._adamw_many(extras, zero_grad, main.cuda_stream if main is not None else None, coef, record)
+            self._adamw_many(extras, zero_grad, main.cuda_stream if main is not None else None, coef, record, ema_w)
         if join:
             for stream in joined:
                 if stream is not None:
@@ -454,8 +519,9 @@ class FusedAdamW:
                                              torch.zeros(p.numel(), dtype=torch.float32, device=p.device))
         return st
 
-    def _extra_items(self):
-        """[(p, g, m, v)] of the extras that have a gradient, the gradients averaged over the ranks"""
+    def _extra_items(self, ema=False):
+        """[(p, g, m, v)] of the extras that have a gradient, the gradients averaged over the ranks; ema: [(p, g, m, v, e)], a new average
+        filled from its parameter here, on the current stream, which the extras' update runs on"""
         if not self.extras:
             return []
         from .parallel import all_reduce_avg
@@ -470,6 +536,12 @@ class FusedAdamW:
                 all_reduce_avg(p.grad)
             m, v = self._extra_moments(p)
             items.append((p.data.view(-1), p.grad.view(-1), m, v))
+            if ema:
+                e = self._ema_of(id(p), p)
+                if id(p) in self._ema_unseeded:
+                    e.copy_(p.data.view(-1))
+                    self._ema_unseeded.discard(id(p))
+                items[-1] += (e,)
         return items
 
     def join(self):
@@ -481,6 +553,111 @@ class FusedAdamW:
         for tw in pending:
             cur.wait_event(tw.opt_done)
             tw.opt_done = None
+
+    # ---- the exponential moving average of the parameters (ema_decay) ----
+    def _ema_weight(self):
+        """None while ema_decay is None, else 1 - ema_decay formed in double and rounded once to f32 (1.f - 0.9999f is 1.66e-4 off)"""
+        if self.ema_decay is None:
+            return None
+        d = float(self.ema_decay)
+        if not 0.0 <= d <= 1.0:                              # (a NaN fails both)
+            raise ValueError(f'FusedAdamW: ema_decay must lie in [0, 1], got {self.ema_decay!r}')
+        return struct.unpack('f', struct.pack('f', 1.0 - d))[0]
+
+    def _has_ema(self):
+        return any(k not in self._ema_unseeded for k in self._ema)
+
+    def _ema_pairs(self):
+        """[(tower or None, [(parameters, average)])]: the optimizer's fixed ranges of every tower that has an average, then the extras"""
+        out = []
+        for tw in self.towers:
+            e = self._ema.get(id(tw))
+            if tw.flat is not None and e is not None and id(tw) not in self._ema_unseeded:
+                out.append((tw, [(tw.flat[a:b], e[a:b]) for a, b in self._ranges(tw)]))
+        extras = [(p.data.view(-1), self._ema[id(p)]) for p in self.extras if id(p) in self._ema and id(p) not in self._ema_unseeded]
+        return out + ([(None, extras)] if extras else [])
+
+    def _ema_exchange(self):
+        """parameters <-> average on the current stream, after every pending update: one launch per tower (per 24 ranges) and one for
+        the extras; every tower touched re-casts its bf16 weight cache at its next forward"""
+        from . import ops
+        self.join()
+        st = torch.cuda.current_stream().cuda_stream if any(a.is_cuda for _, prs in self._ema_pairs() for a, _ in prs) else None
+        for tw, pairs in self._ema_pairs():
+            for i in range(0, len(pairs), ops.ADAMW_MAX_RANGES):
+                self._swap(pairs[i:i + ops.ADAMW_MAX_RANGES], st)
+            if tw is not None:
+                tw.wcache_dirty = True
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights():` the towers (and the extra parameters) hold the averaged weights: evaluate, export, score.  An
+        exchange in place, bit for bit (dclip_swap_multi), of the ranges this optimizer updates — frozen ranges are not touched —, and
+        the same exchange back on exit, after which every parameter is what it was.  Both mark the towers' bf16 weight caches stale.
+        Runs on the current stream; enter and leave on the same one.  Inside, step(), state_dict(), load_state_dict(),
+        ema_state_dict() and a second ema_weights() raise RuntimeError, and so does entering before any step has kept an average."""
+        if self._ema_in_use:
+            raise RuntimeError('FusedAdamW.ema_weights: already inside ema_weights()')
+        if not self._has_ema():
+            raise RuntimeError('FusedAdamW.ema_weights: there is no average yet: no step() has run with ema_decay set, and none was loaded')
+        self._ema_exchange()
+        self._ema_in_use = True
+        try:
+            yield self
+        finally:
+            self._ema_in_use = False
+            self._ema_exchange()
+
+    def _refuse_inside_ema(self, what):
+        if self._ema_in_use:
+            raise RuntimeError(f'FusedAdamW.{what}: inside ema_weights() parameters and average have changed places; leave the context first')
+
+    def _ema_params(self, slots):
+        """{i: the average of slot i, shaped like its parameter} for the slots that have one"""
+        out = {}
+        for i, (tw, off, n, shape) in enumerate(slots):
+            e = self._ema.get(id(tw))
+            if e is not None and id(tw) not in self._ema_unseeded:
+                out[i] = (e if off is None else e[off:off + n]).view(shape).clone()
+        return out
+
+    def ema_state_dict(self, params=None):
+        """{i: averaged parameter i} over _slots(params), the order of state_dict()'s 'state': what to export as the averaged student.
+        A slot without an average of its own (an extra parameter that never had a gradient) carries its parameter."""
+        self._refuse_inside_ema('ema_state_dict')
+        if not self._has_ema():
+            raise RuntimeError('FusedAdamW.ema_state_dict: there is no average yet: no step() has run with ema_decay set, and none was loaded')
+        self.join()
+        slots = self._slots(params)
+        out = self._ema_params(slots)
+        for i, (tw, off, n, shape) in enumerate(slots):
+            if i not in out:
+                out[i] = (tw.data if off is None else tw.flat[off:off + n]).view(shape).clone()
+        return dict(sorted(out.items()))
+
+    def _load_ema(self, ema, slots):
+        """restore the average from state_dict()'s 'ema' entry; none saved: forget the one held, the next step starts from the parameters"""
+        self._ema.clear()
+        self._ema_unseeded.clear()
+        if ema is None:
+            return
+        if ema.get('decay') is not None:
+            self.ema_decay = ema['decay']
+        for i, (tw, off, n, shape) in enumerate(slots):
+            t = ema['params'].get(i, ema['params'].get(str(i)))
+            if t is None:
+                continue
+            if tuple(t.shape) != shape:
+                raise ValueError(f'FusedAdamW.load_state_dict: parameter {i} has shape {shape}, its saved average {tuple(t.shape)}')
+            if off is None:
+                self._ema[id(tw)] = t.detach().to(device=tw.device, dtype=torch.float32, copy=True).reshape(-1)
+                continue
+            if self._sharded(tw):
+                raise RuntimeError('FusedAdamW.load_state_dict: the checkpoint carries an EMA, which the sharded data-parallel exchange '
+                                   'does not keep (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off do)')
+            if id(tw) not in self._ema:
+                self._ema[id(tw)] = tw.flat.detach().clone()     # (frozen ranges and slots without a saved average: the parameters)
+            self._ema[id(tw)][off:off + n].copy_(t.reshape(-1))
 
     def _full_moments(self, tw):
         """(m, v) in the flat layout of the tower; collective in a sharded data-parallel run (all-gather of the ranks' shards)"""
@@ -542,7 +719,11 @@ class FusedAdamW:
         dual_distill_model.py:195: filter(requires_grad, self.parameters())); default = canonical tower order.
 
         COLLECTIVE in a sharded data-parallel run: every rank holds 1/W of m / v, so every rank must call this (the moments are
-        all-gathered per bucket); checkpoint.save_checkpoint does that and lets rank 0 alone write the file."""
+        all-gathered per bucket); checkpoint.save_checkpoint does that and lets rank 0 alone write the file.
+
+        Once a step has kept an EMA (ema_decay) there is a third top-level key: 'ema': {'decay': ema_decay, 'params': {i: the average of
+        parameter i, shaped like it}}, i as in 'state'.  torch.optim.AdamW.load_state_dict ignores it; load_state_dict() here restores it."""
+        self._refuse_inside_ema('state_dict')
         self.join()
         slots = self._slots(params)
         state = {}
@@ -562,10 +743,16 @@ class FusedAdamW:
         group = {'lr': self.lr, 'initial_lr': self.base_lr, 'betas': tuple(self.betas), 'eps': self.eps,
                  'weight_decay': self.weight_decay, 'amsgrad': False, 'maximize': False, 'foreach': None,
                  'capturable': False, 'differentiable': False, 'fused': None, 'params': list(range(len(slots)))}
-        return {'state': state, 'param_groups': [group]}
+        sd = {'state': state, 'param_groups': [group]}
+        if self._has_ema():
+            sd['ema'] = {'decay': self.ema_decay, 'params': self._ema_params(slots)}
+        return sd
 
     @torch.no_grad()
     def load_state_dict(self, sd, params=None):
+        """Restores moments, step count, hyper-parameters and, if the dict carries one, the EMA.  A dict without 'ema' drops an average
+        this optimizer holds: with ema_decay set, the next step() starts a new one from the parameters as they are then."""
+        self._refuse_inside_ema('load_state_dict')
         slots = self._slots(params)
         group = sd['param_groups'][0]
         if len(group['params']) != len(slots):
@@ -604,6 +791,7 @@ class FusedAdamW:
         self.step_count = steps.pop() if steps else 0
         if self._skipped is not None:
             self._skipped.zero_()
+        self._load_ema(sd.get('ema'), slots)
 
 
 class EpochCosineSchedule:

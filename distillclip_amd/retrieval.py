@@ -21,7 +21,8 @@ from .metrics import RECALL_K_LIST, MAX_CUTOFFS, caption_offsets, retrieval_reca
 class RetrievalEvaluator:
     """image_encoder / text_encoder: two towers of this package (students or CLIP towers) whose out_dim agree.  k_list: at most 8
     cut-offs.  max_batch: the most rows one tower run takes; larger inputs go through in chunks.  The towers' parameters, requires_grad
-    and train / eval flags are left alone."""
+    and train / eval flags are left alone.  The towers run on the weights
+    they hold at the call: `with opt.ema_weights():` (FusedAdamW) around the calls scores the averaged student instead of the last iterate."""
 
     def __init__(self, image_encoder, text_encoder, k_list=RECALL_K_LIST, max_batch=512):
         if int(max_batch) < 1:

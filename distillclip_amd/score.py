@@ -32,7 +32,8 @@ def _counts(ref_counts, B, R):
 
 class LCLIPScore(nn.Module):
     """image_encoder / text_encoder: two towers of this package (students or CLIP towers) whose out_dim agree.  w: the paper's rescaling
-    of CLIP-S.  max_batch: the most rows one tower run takes; larger inputs go through in chunks."""
+    of CLIP-S.  max_batch: the most rows one tower run takes; larger inputs go through in chunks.  The towers run on the weights
+    they hold at the call: `with opt.ema_weights():` (FusedAdamW) around the calls scores the averaged student instead of the last iterate."""
 
     def __init__(self, image_encoder, text_encoder, w=2.5, max_batch=512):
         super().__init__()

@@ -31,7 +31,8 @@ def _prompt_offsets(counts, n_classes, n_rows):
 class ZeroShotClassifier:
     """image_encoder / text_encoder: two towers of this package (students or CLIP towers) whose out_dim agree.  k_list: the cut-offs
     of compute(), each in [1, 64].  max_batch: the most rows one tower run takes; larger inputs go through in chunks.  The towers'
-    parameters, requires_grad and train / eval flags are left alone."""
+    parameters, requires_grad and train / eval flags are left alone.  The towers run on the weights
+    they hold at the call: `with opt.ema_weights():` (FusedAdamW) around the calls scores the averaged student instead of the last iterate."""
 
     def __init__(self, image_encoder, text_encoder, k_list=(1, 5), max_batch=512):
         if int(max_batch) < 1:

@@ -328,6 +328,31 @@ int dclip_amp_prepare(const float* found_inf, const float* grad_scale, const flo
                       float max_norm, float beta1, float beta2, int64_t step, int64_t* skipped, float* record, void* stream);
 int dclip_adamw_multi_amp(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
                           float beta1, float beta2, float eps, float weight_decay, int zero_grad, const float* record, void* stream);
+/*
+ * The same step keeping an exponential moving average of the parameters: one more f32 range e[k] per range, in the same launch.
+ *   adamw_multi_ema : gscale == NULL and record == NULL: dclip_adamw_multi ; gscale alone: dclip_adamw_multi_scaled ; record alone:
+ *                     dclip_adamw_multi_amp (`step` is then not read: the record carries the bias corrections) ; both: refused.
+ *                     p, g, m, v come out bit for bit as from that entry.  Per element, with p' the parameter this launch writes
+ *                     and w = ema_weight:
+ *                         d = p' - e (rounded to f32) ;  e <- d == 0 ? e : fmaf(w, d, e)
+ *                     two roundings, the difference and the fused multiply-add: |e' - (e + w (p' - e))| <= u (|w (p' - e)| + |e'|)
+ *                     to first order, u = 2^-24.  p' == e gives e back bit for bit (the sign of a zero included), so a parameter
+ *                     that has stopped moving does not drift.  ema_weight == 0 runs the step alone: e is neither read nor
+ *                     written.  A skipped step (record[DCLIP_AMP_SKIP] set) reads and writes no e, like p, m, v.
+ *                     ema_weight: 1 - decay, in [0, 1].  Form it in double and round once, (float)(1.0 - decay): in f32,
+ *                     1.f - 0.9999f is 1.66e-4 off relatively.
+ *                     e[k]: 16-byte aligned, n[k] elements, disjoint from everything else.  Refused on the host, before any
+ *                     launch: whatever dclip_adamw_multi refuses, a NULL or misaligned e[k], ema_weight outside [0, 1] or NaN,
+ *                     gscale together with record, a misaligned record.
+ *   swap_multi      : a[k][0 .. n[k]) <-> b[k][0 .. n[k]) for `count` <= DCLIP_ADAMW_MAX_RANGES pairs in ONE launch (HOST arrays; the
+ *                     alignment rules of dclip_adamw_multi), moved as 128-bit integers: every bit pattern survives (NaN payloads,
+ *                     -0).  a[k] == b[k] is allowed and leaves the range as it is; two sides that overlap otherwise are refused.
+ *                     Ranges of different k must not overlap (not checked).
+ */
+int dclip_adamw_multi_ema(float* const* p, float* const* g, float* const* m, float* const* v, float* const* e, const int64_t* n, int32_t count,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, float ema_weight,
+                          const float* gscale, const float* record, void* stream);
+int dclip_swap_multi(float* const* a, float* const* b, const int64_t* n, int32_t count, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused distillation loss, forward + backward.
