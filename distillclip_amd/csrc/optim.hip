@@ -237,6 +237,84 @@ __global__ __launch_bounds__(256) void adamw4_multi_kernel(std::conditional_t<EM
     }
 }
 
+// Table-driven form (include/dclip.h: dclip_adamw_table): the ranges are records in DEVICE memory, each with its own learning-rate scale
+// and weight decay, all inside one flat layout that p, g, m, v (and e) share, so one launch takes any number of them: parameter groups
+// cut a student tower into several dozen ranges (weights and biases alternate), three launches and more through the 24-range entries.
+// The grid is 1-D over a tile list in which every range starts a new tile, as in sumsq_multi_kernel: one workgroup per tile of
+// TABLE_TRIPS trips of 256 float4.  Record k holds the first tile of its range, record `count` the number of tiles; a workgroup finds its
+// range by bisection over them (uniform: scalar loads, about log2(count) of them, before the first vector load).  Inside the tile the
+// loop is adamw4_multi_kernel's with a stride of one trip: the float4 loads of the next trip are issued before the stores of the current
+// one, zero_grad and a skipped step are handled the same way, the arithmetic is adamw_elem / ema_elem on lr_k = lr * lr_scale_k (one
+// f32 product) and wd_k.  No atomics, every element is touched by exactly one lane: the same call gives the same bits.
+constexpr int TABLE_TRIPS = DCLIP_ADAMW_TABLE_TILE / 1024;
+constexpr int TABLE_TILE4 = 256 * TABLE_TRIPS;          // float4 per tile
+static_assert(sizeof(dclip_adamw_range) == 32 && DCLIP_ADAMW_TABLE_TILE % 1024 == 0, "the table's record is 32 bytes, a tile whole trips");
+template <int MODE, bool EMA>
+__global__ __launch_bounds__(256) void adamw4_table_kernel(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m, float4* __restrict__ v,
+                                                           float4* __restrict__ e, const dclip_adamw_range* __restrict__ tab, int count, float lr, float b1,
+                                                           float b2, float eps, float bc1, float bc2_sqrt, int zero_grad, float w,
+                                                           const float* __restrict__ gscale) {
+    constexpr bool SCALED = MODE != ADAMW_PLAIN;
+    const int64_t t = blockIdx.x;
+    if (t >= tab[count].tile0) return;                   // (a grid wider than the table's tile list: nothing to do, nothing read past it)
+    int lo = 0, hi = count;                              // tab[lo].tile0 <= t < tab[hi].tile0 (uniform)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tab[mid].tile0 <= t) lo = mid; else hi = mid;
+    }
+    const int64_t first = (t - tab[lo].tile0) * TABLE_TILE4;             // float4 of the range before this tile
+    const int64_t left = tab[lo].length / 4 - first;
+    const int64_t n4 = left < TABLE_TILE4 ? left : TABLE_TILE4;
+    const int64_t at = tab[lo].begin / 4 + first;
+    lr = __fmul_rn(lr, tab[lo].lr_scale);                // (one rounding, never contracted into what follows)
+    const float wd = tab[lo].weight_decay;
+    p += at; g += at; m += at; v += at;
+    if constexpr (EMA) e += at;
+    int64_t i = threadIdx.x;
+    if (i >= n4) return;
+    float gs = MODE == ADAMW_SCALED ? *gscale : 1.f;
+    if constexpr (MODE == ADAMW_AMP) {
+        const float4 c = *(const float4*)gscale;
+        if (c.y != 0.f) {
+            if (zero_grad)
+                for (; i < n4; i += 256) g[i] = float4{0.f, 0.f, 0.f, 0.f};
+            return;
+        }
+        gs = c.x; bc1 = c.z; bc2_sqrt = c.w;
+    }
+    float4 pi = p[i], gi = g[i], mi = m[i], vi = v[i];
+    float4 ei = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) ei = e[i];
+    for (;;) {
+        const int64_t nx = i + 256;
+        const bool more = nx < n4;
+        float4 pn = pi, gn = gi, mn = mi, vn = vi, en = ei;
+        if (more) {
+            pn = p[nx]; gn = g[nx]; mn = m[nx]; vn = v[nx];
+            if constexpr (EMA) en = e[nx];
+        }
+        if (SCALED) { gi.x *= gs; gi.y *= gs; gi.z *= gs; gi.w *= gs; }
+        adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        if constexpr (EMA) { ema_elem(ei.x, pi.x, w); ema_elem(ei.y, pi.y, w); ema_elem(ei.z, pi.z, w); ema_elem(ei.w, pi.w, w); }
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if constexpr (EMA) e[i] = ei;
+        if (zero_grad) g[i] = float4{0.f, 0.f, 0.f, 0.f};
+        if (!more) break;
+        i = nx; pi = pn; gi = gn; mi = mn; vi = vn; ei = en;
+    }
+}
+
+template <bool EMA>
+void adamw_table_launch(int mode, unsigned tiles, hipStream_t stream, float* p, float* g, float* m, float* v, float* e, const void* table, int count, float lr,
+                        float b1, float b2, float eps, float bc1, float bc2, int zero_grad, float w, const float* dev) {
+    auto kernel = mode == ADAMW_PLAIN ? adamw4_table_kernel<ADAMW_PLAIN, EMA> : mode == ADAMW_SCALED ? adamw4_table_kernel<ADAMW_SCALED, EMA> : adamw4_table_kernel<ADAMW_AMP, EMA>;
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), 0, stream, (float4*)p, (float4*)g, (float4*)m, (float4*)v, (float4*)e, (const dclip_adamw_range*)table, count,
+                       lr, b1, b2, eps, bc1, bc2, zero_grad, w, dev);
+}
+
 // Pairs of ranges exchanged word for word (include/dclip.h: dclip_swap_multi).  128-bit integer loads and stores and nothing between
 // them: no value is ever interpreted as a float.  The grid and the order of loads and stores are those of adamw4_multi_kernel.
 struct SwapRanges { uint4* a[DCLIP_ADAMW_MAX_RANGES]; uint4* b[DCLIP_ADAMW_MAX_RANGES]; int64_t n4[DCLIP_ADAMW_MAX_RANGES]; };
@@ -380,6 +458,61 @@ extern "C" int dclip_adamw_multi_ema(float* const* p, float* const* g, float* co
         adamw_ema_launch<false>(mode, grid, (hipStream_t)stream, (const AdamwRanges&)r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad, dev);
     else
         adamw_ema_launch<true>(mode, grid, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad, dev);
+    return dclip_check_launch(what);
+}
+
+extern "C" size_t dclip_adamw_table_bytes(int32_t count) { return count < 1 ? 0 : ((size_t)count + 1) * sizeof(dclip_adamw_range); }
+
+extern "C" int dclip_adamw_table_fill(const int64_t* begin, const int64_t* length, const float* lr_scale, const float* weight_decay, int32_t count,
+                                      int64_t total, void* image, size_t image_bytes, int64_t* tiles) {
+    const char* what = "dclip_adamw_table_fill";
+    DCLIP_REQUIRE(begin && length && lr_scale && weight_decay && image && tiles && count >= 1 && total >= 4, "%s: bad argument (count >= 1 ranges, total >= 4)", what);
+    DCLIP_REQUIRE(((uintptr_t)image & 7) == 0 && image_bytes >= dclip_adamw_table_bytes(count),
+                  "%s: the image needs %zu bytes on an 8-byte boundary (dclip_adamw_table_bytes)", what, dclip_adamw_table_bytes(count));
+    int64_t end = 0, tile0 = 0;                              // everything is checked before the first record is written
+    for (int k = 0; k < count; ++k) {
+        DCLIP_REQUIRE(begin[k] >= 0 && begin[k] % 4 == 0 && length[k] > 0 && length[k] % 4 == 0,
+                      "%s: range %d must be non-empty, begin and length multiples of 4 elements (begin %lld, length %lld)", what, k, (long long)begin[k], (long long)length[k]);
+        DCLIP_REQUIRE(begin[k] >= end, "%s: range %d begins at %lld, inside or before range %d, which ends at %lld: ranges ascend and do not overlap", what, k,
+                      (long long)begin[k], k - 1, (long long)end);
+        DCLIP_REQUIRE(length[k] <= total - begin[k], "%s: range %d ends past the stated total of %lld elements", what, k, (long long)total);
+        DCLIP_REQUIRE(isfinite(lr_scale[k]) && lr_scale[k] >= 0.f && isfinite(weight_decay[k]),
+                      "%s: range %d needs a finite lr_scale >= 0 and a finite weight_decay (got %g, %g)", what, k, (double)lr_scale[k], (double)weight_decay[k]);
+        end = begin[k] + length[k];
+        tile0 += (length[k] + DCLIP_ADAMW_TABLE_TILE - 1) / DCLIP_ADAMW_TABLE_TILE;
+    }
+    DCLIP_REQUIRE(tile0 <= INT32_MAX, "%s: %lld tiles, more than one launch's grid", what, (long long)tile0);
+    dclip_adamw_range* rec = (dclip_adamw_range*)image;
+    tile0 = 0;
+    for (int k = 0; k < count; ++k) {
+        rec[k] = dclip_adamw_range{tile0, begin[k], length[k], lr_scale[k], weight_decay[k]};
+        tile0 += (length[k] + DCLIP_ADAMW_TABLE_TILE - 1) / DCLIP_ADAMW_TABLE_TILE;
+    }
+    rec[count] = dclip_adamw_range{tile0, end, 0, 0.f, 0.f};
+    *tiles = tile0;
+    return DCLIP_OK;
+}
+
+extern "C" int dclip_adamw_table(float* p, float* g, float* m, float* v, float* e, const void* table, int32_t count, int64_t tiles, float lr, float beta1,
+                                 float beta2, float eps, int64_t step, int zero_grad, float ema_weight, const float* gscale, const float* record,
+                                 void* stream) {
+    const char* what = "dclip_adamw_table";
+    DCLIP_REQUIRE(p && g && m && v && ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0),
+                  "%s: bad argument (p, g, m, v non-NULL, all bases 16-byte aligned)", what);
+    DCLIP_REQUIRE(table && ((uintptr_t)table & 7) == 0 && count >= 1, "%s: bad argument (a device table on an 8-byte boundary, count >= 1)", what);
+    DCLIP_REQUIRE(tiles >= count && tiles <= INT32_MAX, "%s: %lld tiles for %d ranges: every range has at least one, a launch at most 2^31 - 1", what,
+                  (long long)tiles, (int)count);
+    DCLIP_REQUIRE(!(gscale && record), "%s: gscale (a clipped step) and record (a scaler-driven step) exclude each other", what);
+    DCLIP_REQUIRE(!e || (ema_weight >= 0.f && ema_weight <= 1.f), "%s: ema_weight = 1 - decay must lie in [0, 1] (got %g)", what, (double)ema_weight);
+    DCLIP_REQUIRE(record ? ((uintptr_t)record & 15) == 0 : step >= 1, "%s: bad argument (a 16-byte aligned record of dclip_amp_prepare, or step >= 1)", what);
+    const int mode = record ? ADAMW_AMP : gscale ? ADAMW_SCALED : ADAMW_PLAIN;
+    const float bc1 = record ? 0.f : 1.f - powf(beta1, (float)step);
+    const float bc2 = record ? 0.f : sqrtf(1.f - powf(beta2, (float)step));
+    const float* dev = record ? record : gscale;
+    if (!e || ema_weight == 0.f)                             // no average, or one that stands still: e neither read nor written
+        adamw_table_launch<false>(mode, (unsigned)tiles, (hipStream_t)stream, p, g, m, v, nullptr, table, count, lr, beta1, beta2, eps, bc1, bc2, zero_grad, 0.f, dev);
+    else
+        adamw_table_launch<true>(mode, (unsigned)tiles, (hipStream_t)stream, p, g, m, v, e, table, count, lr, beta1, beta2, eps, bc1, bc2, zero_grad, ema_weight, dev);
     return dclip_check_launch(what);
 }
 

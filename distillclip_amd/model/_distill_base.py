@@ -59,8 +59,11 @@ class DistillBase(nn.Module):
     # Plain attributes, set on the module before configure_optimizers() / validation (the reference has neither: the defaults are its
     # behaviour).  ema_decay: handed to FusedAdamW, which then keeps an exponential moving average of the student weights inside its
     # step.  validate_with_ema: the validation loop runs on that average (on_validation_start / on_validation_end).
+    # optimizer_groups: FusedAdamW's `groups`, a list of {'params', 'weight_decay', 'lr_scale'} dicts or a callable model -> such a list
+    # (e.g. distillclip_amd.optim.no_decay_groups); None: one weight decay and one learning rate for every trainable element.
     ema_decay = None
     validate_with_ema = False
+    optimizer_groups = None
     _optimizer = None              # the optimizer configure_optimizers() built
     _ema_context = None            # the entered FusedAdamW.ema_weights() of a validation loop
 
@@ -107,7 +110,9 @@ class DistillBase(nn.Module):
             tw.materialize(dev)
         extras = [p for tw in towers                             # a plain CLIP student's projection linears (tw.module: its encoder)
                   for p in getattr(tw.module, 'extra_parameters', lambda: [])()]
-        opt = FusedAdamW(towers, lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras, ema_decay=self.ema_decay)
+        groups = self.optimizer_groups(self) if callable(self.optimizer_groups) else self.optimizer_groups
+        opt = FusedAdamW(towers, lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras, ema_decay=self.ema_decay,
+                         groups=groups)
         self._optimizer = opt
         sched = EpochCosineSchedule(opt, self.hparams.warm_steps, self.hparams.total_steps)
         self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with

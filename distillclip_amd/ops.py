@@ -412,6 +412,40 @@ def adamw_multi_ema(items, lr, betas, eps, weight_decay, step, zero_grad, ema_we
                                 1 if zero_grad else 0, ema_weight, _p(gscale), _p(record), _stream() if stream is None else stream)
 
 
+ADAMW_TABLE_TILE = 8192    # DCLIP_ADAMW_TABLE_TILE: every range of a table starts a new tile of this many elements
+
+
+def adamw_table_image(ranges, total, out=None):
+    """The HOST image of the device table of adamw_table (include/dclip.h: dclip_adamw_table_fill), validated there.
+    ranges: [(begin, length, lr_scale, weight_decay)] in elements, ascending.  total: the element count of the buffers the ranges lie in.
+    out: a CPU uint8 tensor to fill (e.g. pinned), at least adamw_table_bytes long; default a new one.  -> (image, tiles)"""
+    import ctypes
+    n = len(ranges)
+    need = lib().dclip_adamw_table_bytes(n)
+    if out is None:
+        out = torch.zeros(max(need, 8), dtype=torch.uint8)
+    if out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('adamw_table_image: out is a contiguous CPU uint8 tensor')
+    col = lambda k, ct: (ct * max(n, 1))(*[r[k] for r in ranges])
+    tiles = ctypes.c_int64(0)
+    lib().dclip_adamw_table_fill(col(0, ctypes.c_int64), col(1, ctypes.c_int64), col(2, ctypes.c_float), col(3, ctypes.c_float), n, total,
+                                 out.data_ptr(), out.numel(), ctypes.byref(tiles))
+    return out, tiles.value
+
+
+def adamw_table(p, g, m, v, e, table, count, tiles, lr, betas, eps, step, zero_grad=False, ema_weight=0.0, gscale=None, record=None, stream=None):
+    """AdamW on `count` ranges of the flat f32 buffers p, g, m, v (and e, or None) in ONE launch, each range with its own lr_scale and
+    weight_decay from the device `table` (the uploaded image of adamw_table_image, with its `tiles`); gscale / record as in
+    adamw_multi_ema (include/dclip.h: dclip_adamw_table)"""
+    _chk(p, g, m, v, e, table, gscale, record)
+    if table.dtype != torch.uint8 or table.numel() < lib().dclip_adamw_table_bytes(count):
+        raise ValueError('adamw_table: table is the uint8 device copy of an image of %d ranges' % count)
+    if any(t.numel() != p.numel() or t.dtype != torch.float32 for t in (p, g, m, v) + (() if e is None else (e,))):
+        raise ValueError('adamw_table: p, g, m, v (and e) are f32 buffers of one length, the `total` the table was filled for')
+    lib().dclip_adamw_table(_p(p), _p(g), _p(m), _p(v), _p(e), _p(table), count, tiles, lr, betas[0], betas[1], eps, step, 1 if zero_grad else 0,
+                            ema_weight, _p(gscale), _p(record), _stream() if stream is None else stream)
+
+
 def swap_multi(pairs, stream=None):
     """a <-> b, bit for bit, for at most 24 pairs [(a, b)] of equally long 1-D f32 tensors in ONE launch (include/dclip.h: dclip_swap_multi)"""
     import ctypes

@@ -60,11 +60,29 @@ class FusedAdamW:
     step() refuses it under the sharded data-parallel exchange, where every rank holds 1/W of the optimizer state
     (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off work).  `with opt.ema_weights():` runs the towers on the average;
     ema_state_dict() exports it; state_dict() carries it under 'ema', next to 'state' and 'param_groups', which stay what
-    torch.optim.AdamW loads."""
+    torch.optim.AdamW loads.
+
+    groups (None = one weight_decay and one lr for every element, the reference's behaviour and exactly today's launches): a list of
+    torch-style dicts {'params': [...], 'weight_decay': x, 'lr_scale': s}, either key optional.  A group's elements are decayed by its
+    weight_decay and stepped with lr * lr_scale, the product rounded once to f32; a parameter in no group keeps the optimizer's
+    weight_decay and scale 1 (the default group).  Parameters are matched by identity against the trainable set; the constructor
+    raises ValueError for a parameter in two groups, one that is frozen or in none of the towers / extra_params, a negative or
+    non-finite value, an unknown key (betas and eps are not per group).  Every tower is then stepped by ONE table-driven launch
+    (dclip_adamw_table), plain, clipped or scaler-driven, with or without the EMA: its ranges are cut where neighbouring parameters
+    differ in (lr_scale, weight_decay), the table lies in device memory, is built at the tower's first step and uploaded again (pinned
+    memory, asynchronously on the update's stream) only after `opt.groups[i]['weight_decay']` / `['lr_scale']` or opt.weight_decay
+    changed, which takes effect at the next step; no copy and no host synchronisation in any other step.  The clipping norm stays
+    global over all groups.  Extra parameters are stepped per distinct (lr_scale, weight_decay) through the 24-range entries.  The
+    table kernel is float4 only and has no sharded form: an odd or misaligned range raises ValueError, the sharded data-parallel
+    exchange RuntimeError, both before the step counter moves (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off work).  param_groups lists
+    the declared groups and then the default group, each with lr = opt.lr * lr_scale; state_dict() writes torch's multi-group layout
+    with lr_scale as an extra key per group, which torch.optim.AdamW([*groups, {'params': rest}]) loads and whose own dict loads back;
+    a dict with another number of groups is a ValueError."""
 
     _step_supports_amp_scaling = True
 
-    def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None, ema_decay=None):
+    def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None, ema_decay=None,
+                 groups=None):
         """extra_params: trainable parameters that live outside the towers' flat buffers — the embedding_projection / hidden_projection
         linears of a plain CLIP encoder in the student role (reference image_encoder.py:23-25, text_encoder.py:45-47): four small tensors
         whose gradients autograd produces; they are updated together, like one more tower's ranges (after an all-reduce of each gradient
@@ -91,6 +109,8 @@ class FusedAdamW:
         self._ema = {}                                     # id(tower) -> the average, in the tower's flat layout ; id(extra parameter) -> 1-D
         self._ema_unseeded = set()                         # keys of _ema allocated by the step in flight, not yet filled from the parameters
         self._ema_in_use = False                           # inside ema_weights(): parameters and average have changed places
+        self.groups = None if groups is None else self._declare_groups(groups)
+        self._tables = {}                                  # id(tower) -> the device table of its ranges and what it was filled from
 
     def _ranges(self, tw):
         """contiguous [begin, end) element ranges of the parameters this optimizer was built over"""
@@ -98,6 +118,111 @@ class FusedAdamW:
         if r is None:                                  # tower materialised after construction: captured at first use
             r = self._fixed_ranges[id(tw)] = [list(x) for x in tw.trainable_ranges()]
         return r
+
+    # ---- parameter groups ----
+    _GROUP_KEYS = ('params', 'weight_decay', 'lr_scale')
+
+    def _candidates(self):
+        """the parameters a group may name: the trainable set this optimizer is built over (a tower that is not materialised yet:
+        its requires_grad parameters, which are what _ranges() will capture), tower by tower, extras last"""
+        out = []
+        for tw in self.towers:
+            live = [p for p in tw._params() if p is not None]
+            if tw.flat is None:
+                out += [p for p in live if p.requires_grad]
+            else:
+                rng = self._ranges(tw)
+                out += [p for p, off in zip(live, tw._offsets) if any(a <= off < b for a, b in rng)]
+        return out + list(self.extras)
+
+    @staticmethod
+    def _group_value(g, i, key, default):
+        x = g.get(key, default)
+        if x is None and default is None:                    # (weight_decay: the optimizer's own, whatever it is at the step)
+            return None
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0:
+            raise ValueError(f'FusedAdamW: groups[{i}][{key!r}] must be a finite number >= 0, got {x!r}')
+        return float(x)
+
+    def _declare_groups(self, groups):
+        """-> [{'params': [...], 'weight_decay': x or None (the optimizer's), 'lr_scale': s}], checked (class docstring)"""
+        known = {id(p) for p in self._candidates()}
+        seen, out = {}, []
+        for i, g in enumerate(groups):
+            if not isinstance(g, dict) or 'params' not in g:
+                raise ValueError(f'FusedAdamW: groups[{i}] must be a dict with a \'params\' list')
+            unknown = sorted(set(g) - set(self._GROUP_KEYS))
+            if unknown:
+                raise ValueError(f'FusedAdamW: groups[{i}] has unknown key(s) {unknown}; a group takes {list(self._GROUP_KEYS)} '
+                                 '(betas and eps are the optimizer\'s, one lr schedule drives every group through lr_scale)')
+            params = [g['params']] if isinstance(g['params'], torch.Tensor) else list(g['params'])
+            for p in params:
+                if id(p) in seen:
+                    raise ValueError(f'FusedAdamW: a parameter of shape {tuple(p.shape)} is in groups[{seen[id(p)]}] and in groups[{i}]')
+                if id(p) not in known:
+                    raise ValueError(f'FusedAdamW: groups[{i}] names a parameter of shape {tuple(p.shape)} that this optimizer does not update: '
+                                     'it is frozen (requires_grad False), or belongs to none of the towers and extra_params')
+                seen[id(p)] = i
+            out.append({'params': params, 'weight_decay': self._group_value(g, i, 'weight_decay', None), 'lr_scale': self._group_value(g, i, 'lr_scale', 1.0)})
+        return out
+
+    def _hyper_of(self):
+        """{id(parameter): (lr_scale, weight_decay)} of the declared groups as they stand now (their values may change between steps)"""
+        out = {}
+        for i, g in enumerate(self.groups):
+            key = (self._group_value(g, i, 'lr_scale', 1.0), self._group_value(g, i, 'weight_decay', None))
+            out.update((id(p), (key[0], self.weight_decay if key[1] is None else key[1])) for p in g['params'])
+        return out
+
+    def _group_ranges(self, tw, hyper=None):
+        """[(begin, end, lr_scale, weight_decay)] of a tower: its fixed ranges cut where neighbouring parameters differ in (lr_scale,
+        weight_decay).  A parameter's segment runs to the next parameter's offset (the layout's padding goes with the parameter before it)."""
+        hyper = self._hyper_of() if hyper is None else hyper
+        default = (1.0, self.weight_decay)
+        segs = sorted((off, hyper.get(id(p), default)) for p, off in zip([p for p in tw._params() if p is not None], tw._offsets))
+        out = []
+        for a, b in self._ranges(tw):
+            inside = [(off, key) for off, key in segs if a <= off < b]
+            if not inside or inside[0][0] != a:
+                inside.insert(0, (a, default))
+            for (off, key), nxt in zip(inside, [o for o, _ in inside[1:]] + [b]):
+                if out and out[-1][1] == off and out[-1][2:] == key and off != a:
+                    out[-1] = (out[-1][0], nxt) + key
+                else:
+                    out.append((off, nxt) + key)
+        return out
+
+    def _adamw_table_hip(self, tw, bufs, ranges, zero_grad, st, ema_weight, gscale, record):
+        """bufs: the tower's whole flat (p, g, m, v, e or None); ranges: _group_ranges(tw).  ONE launch of dclip_adamw_table.  The device
+        table is built on first use and uploaded again only when `ranges` differ from what it holds: from a fresh pinned image, with an
+        asynchronous copy on the stream the update runs on (the current one), so the launches of that stream see it in order and no
+        host waits.  (`_adamw_table` can be substituted by a torch version like `_adamw`.)"""
+        from . import ops
+        tab = self._tables.get(id(tw))
+        if tab is None or tab['ranges'] != ranges:
+            rows = [(b, e - b, s, wd) for b, e, s, wd in ranges]
+            image, tiles = ops.adamw_table_image(rows, bufs[0].numel(), torch.zeros(lib().dclip_adamw_table_bytes(len(rows)), dtype=torch.uint8).pin_memory())
+            if tab is None or tab['dev'].numel() != image.numel():
+                tab = self._tables[id(tw)] = {'dev': torch.empty(image.numel(), dtype=torch.uint8, device=bufs[0].device), 'uploads': 0}
+            tab['dev'].copy_(image, non_blocking=True)
+            tab.update(ranges=list(ranges), tiles=tiles, uploads=tab['uploads'] + 1)
+        p, g, m, v, e = bufs
+        ops.adamw_table(p, g, m, v, e, tab['dev'], len(ranges), tab['tiles'], self.lr, self.betas, self.eps, self.step_count, zero_grad,
+                        0.0 if ema_weight is None else ema_weight, gscale, record, st)
+
+    _adamw_table = _adamw_table_hip
+
+    @contextlib.contextmanager
+    def _with_hyper(self, lr_scale, weight_decay):
+        """inside: self.lr is lr_k = f32(lr) * f32(lr_scale) rounded once to f32, as the table kernel forms it, and self.weight_decay
+        the group's: what the existing entries read when the extras of one group are stepped through them"""
+        f32 = lambda x: struct.unpack('f', struct.pack('f', x))[0]
+        keep = self.lr, self.weight_decay
+        self.lr, self.weight_decay = f32(f32(self.lr) * f32(lr_scale)), weight_decay   # (the product of two f32 is exact in double)
+        try:
+            yield
+        finally:
+            self.lr, self.weight_decay = keep
 
     def _adamw_hip(self, p, g, m, v, zero_grad, st, gscale=None):
         """p, g, m, v: equally long 1-D f32 views.  (tests/test_parallel_cpu.py substitutes a torch version as `_adamw` to rehearse the
@@ -348,7 +473,13 @@ class FusedAdamW:
             if id(tw) in self._ema_unseeded:
                 self._ema[id(tw)].copy_(tw.flat)
                 self._ema_unseeded.discard(id(tw))
-            self._adamw_many(items, zero_grad, stream.cuda_stream if stream is not None else None, coef, record, ema_weight)
+            st = stream.cuda_stream if stream is not None else None
+            if self.groups is None:
+                self._adamw_many(items, zero_grad, st, coef, record, ema_weight)
+            else:                                            # one table-driven launch for the tower, whichever of the three steps it is
+                m, v = self._moments(tw)
+                self._adamw_table(tw, (tw.flat, tw.flat_grad, m, v, self._ema[id(tw)] if ema_weight is not None else None),
+                                  self._group_ranges(tw), zero_grad, st, ema_weight, coef, record)
             tw.wcache_dirty = True
             tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
             if overlap and self.refresh_cache_in_step:
@@ -450,6 +581,25 @@ class FusedAdamW:
                                  'the gradient norm, is driven by a loss scaler or keeps an EMA (ema_decay) needs every range to be a multiple '
                                  'of 4 elements on a 16-byte boundary.  Only the plain step has an element-wise kernel (dclip_adamw)')
 
+    def _refuse_grouped_step(self):
+        """parameter groups: the table kernel is float4 only and has no sharded form.  Refused here, before the step counter moves: a
+        group value that has become negative or non-finite, the sharded exchange, a cut range that is odd or off a 16-byte boundary"""
+        hyper = self._hyper_of()                             # (raises ValueError on a bad value)
+        if any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
+            raise RuntimeError('FusedAdamW.step: parameter groups are not stepped under the sharded data-parallel exchange: every rank updates '
+                               '1/W of each gradient bucket, cut by the exchange plan and not by the groups.  The modes that take groups are '
+                               'DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
+        if type(self)._adamw_table is not FusedAdamW._adamw_table_hip:
+            return
+        for i, tw in enumerate(self.towers):
+            if tw.flat is None:
+                continue
+            for a, e, _, _ in self._group_ranges(tw, hyper):
+                if (e - a) % 4 or a % 4 or (tw.flat.data_ptr() | tw.flat_grad.data_ptr()) % 16:
+                    raise ValueError(f'FusedAdamW.step: tower {i} range [{a}, {e}) has {e - a} elements at {tw.flat.data_ptr() + 4 * a:#x} (gradient at '
+                                     f'{tw.flat_grad.data_ptr() + 4 * a:#x}); a step with parameter groups (dclip_adamw_table) needs every range, '
+                                     'cut at the group boundaries, to be a multiple of 4 elements on a 16-byte boundary')
+
     @torch.no_grad()
     def step(self, zero_grad=False, overlap=False, join=True):
         """zero_grad=True: the kernel clears each gradient element once it has consumed it (saves the separate 306 MB fill that
@@ -476,6 +626,8 @@ class FusedAdamW:
             raise RuntimeError('FusedAdamW.step: ema_decay is not kept under the sharded data-parallel exchange: every rank updates and '
                                'holds the state of 1/W of each gradient bucket only, and an average in shards would have to be gathered '
                                'to be used.  The modes that keep an EMA are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
+        if self.groups is not None:
+            self._refuse_grouped_step()
         self._refuse_scalar_ranges(self.max_grad_norm is not None, amp is not None, ema_w is not None)
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
@@ -504,7 +656,16 @@ class FusedAdamW:
             joined = [self._update(job, zero_grad, overlap, main, coef, record, ema_w) for job in jobs]
         if extras:
             # the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)
-            self._adamw_many(extras, zero_grad, main.cuda_stream if main is not None else None, coef, record, ema_w)
+            st = main.cuda_stream if main is not None else None
+            if self.groups is None:
+                self._adamw_many(extras, zero_grad, st, coef, record, ema_w)
+            else:                                            # per distinct (lr_scale, weight_decay), through the existing entries
+                hyper, by_key = self._hyper_of(), {}
+                for p, it in zip([p for p in self.extras if p.grad is not None], extras):
+                    by_key.setdefault(hyper.get(id(p), (1.0, self.weight_decay)), []).append(it)
+                for (scale, wd), its in by_key.items():
+                    with self._with_hyper(scale, wd):
+                        self._adamw_many(its, zero_grad, st, coef, record, ema_w)
         if join:
             for stream in joined:
                 if stream is not None:
@@ -667,8 +828,23 @@ class FusedAdamW:
         return m, v
 
     # ---- torch.optim.AdamW-compatible (de)serialisation: what a Lightning checkpoint stores under 'optimizer_states' ----
+    def _partition(self, items, ptr_of):
+        """items split like torch's param_groups: one list per declared group, in the order its 'params' were given, then the rest
+        (the default group) in the order of `items`"""
+        by_ptr = {ptr_of(x): x for x in items}
+        parts = [[by_ptr[p.data_ptr()] for p in g['params'] if p.data_ptr() in by_ptr] for g in self.groups]
+        taken = {p.data_ptr() for g in self.groups for p in g['params']}
+        return parts + [[x for x in items if ptr_of(x) not in taken]]
+
     def _slots(self, params=None):
-        """[(tower, offset, numel, shape)] of the trainable parameters, in `params` order (default: tower order)."""
+        """[(tower, offset, numel, shape)] of the trainable parameters, in `params` order (default: tower order).  With parameter groups:
+        group by group as torch numbers them, the declared groups first, then the default group in `params` order."""
+        slots = self._slots_flat(params)
+        if self.groups is None:
+            return slots
+        return sum(self._partition(slots, lambda s: s[0].data_ptr() if s[1] is None else s[0].flat.data_ptr() + 4 * s[1]), [])
+
+    def _slots_flat(self, params=None):
         where = {}
         for tw in self.towers:
             if tw.flat is None:
@@ -702,13 +878,24 @@ class FusedAdamW:
                 continue
             rng = self._ranges(tw)
             out += [p for p, off in zip([p for p in tw._params() if p is not None], tw._offsets) if any(a <= off < b for a, b in rng)]
-        return out + list(self.extras)
+        out += list(self.extras)
+        return out if self.groups is None else sum(self._partition(out, lambda p: p.data_ptr()), [])
 
     @property
     def param_groups(self):
         """what torch.amp.GradScaler iterates to reach the p.grad views (unscale_, its overflow check): one group over the parameters
-        this optimizer was built over.  A read-only picture: the hyper-parameters are the optimizer's attributes (opt.lr is the knob)."""
-        return [{'params': self._trainable(), 'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay}]
+        this optimizer was built over.  A read-only picture: the hyper-parameters are the optimizer's attributes (opt.lr is the knob).
+        With parameter groups: the declared groups, then the default group with the rest, each with lr = opt.lr * lr_scale; the knobs
+        are opt.lr and the dicts of opt.groups."""
+        one = lambda ps, s, wd: {'params': ps, 'lr': self.lr * s, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': wd}
+        if self.groups is None:
+            return [one(self._trainable(), 1.0, self.weight_decay)]
+        flat = self._trainable()
+        parts = self._partition(flat, lambda p: p.data_ptr())
+        out = []
+        for g, ps in zip(self.groups + [{'lr_scale': 1.0, 'weight_decay': None}], parts):
+            out.append(dict(one(ps, g['lr_scale'], self.weight_decay if g['weight_decay'] is None else g['weight_decay']), lr_scale=g['lr_scale']))
+        return out
 
     def _steps_taken(self):
         """step_count less the steps a loss scaler had skipped (one host read of the device counter)"""
@@ -744,6 +931,14 @@ class FusedAdamW:
                  'weight_decay': self.weight_decay, 'amsgrad': False, 'maximize': False, 'foreach': None,
                  'capturable': False, 'differentiable': False, 'fused': None, 'params': list(range(len(slots)))}
         sd = {'state': state, 'param_groups': [group]}
+        if self.groups is not None:
+            # torch's multi-group layout: parameter ids count on from group to group (_slots() is in that order), lr_scale an extra key
+            sd['param_groups'], at = [], 0
+            sizes = [len(part) for part in self._partition(slots, lambda s: s[0].data_ptr() if s[1] is None else s[0].flat.data_ptr() + 4 * s[1])]
+            for g, n in zip(self.groups + [{'lr_scale': 1.0, 'weight_decay': None}], sizes):
+                s, wd = g['lr_scale'], self.weight_decay if g['weight_decay'] is None else g['weight_decay']
+                sd['param_groups'].append(dict(group, lr=self.lr * s, initial_lr=self.base_lr * s, weight_decay=wd, lr_scale=s, params=list(range(at, at + n))))
+                at += n
         if self._has_ema():
             sd['ema'] = {'decay': self.ema_decay, 'params': self._ema_params(slots)}
         return sd
@@ -754,8 +949,21 @@ class FusedAdamW:
         this optimizer holds: with ema_decay set, the next step() starts a new one from the parameters as they are then."""
         self._refuse_inside_ema('load_state_dict')
         slots = self._slots(params)
-        group = sd['param_groups'][0]
-        if len(group['params']) != len(slots):
+        saved = sd['param_groups']
+        here = 1 if self.groups is None else len(self.groups) + 1
+        if len(saved) != here:
+            raise ValueError(f'FusedAdamW.load_state_dict: the dict has {len(saved)} parameter group(s), this optimizer {here} '
+                             f'({here - 1} declared in `groups` and the default group): build it with the groups the dict was saved with')
+        group = saved[-1]                                    # the default group carries the optimizer's own lr and weight_decay
+        if self.groups is not None:
+            sizes = [len(part) for part in self._partition(slots, lambda s: s[0].data_ptr() if s[1] is None else s[0].flat.data_ptr() + 4 * s[1])]
+            for i, (g, n) in enumerate(zip(saved, sizes)):
+                if len(g['params']) != n:
+                    raise ValueError(f"FusedAdamW.load_state_dict: group {i} has {len(g['params'])} saved parameters, {n} here")
+            for i, (mine, g) in enumerate(zip(self.groups, saved)):
+                new = {'weight_decay': self._group_value(g, i, 'weight_decay', mine['weight_decay']), 'lr_scale': self._group_value(g, i, 'lr_scale', mine['lr_scale'])}
+                mine.update(new)
+        elif len(group['params']) != len(slots):
             raise ValueError(f"FusedAdamW.load_state_dict: {len(group['params'])} saved parameters, {len(slots)} trainable here")
         self.lr = group['lr']
         self.base_lr = group.get('initial_lr', self.base_lr)
@@ -792,6 +1000,23 @@ class FusedAdamW:
         if self._skipped is not None:
             self._skipped.zero_()
         self._load_ema(sd.get('ema'), slots)
+
+
+def no_decay_groups(model):
+    """-> [one group with weight_decay = 0] for FusedAdamW(groups=...) / model.optimizer_groups: every trainable parameter of the student
+    towers (model.towers(), their extra parameters included) with dim() <= 1 — biases, LayerNorm gains and biases, the head-mixing
+    vectors — plus the names each student encoder's no_weight_decay() returns (pos_embed, cls_token): what timm and open_clip leave
+    undecayed by default.  The reference defines no_weight_decay() and never uses it, so this is not the default here either."""
+    params, seen = [], set()
+    for tw in model.towers():
+        skip = set(getattr(tw.module, 'no_weight_decay', lambda: ())())
+        named = {id(p): n for n, p in tw.module.named_parameters()}
+        mine = [p for p in tw._params() if p is not None] + list(getattr(tw.module, 'extra_parameters', lambda: [])())
+        for p in mine:
+            if p.requires_grad and id(p) not in seen and (p.dim() <= 1 or named.get(id(p)) in skip):
+                seen.add(id(p))
+                params.append(p)
+    return [{'params': params, 'weight_decay': 0.0}]
 
 
 class EpochCosineSchedule:

@@ -353,6 +353,46 @@ int dclip_adamw_multi_ema(float* const* p, float* const* g, float* const* m, flo
                           float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, float ema_weight,
                           const float* gscale, const float* record, void* stream);
 int dclip_swap_multi(float* const* a, float* const* b, const int64_t* n, int32_t count, void* stream);
+/*
+ * The same step with per-range hyper-parameters (parameter groups: no decay on 1-D parameters, a smaller learning rate for the parts
+ * that arrive initialised), driven by a table in DEVICE memory: ONE launch for any number of ranges, no cap of DCLIP_ADAMW_MAX_RANGES.
+ * p, g, m, v and e are the BASES of five streams that share one flat layout (a tower's flat buffers); range k covers the elements
+ * [begin, begin + length) of each of them.
+ *   adamw_table_bytes : size of the table of `count` ranges: count + 1 records of 32 bytes, the struct below; 0 for count < 1.
+ *   adamw_table_fill  : builds and validates the HOST image of the table, which the caller then copies to the device (8-byte aligned
+ *                       there too).  begin, length, lr_scale, weight_decay: HOST arrays of `count` >= 1 entries.  Ranges ascend, do not
+ *                       overlap and are not empty; begin and length are multiples of 4 elements (with 16-byte aligned bases every range
+ *                       is then 16-byte aligned); lr_scale is finite and >= 0, weight_decay finite; every range ends inside `total`,
+ *                       the element count of the buffers, which the caller states.  Record k also holds tile0, the first tile of
+ *                       range k in the launch's tile list: every range starts a new tile of DCLIP_ADAMW_TABLE_TILE elements; record
+ *                       `count` closes the list with the number of tiles, which *tiles returns.  A refusal writes neither the image
+ *                       nor *tiles.
+ *   adamw_table       : gscale == NULL and record == NULL: the step of dclip_adamw_multi ; gscale alone: of dclip_adamw_multi_scaled ;
+ *                       record alone: of dclip_adamw_multi_amp (`step` is then not read) ; both: refused.  e != NULL: it keeps the
+ *                       average of dclip_adamw_multi_ema with ema_weight (e == NULL, or ema_weight == 0: e is neither read nor written).
+ *                       Roundings: per range lr_k = lr * lr_scale_k, ONE f32 product of the two f32 values, and wd_k = weight_decay_k as
+ *                       stored; after that every element is computed exactly as by those entries called on the range alone with
+ *                       lr_k and wd_k: p, g, m, v, e come out bit for bit as from them.  No atomics: the same call gives the same
+ *                       bits.  A skipped step (record[DCLIP_AMP_SKIP] set) reads and writes no p, m, v, e; g is still cleared if
+ *                       zero_grad.  Elements outside the ranges are neither read nor written.
+ *                       table, count, tiles: the device copy of an image of adamw_table_fill, and what it was filled with / returned.
+ *                       Refused on the host, before any launch: a NULL or misaligned base (e may be NULL), a NULL or misaligned
+ *                       table, count < 1, tiles < count or > 2^31 - 1, step < 1 without a record, a misaligned record, gscale
+ *                       together with record, ema_weight outside [0, 1] or NaN with e given.  The table itself is in device memory:
+ *                       the host cannot see it, and a table that does not match count and the buffers is the caller's error.
+ */
+#define DCLIP_ADAMW_TABLE_TILE 8192
+typedef struct dclip_adamw_range {
+    int64_t tile0;            /* first tile of the range ; in record `count`: the number of tiles */
+    int64_t begin, length;    /* elements, multiples of 4 */
+    float lr_scale, weight_decay;
+} dclip_adamw_range;
+size_t dclip_adamw_table_bytes(int32_t count);
+int dclip_adamw_table_fill(const int64_t* begin, const int64_t* length, const float* lr_scale, const float* weight_decay, int32_t count,
+                           int64_t total, void* image, size_t image_bytes, int64_t* tiles);
+int dclip_adamw_table(float* p, float* g, float* m, float* v, float* e, const void* table, int32_t count, int64_t tiles, float lr, float beta1,
+                      float beta2, float eps, int64_t step, int zero_grad, float ema_weight, const float* gscale, const float* record,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused distillation loss, forward + backward.
