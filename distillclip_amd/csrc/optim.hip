@@ -5,6 +5,7 @@
 // scaler's 1 / scale, its overflow flag and the bias corrections of the steps that were not skipped.  An exponential moving average of the
 // parameters kept by the same kernel (dclip_adamw_multi_ema), and the exchange of parameters and average in place (dclip_swap_multi).
 #include "common.h"
+#include "optim_elem.h"   // adamw_elem, ema_elem, AdamwMode, the table's tile constants and lookup: shared with lamb.hip
 
 #include <math.h>
 
@@ -144,16 +145,7 @@ __global__ __launch_bounds__(256) void amp_prepare_kernel(const float* __restric
     }
 }
 
-// torch.optim.AdamW semantics (decoupled weight decay; bias-corrected), reference distil_model.py:160-162
-__device__ __forceinline__ void adamw_elem(float& pi, float gi, float& mi, float& vi, float lr, float b1, float b2, float eps,
-                                           float wd, float bc1, float bc2_sqrt) {
-    pi = pi * (1.f - lr * wd);
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-}
-
+// (adamw_elem: optim_elem.h)
 // an element per thread: ranges that are misaligned, and the tail of < 4 elements of the others
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2,
@@ -176,19 +168,13 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 struct AdamwRanges { float4* p[DCLIP_ADAMW_MAX_RANGES]; float4* g[DCLIP_ADAMW_MAX_RANGES]; float4* m[DCLIP_ADAMW_MAX_RANGES]; float4* v[DCLIP_ADAMW_MAX_RANGES]; int64_t n4[DCLIP_ADAMW_MAX_RANGES]; };
 // AMP: gscale points at the record of amp_prepare_kernel, whose first four floats (multiplier, skip flag, the two bias corrections:
 // one 16-byte load, the same for every lane) take the place of *gscale, bc1 and bc2_sqrt.  A skipped step writes no p, m or v and
-// reads nothing; the gradients, which hold an overflow, are still cleared on request.
-enum AdamwMode { ADAMW_PLAIN = 0, ADAMW_SCALED = 1, ADAMW_AMP = 2 };
+// reads nothing; the gradients, which hold an overflow, are still cleared on request.  (enum AdamwMode: optim_elem.h)
 // EMA: a fifth stream e per range, the exponential moving average of the parameters, advanced with weight w = 1 - decay from the p this
 // launch writes (include/dclip.h: dclip_adamw_multi_ema).  The ranges of these instantiations are a struct of their own, which also
 // carries w, so that the kernel arguments of the others stay what they were.  e travels with p, m, v: loaded with the next trip's
 // loads, stored with the current trip's stores, neither read nor written by a skipped step.
 struct AdamwEmaRanges : AdamwRanges { float4* e[DCLIP_ADAMW_MAX_RANGES]; float w; };
-// e <- e + w (p - e): the difference rounded once, then one fmaf, two roundings in all.  p == e gives a difference of 0 and e back as it
-// is (the select keeps the sign of a zero, which 0 + (-0) would lose).
-__device__ __forceinline__ void ema_elem(float& ei, float pi, float w) {
-    const float d = pi - ei;
-    ei = d == 0.f ? ei : fmaf(w, d, ei);
-}
+// (ema_elem, e <- e + w (p - e) in two roundings: optim_elem.h)
 template <int MODE, bool EMA = false>
 __global__ __launch_bounds__(256) void adamw4_multi_kernel(std::conditional_t<EMA, AdamwEmaRanges, AdamwRanges> r, float lr, float b1, float b2, float eps,
                                                            float wd, float bc1, float bc2_sqrt, int zero_grad, const float* __restrict__ gscale) {
@@ -246,9 +232,7 @@ __global__ __launch_bounds__(256) void adamw4_multi_kernel(std::conditional_t<EM
 // loop is adamw4_multi_kernel's with a stride of one trip: the float4 loads of the next trip are issued before the stores of the current
 // one, zero_grad and a skipped step are handled the same way, the arithmetic is adamw_elem / ema_elem on lr_k = lr * lr_scale_k (one
 // f32 product) and wd_k.  No atomics, every element is touched by exactly one lane: the same call gives the same bits.
-constexpr int TABLE_TRIPS = DCLIP_ADAMW_TABLE_TILE / 1024;
-constexpr int TABLE_TILE4 = 256 * TABLE_TRIPS;          // float4 per tile
-static_assert(sizeof(dclip_adamw_range) == 32 && DCLIP_ADAMW_TABLE_TILE % 1024 == 0, "the table's record is 32 bytes, a tile whole trips");
+// (TABLE_TRIPS, TABLE_TILE4: optim_elem.h)
 template <int MODE, bool EMA>
 __global__ __launch_bounds__(256) void adamw4_table_kernel(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m, float4* __restrict__ v,
                                                            float4* __restrict__ e, const dclip_adamw_range* __restrict__ tab, int count, float lr, float b1,
@@ -257,8 +241,8 @@ __global__ __launch_bounds__(256) void adamw4_table_kernel(float4* __restrict__ 
     constexpr bool SCALED = MODE != ADAMW_PLAIN;
     const int64_t t = blockIdx.x;
     if (t >= tab[count].tile0) return;                   // (a grid wider than the table's tile list: nothing to do, nothing read past it)
-    int lo = 0, hi = count;                              // tab[lo].tile0 <= t < tab[hi].tile0 (uniform)
-    while (hi - lo > 1) {
+    int lo = 0, hi = count;                              // tab[lo].tile0 <= t < tab[hi].tile0 (uniform) ; table_range_of() is these lines: calling
+    while (hi - lo > 1) {                                // it here swaps the operands of one s_add_i32, so this kernel keeps its own copy
         const int mid = (lo + hi) >> 1;
         if (tab[mid].tile0 <= t) lo = mid; else hi = mid;
     }

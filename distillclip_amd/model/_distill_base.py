@@ -61,9 +61,14 @@ class DistillBase(nn.Module):
     # step.  validate_with_ema: the validation loop runs on that average (on_validation_start / on_validation_end).
     # optimizer_groups: FusedAdamW's `groups`, a list of {'params', 'weight_decay', 'lr_scale'} dicts or a callable model -> such a list
     # (e.g. distillclip_amd.optim.no_decay_groups); None: one weight decay and one learning rate for every trainable element.
+    # trust_ratio, trust_clip, always_adapt: FusedAdamW's arguments of the same names (layer-wise trust ratios, LAMB); trust_ratio None
+    # or False: plain AdamW.
     ema_decay = None
     validate_with_ema = False
     optimizer_groups = None
+    trust_ratio = None
+    trust_clip = None
+    always_adapt = False
     _optimizer = None              # the optimizer configure_optimizers() built
     _ema_context = None            # the entered FusedAdamW.ema_weights() of a validation loop
 
@@ -112,7 +117,7 @@ class DistillBase(nn.Module):
                   for p in getattr(tw.module, 'extra_parameters', lambda: [])()]
         groups = self.optimizer_groups(self) if callable(self.optimizer_groups) else self.optimizer_groups
         opt = FusedAdamW(towers, lr=self.hparams.lr, weight_decay=self.hparams.weight_decay, extra_params=extras, ema_decay=self.ema_decay,
-                         groups=groups)
+                         groups=groups, trust_ratio=bool(self.trust_ratio), trust_clip=self.trust_clip, always_adapt=self.always_adapt)
         self._optimizer = opt
         sched = EpochCosineSchedule(opt, self.hparams.warm_steps, self.hparams.total_steps)
         self._ensure_sync()          # data-parallel run: shard plan over the same trainable set the optimizer was built with

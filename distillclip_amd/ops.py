@@ -446,6 +446,29 @@ def adamw_table(p, g, m, v, e, table, count, tiles, lr, betas, eps, step, zero_g
                             ema_weight, _p(gscale), _p(record), _stream() if stream is None else stream)
 
 
+def lamb_buffers(count, tiles, device):
+    """-> (workspace, stats) of lamb_table for a table of `count` ranges and `tiles` tiles: the tile records (uint8,
+    dclip_lamb_workspace_bytes) and the f32 [count, 4] rows {|p|, |u|, r, 0}, zero until the first step"""
+    return (torch.empty(max(lib().dclip_lamb_workspace_bytes(count, tiles), 16), dtype=torch.uint8, device=device),
+            torch.zeros(count, 4, dtype=torch.float32, device=device))
+
+
+def lamb_table(p, g, m, v, e, table, count, tiles, lr, betas, eps, step, workspace, stats, zero_grad=False, ema_weight=0.0, gscale=None, record=None,
+               trust_clip=None, always_adapt=False, stream=None):
+    """adamw_table's operands, stepped with a trust ratio per range (include/dclip.h: dclip_lamb_table): three launches.  workspace, stats:
+    lamb_buffers(count, tiles); stats holds {|p|, |u|, r, 0} per range afterwards.  trust_clip: None = no clip."""
+    _chk(p, g, m, v, e, table, gscale, record, workspace, stats)
+    if table.dtype != torch.uint8 or table.numel() < lib().dclip_adamw_table_bytes(count):
+        raise ValueError('lamb_table: table is the uint8 device copy of an image of %d ranges' % count)
+    if any(t.numel() != p.numel() or t.dtype != torch.float32 for t in (p, g, m, v) + (() if e is None else (e,))):
+        raise ValueError('lamb_table: p, g, m, v (and e) are f32 buffers of one length, the `total` the table was filled for')
+    if workspace.dtype != torch.uint8 or stats.dtype != torch.float32 or stats.numel() < 4 * count:
+        raise ValueError('lamb_table: workspace is uint8, stats f32 [%d, 4] (lamb_buffers)' % count)
+    lib().dclip_lamb_table(_p(p), _p(g), _p(m), _p(v), _p(e), _p(table), count, tiles, lr, betas[0], betas[1], eps, step, 1 if zero_grad else 0,
+                           ema_weight, _p(gscale), _p(record), -1.0 if trust_clip is None else float(trust_clip), 1 if always_adapt else 0,
+                           _p(workspace), workspace.numel(), _p(stats), _stream() if stream is None else stream)
+
+
 def swap_multi(pairs, stream=None):
     """a <-> b, bit for bit, for at most 24 pairs [(a, b)] of equally long 1-D f32 tensors in ONE launch (include/dclip.h: dclip_swap_multi)"""
     import ctypes

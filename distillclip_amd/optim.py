@@ -77,12 +77,31 @@ class FusedAdamW:
     exchange RuntimeError, both before the step counter moves (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off work).  param_groups lists
     the declared groups and then the default group, each with lr = opt.lr * lr_scale; state_dict() writes torch's multi-group layout
     with lr_scale as an extra key per group, which torch.optim.AdamW([*groups, {'params': rest}]) loads and whose own dict loads back;
-    a dict with another number of groups is a ValueError."""
+    a dict with another number of groups is a ValueError.
+
+    trust_ratio (False = off, and then every launch and every bit is what it is without the argument), trust_clip (None = no clip),
+    always_adapt: plain attributes, may change between steps.  With trust_ratio the step is LAMB's (You et al. 2020, timm's Lamb): every
+    trainable parameter tensor is one UNIT, its update u = m^ / (sqrt(v^) + eps) + wd p (weight decay INSIDE the update, not AdamW's
+    p (1 - lr wd)) is scaled by r = |p| / |u|, the L2 norms over the unit's old parameters and its update, and p' = p - lr lr_scale r u.
+    r = 1 for a unit whose weight decay is 0 unless always_adapt, and where a norm is 0 or not finite; r <= trust_clip if that is set.
+    m and v mean what they mean in AdamW, so switching between steps is well defined.  Every tower is stepped by dclip_lamb_table
+    (three launches: moments and partial norms, ratios, apply) over a table cut at EVERY trainable parameter's offset (the layout's
+    padding goes with the parameter before it) with the (lr_scale, weight_decay) of its group, or (1, weight_decay) without groups; the
+    table is built and re-uploaded by the mechanism of `groups`, workspace and statistics are allocated once per tower.  It composes
+    with max_grad_norm (the norm stays global and is formed before the ratios), a loss scaler (a skipped step changes nothing, the
+    statistics included), ema_decay, groups and overlap / join=False, with no host wait.  Extra parameters are one unit each, every one
+    stepped by the same entry as its own one-range layout: three tiny launches per tensor, a dozen for the four projection tensors of a
+    plain CLIP student, which is accepted.  last_trust_stats: {tower index: f32 [units, 4] device tensor of (|p|, |u|, r, 0)} and
+    {('extra', j): f32 [1, 4]} after a step; trust_units() lists (parameter name, begin, length) per key in the same order.  Refused
+    before the step counter moves: ValueError for a unit that is no multiple of 4 elements or off a 16-byte boundary and for a
+    trust_clip that is <= 0 or not finite, RuntimeError under the sharded data-parallel exchange (DCLIP_DP_MODE=allreduce and
+    DCLIP_DP_MODE=off work).  state_dict() then carries trust_ratio / trust_clip / always_adapt as extra keys of every parameter group
+    (torch.optim.AdamW.load_state_dict ignores them, like lr_scale); load_state_dict() restores them."""
 
     _step_supports_amp_scaling = True
 
     def __init__(self, towers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, extra_params=(), max_grad_norm=None, ema_decay=None,
-                 groups=None):
+                 groups=None, trust_ratio=False, trust_clip=None, always_adapt=False):
         """extra_params: trainable parameters that live outside the towers' flat buffers — the embedding_projection / hidden_projection
         linears of a plain CLIP encoder in the student role (reference image_encoder.py:23-25, text_encoder.py:45-47): four small tensors
         whose gradients autograd produces; they are updated together, like one more tower's ranges (after an all-reduce of each gradient
@@ -111,6 +130,10 @@ class FusedAdamW:
         self._ema_in_use = False                           # inside ema_weights(): parameters and average have changed places
         self.groups = None if groups is None else self._declare_groups(groups)
         self._tables = {}                                  # id(tower) -> the device table of its ranges and what it was filled from
+        self.trust_ratio, self.trust_clip, self.always_adapt = bool(trust_ratio), trust_clip, bool(always_adapt)
+        self._lamb = {}                                    # id(tower or extra parameter) -> (workspace, stats) of dclip_lamb_table
+        self.last_trust_stats = {}                         # tower index / ('extra', j) -> f32 [units, 4] on the device: (|p|, |u|, r, 0)
+        self._trust_clip_value()
 
     def _ranges(self, tw):
         """contiguous [begin, end) element ranges of the parameters this optimizer was built over"""
@@ -174,10 +197,11 @@ class FusedAdamW:
             out.update((id(p), (key[0], self.weight_decay if key[1] is None else key[1])) for p in g['params'])
         return out
 
-    def _group_ranges(self, tw, hyper=None):
+    def _group_ranges(self, tw, hyper=None, units=False):
         """[(begin, end, lr_scale, weight_decay)] of a tower: its fixed ranges cut where neighbouring parameters differ in (lr_scale,
-        weight_decay).  A parameter's segment runs to the next parameter's offset (the layout's padding goes with the parameter before it)."""
-        hyper = self._hyper_of() if hyper is None else hyper
+        weight_decay).  A parameter's segment runs to the next parameter's offset (the layout's padding goes with the parameter before it).
+        units: cut at EVERY parameter's offset, equal neighbours are not merged (the trust-ratio step: one range per tensor)."""
+        hyper = (self._hyper_of() if self.groups is not None else {}) if hyper is None else hyper
         default = (1.0, self.weight_decay)
         segs = sorted((off, hyper.get(id(p), default)) for p, off in zip([p for p in tw._params() if p is not None], tw._offsets))
         out = []
@@ -186,7 +210,7 @@ class FusedAdamW:
             if not inside or inside[0][0] != a:
                 inside.insert(0, (a, default))
             for (off, key), nxt in zip(inside, [o for o, _ in inside[1:]] + [b]):
-                if out and out[-1][1] == off and out[-1][2:] == key and off != a:
+                if not units and out and out[-1][1] == off and out[-1][2:] == key and off != a:
                     out[-1] = (out[-1][0], nxt) + key
                 else:
                     out.append((off, nxt) + key)
@@ -198,19 +222,102 @@ class FusedAdamW:
         asynchronous copy on the stream the update runs on (the current one), so the launches of that stream see it in order and no
         host waits.  (`_adamw_table` can be substituted by a torch version like `_adamw`.)"""
         from . import ops
-        tab = self._tables.get(id(tw))
-        if tab is None or tab['ranges'] != ranges:
-            rows = [(b, e - b, s, wd) for b, e, s, wd in ranges]
-            image, tiles = ops.adamw_table_image(rows, bufs[0].numel(), torch.zeros(lib().dclip_adamw_table_bytes(len(rows)), dtype=torch.uint8).pin_memory())
-            if tab is None or tab['dev'].numel() != image.numel():
-                tab = self._tables[id(tw)] = {'dev': torch.empty(image.numel(), dtype=torch.uint8, device=bufs[0].device), 'uploads': 0}
-            tab['dev'].copy_(image, non_blocking=True)
-            tab.update(ranges=list(ranges), tiles=tiles, uploads=tab['uploads'] + 1)
+        tab = self._table_of(id(tw), bufs[0], ranges)
         p, g, m, v, e = bufs
         ops.adamw_table(p, g, m, v, e, tab['dev'], len(ranges), tab['tiles'], self.lr, self.betas, self.eps, self.step_count, zero_grad,
                         0.0 if ema_weight is None else ema_weight, gscale, record, st)
 
     _adamw_table = _adamw_table_hip
+
+    def _table_of(self, key, flat, ranges):
+        """the device table of `ranges` over the flat buffer `flat`, kept under `key`: built on first use, uploaded again when `ranges` differ"""
+        from . import ops
+        tab = self._tables.get(key)
+        if tab is None or tab['ranges'] != ranges:
+            rows = [(b, e - b, s, wd) for b, e, s, wd in ranges]
+            image, tiles = ops.adamw_table_image(rows, flat.numel(), torch.zeros(lib().dclip_adamw_table_bytes(len(rows)), dtype=torch.uint8).pin_memory())
+            if tab is None or tab['dev'].numel() != image.numel():
+                tab = self._tables[key] = {'dev': torch.empty(image.numel(), dtype=torch.uint8, device=flat.device), 'uploads': 0}
+            tab['dev'].copy_(image, non_blocking=True)
+            tab.update(ranges=list(ranges), tiles=tiles, uploads=tab['uploads'] + 1)
+        return tab
+
+    # ---- layer-wise trust ratios (trust_ratio) ----
+    def _trust_clip_value(self):
+        """None, or trust_clip as a float; ValueError unless it is finite and > 0"""
+        c = self.trust_clip
+        if c is None:
+            return None
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c <= 0:
+            raise ValueError(f'FusedAdamW: trust_clip must be None or a finite number > 0, got {c!r}')
+        return float(c)
+
+    def _lamb_table_hip(self, key, bufs, ranges, zero_grad, st, ema_weight, gscale, record):
+        """bufs: a whole flat (p, g, m, v, e or None); ranges: its units, [(begin, end, lr_scale, weight_decay)].  The three launches of
+        dclip_lamb_table; the table is _table_of's, workspace and statistics are allocated at the first step and again only when the
+        number of units or tiles changes.  -> the statistics, f32 [units, 4] on the device.  (`_lamb_table` can be substituted by a
+        torch version like `_adamw`.)"""
+        from . import ops
+        tab = self._table_of(key, bufs[0], ranges)
+        held = self._lamb.get(key)
+        if held is None or held[0] != (len(ranges), tab['tiles']):
+            held = self._lamb[key] = ((len(ranges), tab['tiles']),) + ops.lamb_buffers(len(ranges), tab['tiles'], bufs[0].device)
+        p, g, m, v, e = bufs
+        ops.lamb_table(p, g, m, v, e, tab['dev'], len(ranges), tab['tiles'], self.lr, self.betas, self.eps, self.step_count, held[1], held[2], zero_grad,
+                       0.0 if ema_weight is None else ema_weight, gscale, record, self._trust_clip_value(), self.always_adapt, st)
+        return held[2]
+
+    _lamb_table = _lamb_table_hip
+
+    def _extra_hyper(self):
+        """{id(extra parameter): (lr_scale, weight_decay)}"""
+        hyper = self._hyper_of() if self.groups is not None else {}
+        return {id(p): hyper.get(id(p), (1.0, self.weight_decay)) for p in self.extras}
+
+    def trust_units(self):
+        """{tower index: [(parameter name, begin, length)], ('extra', j): [(name, 0, numel)]}: the units of a trust-ratio step, in the
+        order of the rows of last_trust_stats (begin and length in elements of the tower's flat buffer, the layout's padding included)"""
+        out = {}
+        for i, tw in enumerate(self.towers):
+            module = getattr(tw, 'module', None)
+            named = {id(p): n for n, p in module.named_parameters()} if module is not None else {}
+            at = {off: named.get(id(p), f'parameter {j}') for j, (p, off) in enumerate(zip([p for p in tw._params() if p is not None], tw._offsets))}
+            fresh = id(tw) not in self._fixed_ranges
+            out[i] = [(at.get(a, f'[{a}, {b})'), a, b - a) for a, b, _, _ in self._group_ranges(tw, {}, units=True)]
+            if fresh and tw.flat is None:                    # a tower that is not materialised yet: its trainable set is captured at its first step
+                del self._fixed_ranges[id(tw)]
+        names = {}
+        for tw in self.towers:
+            module = getattr(tw, 'module', None)
+            if module is not None:
+                names.update((id(p), n) for n, p in module.named_parameters())
+        for j, p in enumerate(self.extras):
+            out[('extra', j)] = [(names.get(id(p), f'extra parameter {j}'), 0, p.numel())]
+        return out
+
+    def _refuse_trust_step(self):
+        """trust ratios: dclip_lamb_table is float4 only and has no sharded form.  Refused here, before the step counter moves: a bad
+        trust_clip, the sharded exchange, a unit (a tower's or an extra parameter) that is odd or off a 16-byte boundary"""
+        self._trust_clip_value()
+        if any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
+            raise RuntimeError('FusedAdamW.step: trust ratios are not formed under the sharded data-parallel exchange: every rank updates 1/W of '
+                               'each gradient bucket, cut by the exchange plan and not at the tensors, so no rank holds a whole unit\'s norm.  '
+                               'The modes that take trust_ratio are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
+        if type(self)._lamb_table is not FusedAdamW._lamb_table_hip:
+            return
+        hyper = self._hyper_of() if self.groups is not None else {}
+        tail = 'a step with trust ratios (dclip_lamb_table) needs every unit, one per parameter tensor, to be a multiple of 4 elements on a 16-byte boundary'
+        for i, tw in enumerate(self.towers):
+            if tw.flat is None:
+                continue
+            for a, e, _, _ in self._group_ranges(tw, hyper, units=True):
+                if (e - a) % 4 or a % 4 or (tw.flat.data_ptr() | tw.flat_grad.data_ptr()) % 16:
+                    raise ValueError(f'FusedAdamW.step: tower {i} range [{a}, {e}) has {e - a} elements at {tw.flat.data_ptr() + 4 * a:#x} (gradient at '
+                                     f'{tw.flat_grad.data_ptr() + 4 * a:#x}); {tail}')
+        for i, p in enumerate(self.extras):
+            if p.grad is not None and (p.numel() % 4 or (p.data_ptr() | p.grad.data_ptr()) % 16):
+                raise ValueError(f'FusedAdamW.step: extra parameter {i} ({tuple(p.shape)}) has {p.numel()} elements at {p.data_ptr():#x} (gradient at '
+                                 f'{p.grad.data_ptr():#x}); {tail}')
 
     @contextlib.contextmanager
     def _with_hyper(self, lr_scale, weight_decay):
@@ -474,7 +581,12 @@ class FusedAdamW:
                 self._ema[id(tw)].copy_(tw.flat)
                 self._ema_unseeded.discard(id(tw))
             st = stream.cuda_stream if stream is not None else None
-            if self.groups is None:
+            if self.trust_ratio:                             # one unit per tensor: moments and partial norms, ratios, apply
+                m, v = self._moments(tw)
+                self.last_trust_stats[self.towers.index(tw)] = self._lamb_table(
+                    id(tw), (tw.flat, tw.flat_grad, m, v, self._ema[id(tw)] if ema_weight is not None else None),
+                    self._group_ranges(tw, units=True), zero_grad, st, ema_weight, coef, record)
+            elif self.groups is None:
                 self._adamw_many(items, zero_grad, st, coef, record, ema_weight)
             else:                                            # one table-driven launch for the tower, whichever of the three steps it is
                 m, v = self._moments(tw)
@@ -628,6 +740,8 @@ class FusedAdamW:
                                'to be used.  The modes that keep an EMA are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
         if self.groups is not None:
             self._refuse_grouped_step()
+        if self.trust_ratio:
+            self._refuse_trust_step()
         self._refuse_scalar_ranges(self.max_grad_norm is not None, amp is not None, ema_w is not None)
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
@@ -657,7 +771,15 @@ class FusedAdamW:
         if extras:
             # the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)
             st = main.cuda_stream if main is not None else None
-            if self.groups is None:
+            if self.trust_ratio:                             # every tensor is its own one-range layout
+                hyper = self._extra_hyper()
+                for j, p in enumerate(self.extras):
+                    if p.grad is None:
+                        continue
+                    it = extras.pop(0)
+                    self.last_trust_stats[('extra', j)] = self._lamb_table(id(p), it if ema_w is not None else it + (None,), [(0, p.numel()) + hyper[id(p)]],
+                                                                           zero_grad, st, ema_w, coef, record)
+            elif self.groups is None:
                 self._adamw_many(extras, zero_grad, st, coef, record, ema_w)
             else:                                            # per distinct (lr_scale, weight_decay), through the existing entries
                 hyper, by_key = self._hyper_of(), {}
@@ -939,6 +1061,9 @@ class FusedAdamW:
                 s, wd = g['lr_scale'], self.weight_decay if g['weight_decay'] is None else g['weight_decay']
                 sd['param_groups'].append(dict(group, lr=self.lr * s, initial_lr=self.base_lr * s, weight_decay=wd, lr_scale=s, params=list(range(at, at + n))))
                 at += n
+        if self.trust_ratio:                                 # extra keys of every group, like lr_scale: torch ignores them, load_state_dict() restores them
+            for g in sd['param_groups']:
+                g.update(trust_ratio=True, trust_clip=self._trust_clip_value(), always_adapt=self.always_adapt)
         if self._has_ema():
             sd['ema'] = {'decay': self.ema_decay, 'params': self._ema_params(slots)}
         return sd
@@ -968,6 +1093,9 @@ class FusedAdamW:
         self.lr = group['lr']
         self.base_lr = group.get('initial_lr', self.base_lr)
         self.betas, self.eps, self.weight_decay = tuple(group['betas']), group['eps'], group['weight_decay']
+        if 'trust_ratio' in group:                           # (a dict saved with the feature off, or torch's own, has no such key: keep what is set)
+            self.trust_ratio, self.trust_clip, self.always_adapt = bool(group['trust_ratio']), group.get('trust_clip'), bool(group.get('always_adapt', False))
+            self._trust_clip_value()
         steps = set()
         for i, (tw, off, n, shape) in enumerate(slots):
             st = sd['state'].get(i, sd['state'].get(str(i)))
@@ -1000,6 +1128,13 @@ class FusedAdamW:
         if self._skipped is not None:
             self._skipped.zero_()
         self._load_ema(sd.get('ema'), slots)
+
+
+class FusedLAMB(FusedAdamW):
+    """FusedAdamW with trust_ratio=True: LAMB on the towers' flat buffers (the class docstring of FusedAdamW states the arithmetic)."""
+
+    def __init__(self, towers, *args, trust_ratio=True, **kw):
+        super().__init__(towers, *args, trust_ratio=trust_ratio, **kw)
 
 
 def no_decay_groups(model):

@@ -393,6 +393,36 @@ int dclip_adamw_table_fill(const int64_t* begin, const int64_t* length, const fl
 int dclip_adamw_table(float* p, float* g, float* m, float* v, float* e, const void* table, int32_t count, int64_t tiles, float lr, float beta1,
                       float beta2, float eps, int64_t step, int zero_grad, float ema_weight, const float* gscale, const float* record,
                       void* stream);
+/*
+ * Layer-wise trust ratios (LAMB; You et al. 2020, timm's Lamb) on the same table: one range is one UNIT, normally one parameter tensor,
+ * and its update is scaled by |p| / |u|, the L2 norms taken over the unit.  Per element of unit k, in f32, with g' = g, g * *gscale or
+ * g * record[DCLIP_AMP_MULT] and the bias corrections bc1, bc2s of dclip_adamw_table:
+ *       m'  = b1 m + (1 - b1) g' ;  v' = b2 v + (1 - b2) g' g'           (the very lines of the AdamW kernels: m', v' come out bit for bit
+ *                                                                          as from dclip_adamw_table on the same inputs)
+ *       u   = fmaf(wd_k, p, (m' / bc1) / (sqrtf(v') / bc2s + eps))        weight decay INSIDE the update, not the p (1 - lr wd) of AdamW
+ *       r_k = 1                      if wd_k == 0 and not always_adapt
+ *           = |p| / |u|              if both norms, rounded to f32, are > 0 and finite, else 1 ; the quotient of the double norms, rounded once
+ *       r_k = min(r_k, trust_clip)   if trust_clip >= 0
+ *       p'  = fmaf(-(lr_k * r_k), u, p)     lr_k = lr * lr_scale_k, ONE f32 product, then ONE f32 product with r_k
+ *       e   <- the average of dclip_adamw_multi_ema from p' (e == NULL, or ema_weight == 0: e is neither read nor written)
+ *   The norms are over the OLD p and over u.  Three launches on `stream`, no atomics, no host synchronisation: the same call gives the
+ *   same bits.  Sums of squares: per tile of DCLIP_ADAMW_TABLE_TILE elements every lane adds its <= 32 squares in f32 (four chains of
+ *   <= 8 fused multiply-adds and two additions: relative error <= 10 * 2^-24 of the lane's sum), everything above the lane is added in
+ *   double, in a fixed order.
+ *   lamb_workspace_bytes : bytes of the tile records (16 per tile) for a table of `count` ranges and `tiles` tiles; 0 for count < 1,
+ *                          tiles < count or tiles > 2^31 - 1.
+ *   lamb_table           : table, count, tiles: as dclip_adamw_table (an uploaded image of dclip_adamw_table_fill).  workspace: DEVICE,
+ *                          16-byte aligned, ws_bytes >= lamb_workspace_bytes; contents need not survive between calls.  stats: DEVICE,
+ *                          f32 [count][4], 16-byte aligned: {|p|, |u|, r_k, 0} of every range after the call.
+ *                          A skipped step (record[DCLIP_AMP_SKIP] set) changes no byte of p, m, v, e and of stats; g is still cleared if
+ *                          zero_grad.  Elements outside the ranges are neither read nor written.
+ *                          Refused on the host, before any launch: whatever dclip_adamw_table refuses, a NULL or misaligned workspace
+ *                          or stats, a workspace smaller than lamb_workspace_bytes, a NaN trust_clip (trust_clip < 0: no clip).
+ */
+size_t dclip_lamb_workspace_bytes(int32_t count, int64_t tiles);
+int dclip_lamb_table(float* p, float* g, float* m, float* v, float* e, const void* table, int32_t count, int64_t tiles, float lr, float beta1,
+                     float beta2, float eps, int64_t step, int zero_grad, float ema_weight, const float* gscale, const float* record,
+                     float trust_clip, int always_adapt, void* workspace, size_t ws_bytes, float* stats, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused distillation loss, forward + backward.
