@@ -1,20 +1,27 @@
 """Rank correlation of L-CLIPScore with human ratings, the number a caption metric is judged by: Kendall tau-c on Flickr8k-Expert
-(5 664 pairs x 3 annotators) and Composite, tau-b on Flickr8k-CF, as CLIPScore (Hessel et al. 2021) and the work after it report them.
+(5 664 pairs x 3 annotators) and Composite, tau-b on Flickr8k-CF, as CLIPScore (Hessel et al. 2021) and the work after it report them;
+Spearman rho and Pearson r where a benchmark reports those instead or as well (THumB, WMT-style metric evaluations, comparisons with learned metrics).
 
     hc = HumanCorrelation.from_model(model)
     for images, candidates, human, references, ref_counts in loader:     # human [B] (or [B, K]), or [B, A] with A annotators per pair
         hc.update(images, candidates, human, references, ref_counts)
     metrics = hc.compute()                           # {'clip_s_tau_b': .., 'clip_s_tau_c': .., 'refclip_s_tau_c': .., ..}
+    more = hc.compute(stats=('spearman', 'pearson'))                     # {'clip_s_spearman': .., 'clip_s_pearson': .., ..}
 
 The scorer runs as in score.py; the stored score vectors are correlated with the stored ratings by ONE call of the HIP kernels behind
-`metrics.kendall_tau` (include/dclip.h: dclip_kendall_tau), all score kinds in the same pass.  Nothing here waits for the device.
-Gathering across ranks is out of scope: `add_scores` takes flat vectors formed elsewhere, gathered ones included, and is the hook for it.
+`metrics.kendall_tau` (include/dclip.h: dclip_kendall_tau), all score kinds in the same pass; `stats` adds or substitutes Spearman and
+Pearson, again ONE call of `metrics.rank_correlation` (dclip_rank_correlation) for all score kinds, and no Kendall call when 'kendall' is
+not asked for.  Nothing here waits for the device.
+Out of scope: gathering across ranks (`add_scores` takes flat vectors formed elsewhere, gathered ones included, and is the hook for it),
+p-values and confidence intervals, weighted variants, more than 262 144 rated items, and sharing one pair walk between the Kendall and
+the rank kernels.
 """
 import torch
 
-from .metrics import KENDALL_MAX_ITEMS, kendall_tau
+from .metrics import KENDALL_MAX_ITEMS, kendall_tau, rank_correlation
 
 SCORE_NAMES = ('clip_s', 'ref_s', 'refclip_s')
+STATS = ('kendall', 'spearman', 'pearson')
 
 
 class HumanCorrelation:
@@ -94,10 +101,18 @@ class HumanCorrelation:
             raise ValueError('HumanCorrelation: add_scores takes device tensors (distillclip_amd has no CPU path)')
         self._store(human.detach().float(), [None if v is None else v.detach().float() for v in vectors], with_refs)
 
-    def compute(self, return_counts=False):
+    def compute(self, return_counts=False, stats=('kendall',)):
         """-> {'clip_s_tau_b', 'clip_s_tau_c'}, and the same two for ref_s and refclip_s when references were given: 0-dim float64 device
         tensors, views of one result buffer; with return_counts also '{name}_counts', int64 [8] (metrics.KENDALL_COUNTS).  One
-        concatenation per vector and one kernel call."""
+        concatenation per vector and one kernel call.
+        stats: a non-empty subset of ('kendall', 'spearman', 'pearson').  'spearman' / 'pearson' add '{name}_spearman' / '{name}_pearson'
+        for the same score names, from one `rank_correlation` call for all of them; without 'kendall' no Kendall call is issued and
+        there are no tau entries (return_counts then has nothing to return: a ValueError)."""
+        stats = tuple(stats)
+        if not stats or any(s not in STATS for s in stats) or len(set(stats)) != len(stats):
+            raise ValueError(f'HumanCorrelation: stats must be a non-empty subset of {STATS} without repeats, got {stats}')
+        if return_counts and 'kendall' not in stats:
+            raise ValueError(f"HumanCorrelation: return_counts returns the Kendall counts, and stats={stats} has no 'kendall'")
         if not 2 <= self._n <= KENDALL_MAX_ITEMS:
             raise ValueError(f'HumanCorrelation: {self._n} rated items stored since the last reset(), need 2 to {KENDALL_MAX_ITEMS}')
         names = SCORE_NAMES if self._with_refs else SCORE_NAMES[:1]
@@ -106,11 +121,18 @@ class HumanCorrelation:
         scores = torch.empty(len(names), self._n, dtype=torch.float32, device=dev)
         for c in range(len(names)):
             torch.cat(self._scores[c], out=scores[c])
-        res = kendall_tau(scores, human, return_counts=return_counts)
         out = {}
-        for c, name in enumerate(names):
-            out[f'{name}_tau_b'] = res['tau_b'][c]
-            out[f'{name}_tau_c'] = res['tau_c'][c]
-            if return_counts:
-                out[f'{name}_counts'] = res['counts'][c]
+        if 'kendall' in stats:
+            res = kendall_tau(scores, human, return_counts=return_counts)
+            for c, name in enumerate(names):
+                out[f'{name}_tau_b'] = res['tau_b'][c]
+                out[f'{name}_tau_c'] = res['tau_c'][c]
+                if return_counts:
+                    out[f'{name}_counts'] = res['counts'][c]
+        if 'spearman' in stats or 'pearson' in stats:
+            res = rank_correlation(scores, human)
+            for stat in ('spearman', 'pearson'):
+                if stat in stats:
+                    for c, name in enumerate(names):
+                        out[f'{name}_{stat}'] = res[stat][c]
         return out

@@ -6,7 +6,8 @@ logits matrix (dual_distill_model.py:204-224, distil_model.py:171-191), from the
 image, both directions, on `dclip_retrieval_recall`.
 
 `kendall_tau` is what a caption metric itself is judged by: Kendall tau-b / tau-c of its scores against human ratings, on
-`dclip_kendall_tau`.
+`dclip_kendall_tau`; `rank_correlation` is the other two coefficients such work reports, Spearman rho and Pearson r, on
+`dclip_rank_correlation`.
 
 `topk_search` asks the opposite question of the recall figures, which gallery rows are a query's best, on `dclip_topk_search`;
 `group_mean_rows` forms class embeddings from prompt ensembles on `dclip_group_mean_rows` (zeroshot.ZeroShotClassifier uses both)."""
@@ -150,6 +151,57 @@ def kendall_tau(scores, human, return_counts=False):
     res = {'tau_b': tau[:, 0] if many else tau[0, 0], 'tau_c': tau[:, 1] if many else tau[0, 1]}
     if return_counts:
         res['counts'] = counts if many else counts[0]
+    return res
+
+
+RANKCORR_SUMS = ('sxy', 'sxx', 'syy', 'nan')       # include/dclip.h: the int64 sums of the centred twice-ranks, and the NaN items
+
+
+def rank_correlation(scores, human, return_sums=False, return_ranks=False):
+    """Spearman rho and Pearson r of a metric's scores against human ratings, as scipy.stats.spearmanr (average ranks on ties) and
+    scipy.stats.pearsonr define them, on `dclip_rank_correlation`: rho comes from exact int64 sums of the twice-ranks R_i = 2 #{v_j < v_i}
+    + #{v_j == v_i} + 1, r from two passes in double with sums of a fixed shape, so the same call gives the same bits.
+    scores [n] or [C, n] (C <= 4 score vectors, all correlated with the same ratings in one call; the ratings are ranked once), human [n]:
+    device tensors of any float or integer dtype, taken to f32 (equal inputs give equal f32 values, so ties survive).  The limits on n
+    and C are those of `kendall_tau`.
+    -> {'spearman', 'pearson'}: float64 device tensors of shape [] or [C], views of one result buffer; with return_sums also 'sums',
+    int64 [4] or [C, 4] in the order of RANKCORR_SUMS; with return_ranks also 'ranks', int32 twice-ranks [n] or [C, n], and 'human_ranks'
+    [n].  A NaN in a score vector makes that vector's coefficients NaN, a NaN in human all of them; a constant vector gives NaN for
+    both; +-inf is a legal value for rho and makes r NaN.
+    Out of scope: p-values and confidence intervals, weighted variants, gathering across ranks (pass gathered vectors), n > 262 144,
+    and sharing one pair walk with the Kendall kernel.  Every ValueError is raised before any launch; nothing waits for the device."""
+    if not torch.is_tensor(scores) or not torch.is_tensor(human) or scores.dim() not in (1, 2) or human.dim() != 1:
+        raise ValueError(f'rank_correlation: need scores [n] or [C, n] and human [n], got {tuple(getattr(scores, "shape", ()))} and '
+                         f'{tuple(getattr(human, "shape", ()))}')
+    many = scores.dim() == 2
+    C, n = (scores.shape[0], scores.shape[1]) if many else (1, scores.shape[0])
+    if human.shape[0] != n:
+        raise ValueError(f'rank_correlation: {n} scores per vector against {human.shape[0]} ratings')
+    if not 2 <= n <= KENDALL_MAX_ITEMS:
+        raise ValueError(f'rank_correlation: need 2 <= n <= {KENDALL_MAX_ITEMS} items (n={n})')
+    if not 1 <= C <= KENDALL_MAX_VECTORS:
+        raise ValueError(f'rank_correlation: need 1 <= C <= {KENDALL_MAX_VECTORS} score vectors per call (C={C})')
+    if not scores.is_cuda or not human.is_cuda:
+        raise ValueError('rank_correlation: scores and human are device tensors (distillclip_amd has no CPU path)')
+    if scores.device != human.device:
+        raise ValueError(f'rank_correlation: scores on {scores.device}, human on {human.device}')
+    dev = scores.device
+    x = scores.detach().float().contiguous()
+    y = human.detach().float().contiguous()
+    corr = torch.empty(C, 2, dtype=torch.float64, device=dev)
+    sums = torch.empty(C, 4, dtype=torch.int64, device=dev) if return_sums else None
+    ranks = torch.empty(C + 1, n, dtype=torch.int32, device=dev) if return_ranks else None
+    ws = torch.empty(max(lib().dclip_rank_correlation_workspace(n, C), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib().dclip_rank_correlation(x.data_ptr(), n, C, y.data_ptr(), n, corr.data_ptr(), sums.data_ptr() if return_sums else None,
+                                     ranks.data_ptr() if return_ranks else None, ws.data_ptr(), ws.numel(),
+                                     torch.cuda.current_stream().cuda_stream)
+    res = {'spearman': corr[:, 0] if many else corr[0, 0], 'pearson': corr[:, 1] if many else corr[0, 1]}
+    if return_sums:
+        res['sums'] = sums if many else sums[0]
+    if return_ranks:
+        res['ranks'] = ranks[:C] if many else ranks[0]
+        res['human_ranks'] = ranks[C]
     return res
 
 

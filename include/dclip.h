@@ -636,6 +636,48 @@ size_t dclip_kendall_tau_workspace(int64_t n, int64_t C);
 int dclip_kendall_tau(const float* scores, int64_t ld, int64_t C, const float* human, int64_t n, double* out_tau, int64_t* out_counts,
                       void* workspace, size_t ws_bytes, void* stream);
 /*
+ * Spearman rho and Pearson r of C score vectors against one vector of human ratings, in one call (rankcorr.hip): the two coefficients
+ * caption-metric work reports instead of, or next to, Kendall tau.  The reference ships no such evaluation.
+ * Inputs
+ *   As dclip_kendall_tau: scores is C vectors of n f32, vector c at scores + c ld, ld >= n; human is n f32 ratings.  Comparisons are IEEE
+ *   f32 comparisons: -0 == +0, +-inf order normally, a NaN compares false to everything.
+ * Twice-ranks
+ *   For a vector v and item i: L_i = #{j : v_j < v_i}, Q_i = #{j : v_j == v_i} (i itself included), R_i = 2 L_i + Q_i + 1.  R_i is twice
+ *   the average rank of scipy.stats.rankdata(v, 'average'), an exact integer; without a NaN, sum_i R_i = n (n + 1).  (A NaN item has
+ *   L = Q = 0, so R = 1.)  out_ranks, when given, is device int32 [C + 1][n]: the C score vectors, then the ratings, which are ranked
+ *   once and not once per column.
+ * Spearman rho
+ *   cx_i = Rx_i - (n + 1), cy_i = Ry_i - (n + 1); Sxy = sum cx_i cy_i, Sxx = sum cx_i^2, Syy = sum cy_i^2, all in int64.  Range:
+ *   |c_i| <= n <= 2^18 (and |c_i| < 2^18 without a NaN), so every product is at most 2^36 and every sum of n <= 2^18 of them at most
+ *   2^54: int64 never overflows and the three sums are exact.  rho = (double)Sxy / (sqrt((double)Sxx) sqrt((double)Syy)), formed once,
+ *   by one thread, in double, and clipped to [-1, 1]; it is evaluated with one root, Sxy / sqrt(Sxx Syy), which makes it exactly 1 for
+ *   x = y and exactly -1 for reversed ranks and differs from the two-root form in the last bits only.  No floating-point sum occurs
+ *   before that line: the same call gives the same bits.  This is scipy.stats.spearmanr (average ranks on ties).
+ *   out_sums, when given, is device int64 [C][4]: Sxy, Sxx, Syy, and the number of items i for which x_i or y_i is a NaN.
+ * Pearson r
+ *   The f32 values are taken to double, which is exact.  Two passes: the means xm = (sum x_i) / n and ym; then sxy = sum (x_i - xm)
+ *   (y_i - ym), sxx = sum (x_i - xm)^2, syy = sum (y_i - ym)^2 in double, r = sxy / (sqrt(sxx) sqrt(syy)) (one root, as above), clipped
+ *   to [-1, 1].  Every sum has a fixed shape that depends on n alone: per-lane partials in item order, then the wave, then the
+ *   workgroup, then one finalizing workgroup.  No atomics: the same call gives the same bits.  Error bound: DESIGN.md section 7.0.
+ * Results
+ *   out_corr is device f64 [C][2]: rho, r.
+ * Degenerate inputs, all decided on the device with nothing waiting
+ *   A NaN in a score vector makes that vector's rho and r NaN and leaves the other columns bit for bit as they are without it; a NaN in
+ *   human makes every column NaN.  A constant vector (Sxx == 0 or Syy == 0; sxx == 0 or syy == 0) gives rho = r = NaN.  +-inf in a
+ *   vector is a legal value for rho (it ranks first or last) and makes r NaN, as SciPy's float arithmetic does.
+ * Determinism
+ *   Integer counters and fixed-shape sums, no atomics.  No n makes the kernels read or write outside their buffers.
+ * Limits, refused on the host with a message (DCLIP_EINVAL, nothing launched, nothing written)
+ *   2 <= n <= 262144.  1 <= C <= 4.  ld >= n.  Null scores, human, out_corr or workspace (out_sums and out_ranks may be null).  scores,
+ *   human and out_ranks 4-byte, out_corr and out_sums 8-byte, workspace 16-byte aligned.  A workspace smaller than
+ *   dclip_rank_correlation_workspace(n, C), which is 0 for a refused shape.
+ * Out of scope: p-values and confidence intervals, weighted variants, n > 262144, sharing one pair walk with dclip_kendall_tau.
+ * Added without a version bump: no existing signature changed.
+ */
+size_t dclip_rank_correlation_workspace(int64_t n, int64_t C);
+int dclip_rank_correlation(const float* scores, int64_t ld, int64_t C, const float* human, int64_t n, double* out_corr, int64_t* out_sums,
+                           int32_t* out_ranks, void* workspace, size_t ws_bytes, void* stream);
+/*
  * Row block of the same loss for data-parallel global negatives (Collective 2): the four inputs are the GATHERED
  * [B, E] embeddings of all ranks, this call owns rows [row0, row0 + rows) — its own samples — against all B columns.
  * d_s_img / d_s_txt: [rows, E] gradients of the owned samples (d global loss / d embedding).  out_scalars: this block's share of
