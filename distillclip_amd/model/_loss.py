@@ -3,6 +3,10 @@
 Constructor arguments, percent / scale bookkeeping, error behaviour, `get_control_output()` and the returned
 `(loss, dict)` (dict holds the *scaled* terms, tower terms prefixed `image_` / `text_`) follow the reference.
 One `dclip_distill_loss` call computes every enabled term and d loss / d student embeddings; backward just scales them.
+
+Two names beyond the reference complete the CLIP-KD recipe (Yang et al., CVPR 2024) next to `soft_label`: `out_mse` (feature distillation:
+the MSE of the `last_representation`s, a tower term on `dclip_feature_mse`) and `icl` (interactive contrastive learning: student rows
+against the other modality's TEACHER rows, a cross-modal term on `dclip_interactive_loss`).
 """
 from typing import Dict, List
 
@@ -12,10 +16,12 @@ from torch import nn
 from .component.output import ControlOutput
 from .. import ops
 
-IMAGE_TEXT_LOSS = ['hard_label', 'soft_label', 'logits_mse', 'fine_grain', 'cos_diff']     # reference _loss.py:14
+IMAGE_TEXT_LOSS = ['hard_label', 'soft_label', 'logits_mse', 'fine_grain', 'cos_diff', 'icl']     # reference _loss.py:14, and icl
 _TOWER_FUSED = ('out_l1', 'out_cos', 'out_kl', 'out_ce')
 _CROSS_FUSED = ('cos_diff', 'hard_label', 'soft_label', 'logits_mse')
-_FEATURE = ('hidden_rep_mse', 'embedding_mse', 'attention_score_mse', 'attention_probs_mse')
+_FEATURE = ('hidden_rep_mse', 'embedding_mse', 'attention_score_mse', 'attention_probs_mse', 'out_mse')
+_CROSS_OWN = ('icl',)                             # cross-modal terms with a kernel call of their own
+_ICL_MAX_B = 4096                                 # include/dclip.h: dclip_interactive_loss
 _KNOWN_UNSUPPORTED = ('attention_probs_kl', 'last_value_map_kl', 'vit_kd', 'fine_grain', 'smd')
 _SLOT_TOWER = {'out_l1': 1, 'out_cos': 2, 'out_kl': 3, 'out_ce': 4}
 _SLOT_CROSS = {'cos_diff': 9, 'hard_label': 10, 'soft_label': 11, 'logits_mse': 12}
@@ -96,6 +102,26 @@ class _FeatureMSEFn(torch.autograd.Function):
         return ds * g, None
 
 
+class _InteractiveLossFn(torch.autograd.Function):
+    """weight * icl and the four scalars of dclip_interactive_loss; the kernel's gradients of the two student embeddings are kept for
+    the backward, the teacher gets none"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, s_img, s_txt, t_img, t_txt, temperature, weight):
+        prep = lambda x: x.detach().float().contiguous()
+        out, d_i, d_t = ops.interactive_loss(prep(s_img), prep(t_img), prep(s_txt), prep(t_txt), temperature, weight)
+        ctx.save_for_backward(d_i, d_t)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, g_loss, _g_out):
+        d_i, d_t = ctx.saved_tensors
+        return d_i * g_loss, d_t * g_loss, None, None, None, None
+
+
 def _map_mse(s, t):
     """_FeatureMSEFn on one pair of head-mean maps [B, 1, N, N]: dclip_feature_mse reads 4 elements at a time, so an element count that is
     not a multiple of 4 (odd N at odd B) is zero-padded and the mean rescaled to the true count"""
@@ -140,7 +166,7 @@ class LossCalculator(nn.Module):
             if n in _KNOWN_UNSUPPORTED:
                 raise NotImplementedError(f"loss '{n}' is registered by the reference but used by no shipped config; it is "
                                           f'outside the HIP hot path (SURVEY.md §2.1)')
-            if n not in _TOWER_FUSED and n not in _CROSS_FUSED and n not in _FEATURE:
+            if n not in _TOWER_FUSED and n not in _CROSS_FUSED and n not in _FEATURE and n not in _CROSS_OWN:
                 raise ValueError('Invalid Loss Type!')
 
     def get_control_output(self):
@@ -166,6 +192,9 @@ class LossCalculator(nn.Module):
                 sm, tm = (stu.attention_scores, tea.attention_scores) if n == 'attention_score_mse' else (stu.attention_probs, tea.attention_probs)
                 val = sum(_map_mse(s, t) for s, t in zip(sm, tm))
                 val = val / max(getattr(sm, 'executions', len(sm)), 1)
+            elif n == 'out_mse':
+                # feature distillation of CLIP-KD: the plain MSE of the output embeddings
+                val = _map_mse(stu.last_representation, tea.last_representation)
             else:
                 continue
             res[n] = val * self.loss_scale[n]
@@ -183,9 +212,16 @@ class LossCalculator(nn.Module):
         for n in self.loss_name:
             if n in _TOWER_FUSED or (two_tower and n in _CROSS_FUSED):
                 w[n] = self.loss_scale[n] * self.percent[n]
-        if 'out_kl' in w or 'soft_label' in w:
+        if 'out_kl' in w or 'soft_label' in w or (two_tower and 'icl' in self.loss_name):
             assert self.temperature, 'You should give the temperature for the kl loss'     # reference :133,:166
         return w
+
+    def _interactive(self, stu_out, tea_out):
+        """-> (loss_scale * percent * icl with its autograd, loss_scale * icl) by one dclip_interactive_loss call"""
+        val, out = _InteractiveLossFn.apply(stu_out.visual_output.last_representation, stu_out.text_output.last_representation,
+                                            tea_out.visual_output.last_representation, tea_out.text_output.last_representation,
+                                            float(self.temperature), float(self.loss_scale['icl'] * self.percent['icl']))
+        return val, out[1] * self.loss_scale['icl']
 
     def _scale_vector(self, device):
         """loss_scale of each raw term in the kernel's 16-slot output order (cached on the device; rebuilt when the scales change)"""
@@ -201,6 +237,13 @@ class LossCalculator(nn.Module):
         return self._scale_cache[1]
 
     def cal_tow_tower_loss(self, stu_out, tea_out):
+        icl = 'icl' in self.loss_name
+        if icl and self.global_negatives:
+            # decided from the configuration alone, the same on every rank, before the first collective
+            raise ValueError("loss 'icl' contrasts against the local teacher rows only: it is not offered with global_negatives=True")
+        if icl and stu_out.visual_output.last_representation.shape[0] > _ICL_MAX_B:
+            raise ValueError(f"loss 'icl': batch {stu_out.visual_output.last_representation.shape[0]} exceeds the kernel's "
+                             f'{_ICL_MAX_B} rows (include/dclip.h: dclip_interactive_loss)')
         loss, scal = _FusedLossFn.apply(stu_out.visual_output.last_representation, stu_out.text_output.last_representation,
                                         tea_out.visual_output.last_representation, tea_out.text_output.last_representation,
                                         self._weights(True), self.temperature, self.global_negatives)
@@ -218,6 +261,9 @@ class LossCalculator(nn.Module):
         for n in self.loss_name:
             if n in _CROSS_FUSED:
                 res[n] = scaled[_SLOT_CROSS[n]]
+        if icl:
+            val, res['icl'] = self._interactive(stu_out, tea_out)
+            loss = loss + val
         return loss, res
 
     def cal_one_tower_loss(self, stu_out, tea_out):

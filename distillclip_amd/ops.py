@@ -214,6 +214,26 @@ def distill_loss(s_img, t_img, s_txt=None, t_txt=None, *, weights, temperature=N
     return out, d_i, d_t
 
 
+def interactive_loss(s_img, t_img, s_txt, t_txt, temperature, weight=1.0):
+    """Interactive contrastive distillation fwd+bwd (include/dclip.h: dclip_interactive_loss): student image rows against teacher text
+    rows and student text rows against teacher image rows.  f32 [B, E] contiguous device tensors.
+    -> (out[4] = weight * icl, icl, L_i2t, L_t2i ; d_s_img, d_s_txt = weight * d icl / d student rows)"""
+    _chk(s_img, t_img, s_txt, t_txt)
+    for t in (s_img, t_img, s_txt, t_txt):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != s_img.shape or not t.is_contiguous():
+            raise ValueError(f'interactive_loss: need four contiguous f32 [B, E] tensors of one shape, got {tuple(t.shape)} {t.dtype}')
+    B, E = s_img.shape
+    ws_bytes = lib().dclip_interactive_loss_workspace(B, E)
+    if ws_bytes == 0:
+        raise ValueError(f'interactive_loss: need 1 <= B <= 4096, E % 16 == 0, 16 <= E <= 1024, got B={B} E={E}')
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s_img.device)
+    out = torch.empty(4, dtype=torch.float32, device=s_img.device)
+    d_i, d_t = torch.empty_like(s_img), torch.empty_like(s_txt)
+    lib().dclip_interactive_loss(_p(s_img), _p(t_img), _p(s_txt), _p(t_txt), B, E, float(temperature), float(weight), _p(out), _p(d_i),
+                                 _p(d_t), _p(ws), ws_bytes, _stream())
+    return out, d_i, d_t
+
+
 def attn_fused_fwd(qkv, B, N, H, hd, causal=False):
     """ctx = softmax(q k^T / sqrt(hd) (+ causal mask)) v for plain multi-head attention; qkv: [B*N, 3*H*hd] bf16."""
     _chk(qkv)

@@ -700,6 +700,35 @@ int dclip_distill_loss_rows(const float* s_img, const float* t_img, const float*
 /* feature MSE (hidden_rep_mse / embedding_mse: hidden_mse.py:9-17, embed_mse.py:9-10):
  *   loss_acc[0] += coef * mean((s - t)^2) ; ds_acc (nullable) += coef * 2 (s - t) / n */
 int dclip_feature_mse(const float* s, const float* t, int64_t n, float coef, float* loss_acc, float* ds_acc, void* stream);
+/*
+ * Interactive contrastive distillation, forward + backward (the ICL term of CLIP-KD, Yang et al., CVPR 2024): the student's image rows
+ * are contrasted against the TEACHER's text rows and the student's text rows against the teacher's image rows.
+ *   a, b = rows of s_img, s_txt ; p, q = rows of t_img, t_txt ; x^ = x / |x|, no epsilon (clip_model.py:37-44, as dclip_distill_loss)
+ *       A_ij = a^_i . q^_j / tau                 C_ij = b^_i . p^_j / tau
+ *       L_i2t = mean_i (lse_j A_ij - A_ii)       L_t2i = mean_i (lse_j C_ij - C_ii)       icl = (L_i2t + L_t2i) / 2
+ *   The anchors are the student rows only (row softmaxes, no column direction); the teacher receives no gradient:
+ *       P_ij = exp(A_ij - lse_j A_ij) ;  G_i = (sum_j P_ij q^_j - q^_i) / (2 B tau) ;  d a_i = (G_i - a^_i (a^_i . G_i)) / |a_i|
+ *   and the same of b with C and p^.  lse is the natural-log log-sum-exp with the row's true maximum.
+ *   s_*, t_*   : DEVICE, f32 [B, E], 16-byte aligned.  Limits: 1 <= B <= 4096, E % 16 == 0, 16 <= E <= 1024, tau finite and > 0,
+ *                weight finite.
+ *   out        : DEVICE, 4 f32, 16-byte aligned: weight * icl, icl, L_i2t, L_t2i.
+ *   d_s_img, d_s_txt : DEVICE, f32 [B, E], 16-byte aligned, OVERWRITTEN with weight * d icl / d row.
+ *   workspace  : DEVICE, 256-byte aligned, ws_bytes >= dclip_interactive_loss_workspace(B, E) (0 for a refused shape); contents need
+ *                not survive between calls.  The [B, B] logits never reach HBM.
+ *   Four launches on `stream`.  No atomics, no allocation, no synchronisation, no global state: the same call gives the same bits.
+ *   Zero and non-finite rows follow dclip_distill_loss: there is no epsilon, so a zero row normalises to 0 * (1 / 0) = NaN in every
+ *   element, and so does a row that holds a NaN or an infinity.  Such a STUDENT row i makes row i of its own gradient NaN in every
+ *   element and its direction's L, icl and out[0] NaN; the other rows of that gradient and the other direction stay finite.  Such a
+ *   TEACHER row makes every logit of its column NaN: every element of the gradient that is contrasted against it (d_s_img for a row of
+ *   t_txt, d_s_txt for a row of t_img), that direction's L, icl and out[0] become NaN; the other gradient and the other L stay finite.
+ *   Refused on the host with DCLIP_EINVAL, nothing launched, nothing written: B or E outside the limits, tau not finite or <= 0, a
+ *   non-finite weight, any null pointer, a misaligned pointer, a workspace smaller than the query.
+ *   Added without a version bump: no existing signature changed.
+ */
+size_t dclip_interactive_loss_workspace(int64_t B, int64_t E);
+int dclip_interactive_loss(const float* s_img, const float* t_img, const float* s_txt, const float* t_txt, int64_t B, int64_t E,
+                           float tau, float weight, float* out, float* d_s_img, float* d_s_txt, void* workspace, size_t ws_bytes,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Tower-level runtime: one call issues the whole launch sequence of an encoder tower on `stream`.
