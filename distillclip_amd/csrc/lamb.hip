@@ -198,33 +198,24 @@ extern "C" int dclip_lamb_table(float* p, float* g, float* m, float* v, float* e
                                 float beta2, float eps, int64_t step, int zero_grad, float ema_weight, const float* gscale, const float* record,
                                 float trust_clip, int always_adapt, void* workspace, size_t ws_bytes, float* stats, void* stream) {
     const char* what = "dclip_lamb_table";
-    DCLIP_REQUIRE(p && g && m && v && ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0),
-                  "%s: bad argument (p, g, m, v non-NULL, all bases 16-byte aligned)", what);
-    DCLIP_REQUIRE(table && ((uintptr_t)table & 7) == 0 && count >= 1, "%s: bad argument (a device table on an 8-byte boundary, count >= 1)", what);
-    DCLIP_REQUIRE(tiles >= count && tiles <= INT32_MAX, "%s: %lld tiles for %d ranges: every range has at least one, a launch at most 2^31 - 1", what,
-                  (long long)tiles, (int)count);
-    DCLIP_REQUIRE(!(gscale && record), "%s: gscale (a clipped step) and record (a scaler-driven step) exclude each other", what);
-    DCLIP_REQUIRE(!e || (ema_weight >= 0.f && ema_weight <= 1.f), "%s: ema_weight = 1 - decay must lie in [0, 1] (got %g)", what, (double)ema_weight);
-    DCLIP_REQUIRE(record ? ((uintptr_t)record & 15) == 0 : step >= 1, "%s: bad argument (a 16-byte aligned record of dclip_amp_prepare, or step >= 1)", what);
+    const int rc = adamw_table_operands(what, p, g, m, v, e, table, count, tiles, step, ema_weight, gscale, record);
+    if (rc != DCLIP_OK) return rc;
     DCLIP_REQUIRE(trust_clip == trust_clip, "%s: trust_clip is NaN (a negative value switches the clip off)", what);
     DCLIP_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= dclip_lamb_workspace_bytes(count, tiles),
                   "%s: the workspace needs %zu bytes on a 16-byte boundary (dclip_lamb_workspace_bytes), got %zu", what, dclip_lamb_workspace_bytes(count, tiles), ws_bytes);
     DCLIP_REQUIRE(stats && ((uintptr_t)stats & 15) == 0, "%s: stats is %d x 4 f32 on a 16-byte boundary", what, (int)count);
-    const int mode = record ? ADAMW_AMP : gscale ? ADAMW_SCALED : ADAMW_PLAIN;
-    const float bc1 = record ? 0.f : 1.f - powf(beta1, (float)step);
-    const float bc2 = record ? 0.f : sqrtf(1.f - powf(beta2, (float)step));
-    const float* dev = record ? record : gscale;
+    const AdamwControl c = adamw_control(beta1, beta2, step, gscale, record);
     const dclip_adamw_range* tab = (const dclip_adamw_range*)table;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (const float4*)p, (float4*)g, (float4*)m, (float4*)v, tab, (int)count, beta1,
-                       beta2, eps, bc1, bc2, zero_grad, mode, dev, (LambTile*)workspace);
-    hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)count), dim3(256), 0, st, tab, (int)count, tiles, (const LambTile*)workspace, trust_clip, always_adapt, mode,
-                       dev, (float4*)stats);
+                       beta2, eps, c.bc1, c.bc2_sqrt, zero_grad, c.mode, c.dev, (LambTile*)workspace);
+    hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)count), dim3(256), 0, st, tab, (int)count, tiles, (const LambTile*)workspace, trust_clip, always_adapt,
+                       c.mode, c.dev, (float4*)stats);
     if (!e || ema_weight == 0.f)                             // no average, or one that stands still: e neither read nor written
         hipLaunchKernelGGL(lamb_apply_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, (float4*)p, (const float4*)m, (const float4*)v, (float4*)nullptr, tab,
-                           (int)count, lr, eps, bc1, bc2, 0.f, mode, dev, (const float4*)stats);
+                           (int)count, lr, eps, c.bc1, c.bc2_sqrt, 0.f, c.mode, c.dev, (const float4*)stats);
     else
         hipLaunchKernelGGL(lamb_apply_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, (float4*)p, (const float4*)m, (const float4*)v, (float4*)e, tab,
-                           (int)count, lr, eps, bc1, bc2, ema_weight, mode, dev, (const float4*)stats);
+                           (int)count, lr, eps, c.bc1, c.bc2_sqrt, ema_weight, c.mode, c.dev, (const float4*)stats);
     return dclip_check_launch(what);
 }

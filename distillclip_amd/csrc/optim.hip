@@ -4,8 +4,12 @@
 // Under a loss scaler (dclip_amp_prepare, dclip_adamw_multi_amp): the same step driven by a device record that also carries the
 // scaler's 1 / scale, its overflow flag and the bias corrections of the steps that were not skipped.  An exponential moving average of the
 // parameters kept by the same kernel (dclip_adamw_multi_ema), and the exchange of parameters and average in place (dclip_swap_multi).
+// The table-driven form of all of these for parameter groups (dclip_adamw_table_bytes, dclip_adamw_table_fill, dclip_adamw_table): ranges
+// with their own lr_scale and weight_decay as records in device memory, one launch per flat buffer.  Host side: every dclip_adamw_multi*
+// entry and dclip_adamw are argument checks and one call of adamw_multi_launch; the step control (mode, bias corrections, device
+// pointer) and the table entries' operand checks are optim_elem.h's, shared with lamb.hip.
 #include "common.h"
-#include "optim_elem.h"   // adamw_elem, ema_elem, AdamwMode, the table's tile constants and lookup: shared with lamb.hip
+#include "optim_elem.h"   // adamw_elem, ema_elem, AdamwMode, the table's tile constants and lookup, adamw_control, adamw_table_operands
 
 #include <math.h>
 
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
     }
 }
 
-// beta^t for the host's powf(beta, (float)t) (adamw_multi_launch): square-and-multiply in double (a relative error below
+// beta^t for the host's powf(beta, (float)t) (adamw_control): square-and-multiply in double (a relative error below
 // 2 * 24 * 2^-53 for t < 2^24, far inside the half-ulp of the f32 it is rounded to), i.e. the correctly rounded f32.  The host's powf
 // is within 0.52 ulp of that: the bias corrections agree bit for bit except for a rare last bit (DESIGN.md section 7.0 counts them).
 __device__ __forceinline__ float powf_int(float beta, int64_t t) {
@@ -292,11 +296,11 @@ __global__ __launch_bounds__(256) void adamw4_table_kernel(float4* __restrict__ 
 }
 
 template <bool EMA>
-void adamw_table_launch(int mode, unsigned tiles, hipStream_t stream, float* p, float* g, float* m, float* v, float* e, const void* table, int count, float lr,
-                        float b1, float b2, float eps, float bc1, float bc2, int zero_grad, float w, const float* dev) {
-    auto kernel = mode == ADAMW_PLAIN ? adamw4_table_kernel<ADAMW_PLAIN, EMA> : mode == ADAMW_SCALED ? adamw4_table_kernel<ADAMW_SCALED, EMA> : adamw4_table_kernel<ADAMW_AMP, EMA>;
+void adamw_table_launch(const AdamwControl& c, unsigned tiles, hipStream_t stream, float* p, float* g, float* m, float* v, float* e, const void* table, int count,
+                        float lr, float b1, float b2, float eps, int zero_grad, float w) {
+    auto kernel = c.mode == ADAMW_PLAIN ? adamw4_table_kernel<ADAMW_PLAIN, EMA> : c.mode == ADAMW_SCALED ? adamw4_table_kernel<ADAMW_SCALED, EMA> : adamw4_table_kernel<ADAMW_AMP, EMA>;
     hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), 0, stream, (float4*)p, (float4*)g, (float4*)m, (float4*)v, (float4*)e, (const dclip_adamw_range*)table, count,
-                       lr, b1, b2, eps, bc1, bc2, zero_grad, w, dev);
+                       lr, b1, b2, eps, c.bc1, c.bc2_sqrt, zero_grad, w, c.dev);
 }
 
 // Pairs of ranges exchanged word for word (include/dclip.h: dclip_swap_multi).  128-bit integer loads and stores and nothing between
@@ -337,26 +341,31 @@ int adamw_ranges(const char* what, float* const* p, float* const* g, float* cons
     return DCLIP_OK;
 }
 
-int adamw_multi_launch(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, const float* gscale, void* stream) {
-    DCLIP_REQUIRE(step >= 1, "%s: bad argument (step >= 1)", what);
-    AdamwRanges r;
+// the (MODE, EMA) instantiation of adamw4_multi_kernel that `c` and the ranges' type ask for, launched
+template <bool EMA, class R>
+void adamw_multi_go(const AdamwControl& c, dim3 grid, hipStream_t stream, const R& r, float lr, float b1, float b2, float eps, float wd, int zero_grad) {
+    auto kernel = c.mode == ADAMW_PLAIN ? adamw4_multi_kernel<ADAMW_PLAIN, EMA> : c.mode == ADAMW_SCALED ? adamw4_multi_kernel<ADAMW_SCALED, EMA> : adamw4_multi_kernel<ADAMW_AMP, EMA>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, r, lr, b1, b2, eps, wd, c.bc1, c.bc2_sqrt, zero_grad, c.dev);
+}
+
+// THE launch of adamw4_multi_kernel, behind every dclip_adamw_multi* entry and dclip_adamw: the ranges checked, and with `e` the averages;
+// ema_weight == 0 (always so without e): the average stands still, the step alone, e neither read nor written.
+int adamw_multi_launch(const char* what, float* const* p, float* const* g, float* const* m, float* const* v, float* const* e, const int64_t* n, int32_t count,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, const AdamwControl& c, int zero_grad, float ema_weight, void* stream) {
+    AdamwEmaRanges r;
     dim3 grid;
     const int rc = adamw_ranges(what, p, g, m, v, n, count, r, grid);
     if (rc != DCLIP_OK) return rc;
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(gscale ? adamw4_multi_kernel<ADAMW_SCALED> : adamw4_multi_kernel<ADAMW_PLAIN>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps,
-                       weight_decay, bc1, bc2, zero_grad, gscale);
+    for (int k = 0; e && k < count; ++k) {
+        DCLIP_REQUIRE(e[k] && ((uintptr_t)e[k] & 15) == 0, "%s: e of range %d must be non-NULL and 16-byte aligned", what, k);
+        r.e[k] = (float4*)e[k];
+    }
+    r.w = ema_weight;
+    if (ema_weight == 0.f)
+        adamw_multi_go<false>(c, grid, (hipStream_t)stream, (const AdamwRanges&)r, lr, beta1, beta2, eps, weight_decay, zero_grad);
+    else
+        adamw_multi_go<true>(c, grid, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, zero_grad);
     return dclip_check_launch(what);
-}
-
-// dclip_adamw_multi_ema's launch: the instantiation of `mode`, with the average (R = AdamwEmaRanges) or without (R = AdamwRanges)
-template <bool EMA, class R>
-void adamw_ema_launch(int mode, dim3 grid, hipStream_t stream, const R& r, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, int zero_grad,
-                      const float* dev) {
-    auto kernel = mode == ADAMW_PLAIN ? adamw4_multi_kernel<ADAMW_PLAIN, EMA> : mode == ADAMW_SCALED ? adamw4_multi_kernel<ADAMW_SCALED, EMA> : adamw4_multi_kernel<ADAMW_AMP, EMA>;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, r, lr, b1, b2, eps, wd, bc1, bc2, zero_grad, dev);
 }
 
 }  // namespace
@@ -386,13 +395,17 @@ extern "C" int dclip_clip_coef(const float* partials, int64_t n_partials, const 
 
 extern "C" int dclip_adamw_multi(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
                                  float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad, void* stream) {
-    return adamw_multi_launch("dclip_adamw_multi", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, nullptr, stream);
+    DCLIP_REQUIRE(step >= 1, "dclip_adamw_multi: bad argument (step >= 1)");
+    return adamw_multi_launch("dclip_adamw_multi", p, g, m, v, nullptr, n, count, lr, beta1, beta2, eps, weight_decay, adamw_control(beta1, beta2, step, nullptr, nullptr),
+                              zero_grad, 0.f, stream);
 }
 
 extern "C" int dclip_adamw_multi_scaled(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count,
                                         float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int zero_grad,
                                         const float* gscale, void* stream) {
-    return adamw_multi_launch("dclip_adamw_multi_scaled", p, g, m, v, n, count, lr, beta1, beta2, eps, weight_decay, step, zero_grad, gscale, stream);
+    DCLIP_REQUIRE(step >= 1, "dclip_adamw_multi_scaled: bad argument (step >= 1)");
+    return adamw_multi_launch("dclip_adamw_multi_scaled", p, g, m, v, nullptr, n, count, lr, beta1, beta2, eps, weight_decay,
+                              adamw_control(beta1, beta2, step, gscale, nullptr), zero_grad, 0.f, stream);
 }
 
 extern "C" int dclip_amp_prepare(const float* found_inf, const float* grad_scale, const float* partials, int64_t n_partials, const float* extra_sumsq,
@@ -408,13 +421,8 @@ extern "C" int dclip_amp_prepare(const float* found_inf, const float* grad_scale
 extern "C" int dclip_adamw_multi_amp(float* const* p, float* const* g, float* const* m, float* const* v, const int64_t* n, int32_t count, float lr,
                                      float beta1, float beta2, float eps, float weight_decay, int zero_grad, const float* record, void* stream) {
     DCLIP_REQUIRE(record && ((uintptr_t)record & 15) == 0, "dclip_adamw_multi_amp: bad argument (a 16-byte aligned record of dclip_amp_prepare)");
-    AdamwRanges r;
-    dim3 grid;
-    const int rc = adamw_ranges("dclip_adamw_multi_amp", p, g, m, v, n, count, r, grid);
-    if (rc != DCLIP_OK) return rc;
-    hipLaunchKernelGGL(adamw4_multi_kernel<ADAMW_AMP>, grid, dim3(256), 0, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f,
-                       zero_grad, record);
-    return dclip_check_launch("dclip_adamw_multi_amp");
+    return adamw_multi_launch("dclip_adamw_multi_amp", p, g, m, v, nullptr, n, count, lr, beta1, beta2, eps, weight_decay, adamw_control(beta1, beta2, 0, nullptr, record),
+                              zero_grad, 0.f, stream);
 }
 
 extern "C" int dclip_adamw_multi_ema(float* const* p, float* const* g, float* const* m, float* const* v, float* const* e, const int64_t* n, int32_t count,
@@ -425,24 +433,8 @@ extern "C" int dclip_adamw_multi_ema(float* const* p, float* const* g, float* co
     DCLIP_REQUIRE(!(gscale && record), "%s: gscale (a clipped step) and record (a scaler-driven step) exclude each other", what);
     DCLIP_REQUIRE(ema_weight >= 0.f && ema_weight <= 1.f, "%s: ema_weight = 1 - decay must lie in [0, 1] (got %g)", what, (double)ema_weight);   // (a NaN fails both)
     DCLIP_REQUIRE(record ? ((uintptr_t)record & 15) == 0 : step >= 1, "%s: bad argument (a 16-byte aligned record of dclip_amp_prepare, or step >= 1)", what);
-    AdamwEmaRanges r;
-    dim3 grid;
-    const int rc = adamw_ranges(what, p, g, m, v, n, count, r, grid);
-    if (rc != DCLIP_OK) return rc;
-    for (int k = 0; k < count; ++k) {
-        DCLIP_REQUIRE(e[k] && ((uintptr_t)e[k] & 15) == 0, "%s: e of range %d must be non-NULL and 16-byte aligned", what, k);
-        r.e[k] = (float4*)e[k];
-    }
-    r.w = ema_weight;
-    const int mode = record ? ADAMW_AMP : gscale ? ADAMW_SCALED : ADAMW_PLAIN;
-    const float bc1 = record ? 0.f : 1.f - powf(beta1, (float)step);
-    const float bc2 = record ? 0.f : sqrtf(1.f - powf(beta2, (float)step));
-    const float* dev = record ? record : gscale;
-    if (ema_weight == 0.f)                                   // the average stands still: the step alone, e neither read nor written
-        adamw_ema_launch<false>(mode, grid, (hipStream_t)stream, (const AdamwRanges&)r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad, dev);
-    else
-        adamw_ema_launch<true>(mode, grid, (hipStream_t)stream, r, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad, dev);
-    return dclip_check_launch(what);
+    return adamw_multi_launch(what, p, g, m, v, e, n, count, lr, beta1, beta2, eps, weight_decay, adamw_control(beta1, beta2, step, gscale, record), zero_grad,
+                              ema_weight, stream);
 }
 
 extern "C" size_t dclip_adamw_table_bytes(int32_t count) { return count < 1 ? 0 : ((size_t)count + 1) * sizeof(dclip_adamw_range); }
@@ -481,22 +473,13 @@ extern "C" int dclip_adamw_table(float* p, float* g, float* m, float* v, float* 
                                  float beta2, float eps, int64_t step, int zero_grad, float ema_weight, const float* gscale, const float* record,
                                  void* stream) {
     const char* what = "dclip_adamw_table";
-    DCLIP_REQUIRE(p && g && m && v && ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0),
-                  "%s: bad argument (p, g, m, v non-NULL, all bases 16-byte aligned)", what);
-    DCLIP_REQUIRE(table && ((uintptr_t)table & 7) == 0 && count >= 1, "%s: bad argument (a device table on an 8-byte boundary, count >= 1)", what);
-    DCLIP_REQUIRE(tiles >= count && tiles <= INT32_MAX, "%s: %lld tiles for %d ranges: every range has at least one, a launch at most 2^31 - 1", what,
-                  (long long)tiles, (int)count);
-    DCLIP_REQUIRE(!(gscale && record), "%s: gscale (a clipped step) and record (a scaler-driven step) exclude each other", what);
-    DCLIP_REQUIRE(!e || (ema_weight >= 0.f && ema_weight <= 1.f), "%s: ema_weight = 1 - decay must lie in [0, 1] (got %g)", what, (double)ema_weight);
-    DCLIP_REQUIRE(record ? ((uintptr_t)record & 15) == 0 : step >= 1, "%s: bad argument (a 16-byte aligned record of dclip_amp_prepare, or step >= 1)", what);
-    const int mode = record ? ADAMW_AMP : gscale ? ADAMW_SCALED : ADAMW_PLAIN;
-    const float bc1 = record ? 0.f : 1.f - powf(beta1, (float)step);
-    const float bc2 = record ? 0.f : sqrtf(1.f - powf(beta2, (float)step));
-    const float* dev = record ? record : gscale;
+    const int rc = adamw_table_operands(what, p, g, m, v, e, table, count, tiles, step, ema_weight, gscale, record);
+    if (rc != DCLIP_OK) return rc;
+    const AdamwControl c = adamw_control(beta1, beta2, step, gscale, record);
     if (!e || ema_weight == 0.f)                             // no average, or one that stands still: e neither read nor written
-        adamw_table_launch<false>(mode, (unsigned)tiles, (hipStream_t)stream, p, g, m, v, nullptr, table, count, lr, beta1, beta2, eps, bc1, bc2, zero_grad, 0.f, dev);
+        adamw_table_launch<false>(c, (unsigned)tiles, (hipStream_t)stream, p, g, m, v, nullptr, table, count, lr, beta1, beta2, eps, zero_grad, 0.f);
     else
-        adamw_table_launch<true>(mode, (unsigned)tiles, (hipStream_t)stream, p, g, m, v, e, table, count, lr, beta1, beta2, eps, bc1, bc2, zero_grad, ema_weight, dev);
+        adamw_table_launch<true>(c, (unsigned)tiles, (hipStream_t)stream, p, g, m, v, e, table, count, lr, beta1, beta2, eps, zero_grad, ema_weight);
     return dclip_check_launch(what);
 }
 
@@ -522,17 +505,15 @@ extern "C" int dclip_adamw(float* p, float* g, float* m, float* v, int64_t n, fl
     DCLIP_REQUIRE(p && g && m && v && n > 0 && step >= 1, "dclip_adamw: bad argument");
     // 16-byte aligned buffers (the flat parameter layout guarantees it; odd slices fall back): the float4 kernel, one range, for the
     // multiple-of-4 part, the scalar kernel for a tail of < 4 elements
+    const AdamwControl c = adamw_control(beta1, beta2, step, nullptr, nullptr);
     int64_t done = 0;
     if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) done = n / 4 * 4;
     if (done > 0) {
-        const int rc = adamw_multi_launch("dclip_adamw", &p, &g, &m, &v, &done, 1, lr, beta1, beta2, eps, weight_decay, step, zero_grad, nullptr, stream);
+        const int rc = adamw_multi_launch("dclip_adamw", &p, &g, &m, &v, nullptr, &done, 1, lr, beta1, beta2, eps, weight_decay, c, zero_grad, 0.f, stream);
         if (rc != DCLIP_OK) return rc;
     }
-    if (done < n) {
-        const float bc1 = 1.f - powf(beta1, (float)step);
-        const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
+    if (done < n)
         hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n - done)), dim3(256), 0, (hipStream_t)stream, p + done, g + done, m + done,
-                           v + done, n - done, lr, beta1, beta2, eps, weight_decay, bc1, bc2, zero_grad);
-    }
+                           v + done, n - done, lr, beta1, beta2, eps, weight_decay, c.bc1, c.bc2_sqrt, zero_grad);
     return dclip_check_launch("dclip_adamw");
 }

@@ -1,5 +1,6 @@
 // Per-element arithmetic and the table lookup shared by the optimizer kernels (optim.hip: AdamW; lamb.hip: the trust-ratio step).  Every
-// function is forced inline: a kernel that used to hold these lines itself compiles to the instruction stream it had.
+// function is forced inline: a kernel that used to hold these lines itself compiles to the instruction stream it had.  At the end, the
+// host code the entries of both files share: the step control and the table entries' operand checks.
 #pragma once
 #include "common.h"
 
@@ -44,4 +45,28 @@ __device__ __forceinline__ int table_range_of(const dclip_adamw_range* __restric
         if (tab[mid].tile0 <= t) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// ---- host side: what the entries of optim.hip and lamb.hip share before they launch ----
+
+// How a step's kernels learn their multiplier and bias corrections: the mode, bc1 and sqrt(bc2) of `step` (0 under a scaler, whose record
+// carries those of the steps taken) and the device pointer the kernels read, the record or gscale (NULL: the plain step).
+struct AdamwControl { int mode; float bc1, bc2_sqrt; const float* dev; };
+inline AdamwControl adamw_control(float beta1, float beta2, int64_t step, const float* gscale, const float* record) {
+    if (record) return {ADAMW_AMP, 0.f, 0.f, record};
+    return {gscale ? ADAMW_SCALED : ADAMW_PLAIN, 1.f - powf(beta1, (float)step), sqrtf(1.f - powf(beta2, (float)step)), gscale};
+}
+
+// the operands dclip_adamw_table and dclip_lamb_table have in common, checked
+inline int adamw_table_operands(const char* what, const float* p, const float* g, const float* m, const float* v, const float* e, const void* table, int32_t count,
+                                int64_t tiles, int64_t step, float ema_weight, const float* gscale, const float* record) {
+    DCLIP_REQUIRE(p && g && m && v && ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15) == 0),
+                  "%s: bad argument (p, g, m, v non-NULL, all bases 16-byte aligned)", what);
+    DCLIP_REQUIRE(table && ((uintptr_t)table & 7) == 0 && count >= 1, "%s: bad argument (a device table on an 8-byte boundary, count >= 1)", what);
+    DCLIP_REQUIRE(tiles >= count && tiles <= INT32_MAX, "%s: %lld tiles for %d ranges: every range has at least one, a launch at most 2^31 - 1", what,
+                  (long long)tiles, (int)count);
+    DCLIP_REQUIRE(!(gscale && record), "%s: gscale (a clipped step) and record (a scaler-driven step) exclude each other", what);
+    DCLIP_REQUIRE(!e || (ema_weight >= 0.f && ema_weight <= 1.f), "%s: ema_weight = 1 - decay must lie in [0, 1] (got %g)", what, (double)ema_weight);
+    DCLIP_REQUIRE(record ? ((uintptr_t)record & 15) == 0 : step >= 1, "%s: bad argument (a 16-byte aligned record of dclip_amp_prepare, or step >= 1)", what);
+    return DCLIP_OK;
 }

@@ -352,14 +352,22 @@ SUMSQ_PARTIALS = 1024      # DCLIP_SUMSQ_PARTIALS (include/dclip.h): partial sum
 ADAMW_MAX_RANGES = 24      # DCLIP_ADAMW_MAX_RANGES
 
 
+def _range_arrays(items, width):
+    """what a multi-range entry takes for `items`, a list of `width`-tuples of equally long 1-D tensors (all checked to be on a GPU):
+    -> ([one pointer array per position], the array of their lengths, the number of ranges)"""
+    import ctypes
+    for it in items:
+        _chk(*it)
+    n = len(items)
+    ptrs = [(ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items]) for k in range(width)]
+    return ptrs, (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items]), n
+
+
 def sumsq_multi(gs, partials, stream=None):
     """partials[:SUMSQ_PARTIALS] <- partial sums of g^2 over at most 24 read-only f32 ranges `gs` in ONE launch, the rest of `partials` <- 0
     (include/dclip.h: dclip_sumsq_multi); dclip_clip_coef adds them up"""
-    import ctypes
-    _chk(partials, *gs)
-    n = len(gs)
-    ptrs = (ctypes.c_void_p * max(n, 1))(*[g.data_ptr() for g in gs])
-    lens = (ctypes.c_int64 * max(n, 1))(*[g.numel() for g in gs])
+    _chk(partials)
+    (ptrs,), lens, n = _range_arrays([(g,) for g in gs], 1)
     lib().dclip_sumsq_multi(ptrs, lens, n, _p(partials), partials.numel(), _stream() if stream is None else stream)
     return partials
 
@@ -374,14 +382,9 @@ def clip_coef(partials, max_norm, out, extra_sumsq=None, stream=None):
 def adamw_multi_scaled(items, lr, betas, eps, weight_decay, step, zero_grad=False, gscale=None, stream=None):
     """AdamW on at most 24 ranges [(p, g, m, v)] of equally long 1-D f32 tensors in ONE launch, on g * gscale[0] (gscale: a device tensor,
     None = unscaled; include/dclip.h: dclip_adamw_multi_scaled)"""
-    import ctypes
-    for it in items:
-        _chk(*it)
+    ptrs, lens, n = _range_arrays(items, 4)
     _chk(gscale)
-    n = len(items)
-    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items])
-    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
-    lib().dclip_adamw_multi_scaled(arr(0), arr(1), arr(2), arr(3), lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
+    lib().dclip_adamw_multi_scaled(*ptrs, lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
                                    1 if zero_grad else 0, _p(gscale), _stream() if stream is None else stream)
 
 
@@ -406,14 +409,9 @@ def amp_prepare(record, skipped, betas, step, found_inf=None, grad_scale=None, p
 
 def adamw_multi_amp(items, lr, betas, eps, weight_decay, zero_grad, record, stream=None):
     """adamw_multi_scaled with multiplier, skip flag and bias corrections read from `record` of amp_prepare (include/dclip.h: dclip_adamw_multi_amp)"""
-    import ctypes
-    for it in items:
-        _chk(*it)
+    ptrs, lens, n = _range_arrays(items, 4)
     _chk(record)
-    n = len(items)
-    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items])
-    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
-    lib().dclip_adamw_multi_amp(arr(0), arr(1), arr(2), arr(3), lens, n, lr, betas[0], betas[1], eps, weight_decay, 1 if zero_grad else 0,
+    lib().dclip_adamw_multi_amp(*ptrs, lens, n, lr, betas[0], betas[1], eps, weight_decay, 1 if zero_grad else 0,
                                 _p(record), _stream() if stream is None else stream)
 
 
@@ -421,14 +419,9 @@ def adamw_multi_ema(items, lr, betas, eps, weight_decay, step, zero_grad, ema_we
     """AdamW on at most 24 ranges [(p, g, m, v, e)] in ONE launch, e <- e + ema_weight * (p' - e) on the parameters it writes
     (include/dclip.h: dclip_adamw_multi_ema).  gscale: adamw_multi_scaled's multiplier; record: adamw_multi_amp's record (`step` is then
     not read); not both.  ema_weight: float(numpy.float32(1.0 - decay)), the subtraction in double."""
-    import ctypes
-    for it in items:
-        _chk(*it)
+    ptrs, lens, n = _range_arrays(items, 5)
     _chk(gscale, record)
-    n = len(items)
-    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in items])
-    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in items])
-    lib().dclip_adamw_multi_ema(arr(0), arr(1), arr(2), arr(3), arr(4), lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
+    lib().dclip_adamw_multi_ema(*ptrs, lens, n, lr, betas[0], betas[1], eps, weight_decay, step,
                                 1 if zero_grad else 0, ema_weight, _p(gscale), _p(record), _stream() if stream is None else stream)
 
 
@@ -453,15 +446,20 @@ def adamw_table_image(ranges, total, out=None):
     return out, tiles.value
 
 
+def _table_operands(what, p, g, m, v, e, table, count):
+    """the operand checks adamw_table and lamb_table share"""
+    if table.dtype != torch.uint8 or table.numel() < lib().dclip_adamw_table_bytes(count):
+        raise ValueError('%s: table is the uint8 device copy of an image of %d ranges' % (what, count))
+    if any(t.numel() != p.numel() or t.dtype != torch.float32 for t in (p, g, m, v) + (() if e is None else (e,))):
+        raise ValueError('%s: p, g, m, v (and e) are f32 buffers of one length, the `total` the table was filled for' % what)
+
+
 def adamw_table(p, g, m, v, e, table, count, tiles, lr, betas, eps, step, zero_grad=False, ema_weight=0.0, gscale=None, record=None, stream=None):
     """AdamW on `count` ranges of the flat f32 buffers p, g, m, v (and e, or None) in ONE launch, each range with its own lr_scale and
     weight_decay from the device `table` (the uploaded image of adamw_table_image, with its `tiles`); gscale / record as in
     adamw_multi_ema (include/dclip.h: dclip_adamw_table)"""
     _chk(p, g, m, v, e, table, gscale, record)
-    if table.dtype != torch.uint8 or table.numel() < lib().dclip_adamw_table_bytes(count):
-        raise ValueError('adamw_table: table is the uint8 device copy of an image of %d ranges' % count)
-    if any(t.numel() != p.numel() or t.dtype != torch.float32 for t in (p, g, m, v) + (() if e is None else (e,))):
-        raise ValueError('adamw_table: p, g, m, v (and e) are f32 buffers of one length, the `total` the table was filled for')
+    _table_operands('adamw_table', p, g, m, v, e, table, count)
     lib().dclip_adamw_table(_p(p), _p(g), _p(m), _p(v), _p(e), _p(table), count, tiles, lr, betas[0], betas[1], eps, step, 1 if zero_grad else 0,
                             ema_weight, _p(gscale), _p(record), _stream() if stream is None else stream)
 
@@ -478,10 +476,7 @@ def lamb_table(p, g, m, v, e, table, count, tiles, lr, betas, eps, step, workspa
     """adamw_table's operands, stepped with a trust ratio per range (include/dclip.h: dclip_lamb_table): three launches.  workspace, stats:
     lamb_buffers(count, tiles); stats holds {|p|, |u|, r, 0} per range afterwards.  trust_clip: None = no clip."""
     _chk(p, g, m, v, e, table, gscale, record, workspace, stats)
-    if table.dtype != torch.uint8 or table.numel() < lib().dclip_adamw_table_bytes(count):
-        raise ValueError('lamb_table: table is the uint8 device copy of an image of %d ranges' % count)
-    if any(t.numel() != p.numel() or t.dtype != torch.float32 for t in (p, g, m, v) + (() if e is None else (e,))):
-        raise ValueError('lamb_table: p, g, m, v (and e) are f32 buffers of one length, the `total` the table was filled for')
+    _table_operands('lamb_table', p, g, m, v, e, table, count)
     if workspace.dtype != torch.uint8 or stats.dtype != torch.float32 or stats.numel() < 4 * count:
         raise ValueError('lamb_table: workspace is uint8, stats f32 [%d, 4] (lamb_buffers)' % count)
     lib().dclip_lamb_table(_p(p), _p(g), _p(m), _p(v), _p(e), _p(table), count, tiles, lr, betas[0], betas[1], eps, step, 1 if zero_grad else 0,
@@ -491,15 +486,12 @@ def lamb_table(p, g, m, v, e, table, count, tiles, lr, betas, eps, step, workspa
 
 def swap_multi(pairs, stream=None):
     """a <-> b, bit for bit, for at most 24 pairs [(a, b)] of equally long 1-D f32 tensors in ONE launch (include/dclip.h: dclip_swap_multi)"""
-    import ctypes
     for a, b in pairs:
         _chk(a, b)
         if a.numel() != b.numel():
             raise ValueError('swap_multi: the two sides of a pair have %d and %d elements' % (a.numel(), b.numel()))
-    n = len(pairs)
-    arr = lambda k: (ctypes.c_void_p * max(n, 1))(*[t[k].data_ptr() for t in pairs])
-    lens = (ctypes.c_int64 * max(n, 1))(*[t[0].numel() for t in pairs])
-    lib().dclip_swap_multi(arr(0), arr(1), lens, n, _stream() if stream is None else stream)
+    ptrs, lens, n = _range_arrays(pairs, 2)
+    lib().dclip_swap_multi(*ptrs, lens, n, _stream() if stream is None else stream)
 
 
 def clipscore(img, cand, refs=None, ref_offsets=None, *, K=1, w=2.5):

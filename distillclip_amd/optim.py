@@ -4,10 +4,25 @@ stepped per epoch)."""
 import contextlib
 import math
 import struct
+from typing import NamedTuple
 
 import torch
 
 from ._lib import lib
+
+
+# One materialised tower's part of a step: the stream its update runs on (None: a CPU rehearsal) and its ranges, [(p, g, m, v)] or, keeping
+# an EMA, [(p, g, m, v, e)] (a sharded tower's: its owned slices, and only for the sums of a clipping step).
+_Job = NamedTuple('_Job', [('tower', object), ('stream', object), ('items', list), ('sharded', bool)])
+# What every update of one step is handed after its operands, in the order of the hooks' trailing arguments.  st: the raw handle of the stream
+# it runs on (None: the current one); ema_weight: None, or 1 - ema_decay, the step keeps the average; gscale: None, or the clipping
+# coefficient, a 1-element device tensor; record: None, or the scaler-driven step's device record.
+_Control = NamedTuple('_Control', [('zero_grad', bool), ('st', object), ('ema_weight', object), ('gscale', object), ('record', object)])
+# What one step() does, settled (and what it cannot do refused) before the step counter moves.  clip: max_grad_norm is set; amp: None, or
+# (found_inf, grad_scale) as the loss scaler left them; ema_w: None, or 1 - ema_decay rounded once to f32; kind: the launch, 'multi' (the 24-range
+# entries), 'table' (groups) or 'lamb' (trust_ratio); hyper: {id(parameter): (lr_scale, weight_decay)} of the declared groups; layouts:
+# (kind, id(tower)) -> the ranges such a launch takes, cut once per step (_layout).
+_Plan = NamedTuple('_Plan', [('clip', bool), ('amp', object), ('ema_w', object), ('kind', str), ('hyper', dict), ('layouts', dict)])
 
 
 def cosine_with_warmup(step, warm, total):
@@ -21,9 +36,7 @@ def cosine_with_warmup(step, warm, total):
 class FusedAdamW:
     """AdamW over the contiguous trainable ranges of each tower's flat buffer: one multi-range launch (dclip_adamw_multi_scaled) per
     tower and 24 ranges; a range of odd length or off a 16-byte boundary gets a dclip_adamw launch of its own.  That holds for the plain
-    step only: a step that clips (max_grad_norm set) or that a loss scaler drives has float4 kernels alone, and step() raises ValueError
-    naming such a range (a tower range or an `extra_params` tensor whose length is no multiple of 4 or which is off a 16-byte boundary)
-    before the step counter advances and before anything is launched or written.
+    step only: every other step has float4 kernels alone (REFUSALS, below).
 
     The trainable set is fixed when the optimizer is built, like the reference's AdamW(filter(requires_grad, parameters()))
     (dual_distill_model.py:195, distil_model.py:161): parameters unfrozen later (unfreeze_embed) do not enter it.
@@ -46,8 +59,7 @@ class FusedAdamW:
     parameter and no moment is written, on the device, without a host synchronisation.  A skipped step is counted on the device
     and does not advance the bias corrections (t = step_count - skipped); state_dict() writes that t.  The gradients themselves
     are consumed as they are: p.grad is not written back unscaled (torch's fused AdamW does that).  Once steps have been taken
-    through a scaler, keep stepping through it: a plain step() takes its bias corrections from step_count alone.  Not with the
-    sharded data-parallel exchange: there p.grad holds zeros when the scaler looks for overflows, so step() refuses.
+    through a scaler, keep stepping through it: a plain step() takes its bias corrections from step_count alone.
 
     ema_decay (None = off; a plain attribute, may change between steps): the step also keeps an exponential moving average of the
     parameters it updates, e <- e + (1 - ema_decay) * (p' - e) with p' the parameter the step has just written, in the same kernel
@@ -56,11 +68,8 @@ class FusedAdamW:
     host synchronisation, and a step that a loss scaler skips leaves the average where it is.  1 - ema_decay is formed in double and
     rounded once.  The usual warm-up, so that the average does not stay at the initial weights for the first 1 / (1 - d) steps, is
     host arithmetic before each step: `opt.ema_decay = min(d, (1 + t) / (10 + t))` with t = opt.step_count.  Back to None freezes the
-    average and keeps it.  An EMA step has float4 kernels only (an odd or misaligned range is refused like a clipping step's), and
-    step() refuses it under the sharded data-parallel exchange, where every rank holds 1/W of the optimizer state
-    (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off work).  `with opt.ema_weights():` runs the towers on the average;
-    ema_state_dict() exports it; state_dict() carries it under 'ema', next to 'state' and 'param_groups', which stay what
-    torch.optim.AdamW loads.
+    average and keeps it.  `with opt.ema_weights():` runs the towers on the average; ema_state_dict() exports it; state_dict() carries
+    it under 'ema', next to 'state' and 'param_groups', which stay what torch.optim.AdamW loads.
 
     groups (None = one weight_decay and one lr for every element, the reference's behaviour and exactly today's launches): a list of
     torch-style dicts {'params': [...], 'weight_decay': x, 'lr_scale': s}, either key optional.  A group's elements are decayed by its
@@ -72,12 +81,10 @@ class FusedAdamW:
     differ in (lr_scale, weight_decay), the table lies in device memory, is built at the tower's first step and uploaded again (pinned
     memory, asynchronously on the update's stream) only after `opt.groups[i]['weight_decay']` / `['lr_scale']` or opt.weight_decay
     changed, which takes effect at the next step; no copy and no host synchronisation in any other step.  The clipping norm stays
-    global over all groups.  Extra parameters are stepped per distinct (lr_scale, weight_decay) through the 24-range entries.  The
-    table kernel is float4 only and has no sharded form: an odd or misaligned range raises ValueError, the sharded data-parallel
-    exchange RuntimeError, both before the step counter moves (DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off work).  param_groups lists
-    the declared groups and then the default group, each with lr = opt.lr * lr_scale; state_dict() writes torch's multi-group layout
-    with lr_scale as an extra key per group, which torch.optim.AdamW([*groups, {'params': rest}]) loads and whose own dict loads back;
-    a dict with another number of groups is a ValueError.
+    global over all groups.  Extra parameters are stepped per distinct (lr_scale, weight_decay) through the 24-range entries.
+    param_groups lists the declared groups and then the default group, each with lr = opt.lr * lr_scale; state_dict() writes torch's
+    multi-group layout with lr_scale as an extra key per group, which torch.optim.AdamW([*groups, {'params': rest}]) loads and whose
+    own dict loads back; a dict with another number of groups is a ValueError.
 
     trust_ratio (False = off, and then every launch and every bit is what it is without the argument), trust_clip (None = no clip),
     always_adapt: plain attributes, may change between steps.  With trust_ratio the step is LAMB's (You et al. 2020, timm's Lamb): every
@@ -92,11 +99,21 @@ class FusedAdamW:
     statistics included), ema_decay, groups and overlap / join=False, with no host wait.  Extra parameters are one unit each, every one
     stepped by the same entry as its own one-range layout: three tiny launches per tensor, a dozen for the four projection tensors of a
     plain CLIP student, which is accepted.  last_trust_stats: {tower index: f32 [units, 4] device tensor of (|p|, |u|, r, 0)} and
-    {('extra', j): f32 [1, 4]} after a step; trust_units() lists (parameter name, begin, length) per key in the same order.  Refused
-    before the step counter moves: ValueError for a unit that is no multiple of 4 elements or off a 16-byte boundary and for a
-    trust_clip that is <= 0 or not finite, RuntimeError under the sharded data-parallel exchange (DCLIP_DP_MODE=allreduce and
-    DCLIP_DP_MODE=off work).  state_dict() then carries trust_ratio / trust_clip / always_adapt as extra keys of every parameter group
-    (torch.optim.AdamW.load_state_dict ignores them, like lr_scale); load_state_dict() restores them."""
+    {('extra', j): f32 [1, 4]} after a step; trust_units() lists (parameter name, begin, length) per key in the same order.
+    state_dict() then carries trust_ratio / trust_clip / always_adapt as extra keys of every parameter group
+    (torch.optim.AdamW.load_state_dict ignores them, like lr_scale); load_state_dict() restores them.
+
+    REFUSALS.  What a step cannot do, step() refuses on the host, before the step counter advances and before anything is launched or
+    written (_plan):
+      - RuntimeError under the sharded data-parallel exchange for a step that a loss scaler drives (there p.grad holds zeros when the
+        scaler looks for overflows), that keeps an EMA (every rank holds 1/W of the optimizer state), that has groups or that forms
+        trust ratios (the table kernels have no sharded form; no rank holds a whole unit's norm).  DCLIP_DP_MODE=allreduce and
+        DCLIP_DP_MODE=off work for all four.
+      - ValueError naming the range, for every step but the plain one, if a range is no multiple of 4 elements or off a 16-byte
+        boundary: a tower range or an `extra_params` tensor of a step that clips, is driven by a loss scaler or keeps an EMA; a range as
+        the groups cut it; a unit of a trust-ratio step, an extra parameter included.
+      - ValueError for an ema_decay outside [0, 1], a group value that has become negative or non-finite, a trust_clip that is <= 0 or
+        not finite; RuntimeError inside ema_weights()."""
 
     _step_supports_amp_scaling = True
 
@@ -142,6 +159,20 @@ class FusedAdamW:
             r = self._fixed_ranges[id(tw)] = [list(x) for x in tw.trainable_ranges()]
         return r
 
+    @staticmethod
+    def _placed(tw):
+        """[(parameter, its offset in the tower's flat layout)]"""
+        return list(zip([p for p in tw._params() if p is not None], tw._offsets))
+
+    def _owned(self, tw):
+        """_placed(tw) of the parameters this optimizer updates: the set captured by _ranges(), not the live requires_grad flags"""
+        rng = self._ranges(tw)
+        return [(p, off) for p, off in self._placed(tw) if any(a <= off < b for a, b in rng)]
+
+    def _is_hip(self, hook):
+        """whether `hook` (one of the nine, e.g. '_adamw') is the product's HIP launch, not a torch stand-in substituted for a rehearsal"""
+        return getattr(type(self), hook) is getattr(FusedAdamW, hook + '_hip')
+
     # ---- parameter groups ----
     _GROUP_KEYS = ('params', 'weight_decay', 'lr_scale')
 
@@ -150,12 +181,7 @@ class FusedAdamW:
         its requires_grad parameters, which are what _ranges() will capture), tower by tower, extras last"""
         out = []
         for tw in self.towers:
-            live = [p for p in tw._params() if p is not None]
-            if tw.flat is None:
-                out += [p for p in live if p.requires_grad]
-            else:
-                rng = self._ranges(tw)
-                out += [p for p, off in zip(live, tw._offsets) if any(a <= off < b for a, b in rng)]
+            out += [p for p, _ in self._placed(tw) if p.requires_grad] if tw.flat is None else [p for p, _ in self._owned(tw)]
         return out + list(self.extras)
 
     @staticmethod
@@ -203,7 +229,7 @@ class FusedAdamW:
         units: cut at EVERY parameter's offset, equal neighbours are not merged (the trust-ratio step: one range per tensor)."""
         hyper = (self._hyper_of() if self.groups is not None else {}) if hyper is None else hyper
         default = (1.0, self.weight_decay)
-        segs = sorted((off, hyper.get(id(p), default)) for p, off in zip([p for p in tw._params() if p is not None], tw._offsets))
+        segs = sorted((off, hyper.get(id(p), default)) for p, off in self._owned(tw))
         out = []
         for a, b in self._ranges(tw):
             inside = [(off, key) for off, key in segs if a <= off < b]
@@ -226,8 +252,6 @@ class FusedAdamW:
         p, g, m, v, e = bufs
         ops.adamw_table(p, g, m, v, e, tab['dev'], len(ranges), tab['tiles'], self.lr, self.betas, self.eps, self.step_count, zero_grad,
                         0.0 if ema_weight is None else ema_weight, gscale, record, st)
-
-    _adamw_table = _adamw_table_hip
 
     def _table_of(self, key, flat, ranges):
         """the device table of `ranges` over the flat buffer `flat`, kept under `key`: built on first use, uploaded again when `ranges` differ"""
@@ -267,57 +291,22 @@ class FusedAdamW:
                        0.0 if ema_weight is None else ema_weight, gscale, record, self._trust_clip_value(), self.always_adapt, st)
         return held[2]
 
-    _lamb_table = _lamb_table_hip
-
-    def _extra_hyper(self):
-        """{id(extra parameter): (lr_scale, weight_decay)}"""
-        hyper = self._hyper_of() if self.groups is not None else {}
-        return {id(p): hyper.get(id(p), (1.0, self.weight_decay)) for p in self.extras}
-
     def trust_units(self):
         """{tower index: [(parameter name, begin, length)], ('extra', j): [(name, 0, numel)]}: the units of a trust-ratio step, in the
         order of the rows of last_trust_stats (begin and length in elements of the tower's flat buffer, the layout's padding included)"""
-        out = {}
+        out, names = {}, {}
         for i, tw in enumerate(self.towers):
             module = getattr(tw, 'module', None)
             named = {id(p): n for n, p in module.named_parameters()} if module is not None else {}
-            at = {off: named.get(id(p), f'parameter {j}') for j, (p, off) in enumerate(zip([p for p in tw._params() if p is not None], tw._offsets))}
+            names.update(named)
+            at = {off: named.get(id(p), f'parameter {j}') for j, (p, off) in enumerate(self._placed(tw))}
             fresh = id(tw) not in self._fixed_ranges
             out[i] = [(at.get(a, f'[{a}, {b})'), a, b - a) for a, b, _, _ in self._group_ranges(tw, {}, units=True)]
             if fresh and tw.flat is None:                    # a tower that is not materialised yet: its trainable set is captured at its first step
                 del self._fixed_ranges[id(tw)]
-        names = {}
-        for tw in self.towers:
-            module = getattr(tw, 'module', None)
-            if module is not None:
-                names.update((id(p), n) for n, p in module.named_parameters())
         for j, p in enumerate(self.extras):
             out[('extra', j)] = [(names.get(id(p), f'extra parameter {j}'), 0, p.numel())]
         return out
-
-    def _refuse_trust_step(self):
-        """trust ratios: dclip_lamb_table is float4 only and has no sharded form.  Refused here, before the step counter moves: a bad
-        trust_clip, the sharded exchange, a unit (a tower's or an extra parameter) that is odd or off a 16-byte boundary"""
-        self._trust_clip_value()
-        if any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
-            raise RuntimeError('FusedAdamW.step: trust ratios are not formed under the sharded data-parallel exchange: every rank updates 1/W of '
-                               'each gradient bucket, cut by the exchange plan and not at the tensors, so no rank holds a whole unit\'s norm.  '
-                               'The modes that take trust_ratio are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
-        if type(self)._lamb_table is not FusedAdamW._lamb_table_hip:
-            return
-        hyper = self._hyper_of() if self.groups is not None else {}
-        tail = 'a step with trust ratios (dclip_lamb_table) needs every unit, one per parameter tensor, to be a multiple of 4 elements on a 16-byte boundary'
-        for i, tw in enumerate(self.towers):
-            if tw.flat is None:
-                continue
-            for a, e, _, _ in self._group_ranges(tw, hyper, units=True):
-                if (e - a) % 4 or a % 4 or (tw.flat.data_ptr() | tw.flat_grad.data_ptr()) % 16:
-                    raise ValueError(f'FusedAdamW.step: tower {i} range [{a}, {e}) has {e - a} elements at {tw.flat.data_ptr() + 4 * a:#x} (gradient at '
-                                     f'{tw.flat_grad.data_ptr() + 4 * a:#x}); {tail}')
-        for i, p in enumerate(self.extras):
-            if p.grad is not None and (p.numel() % 4 or (p.data_ptr() | p.grad.data_ptr()) % 16):
-                raise ValueError(f'FusedAdamW.step: extra parameter {i} ({tuple(p.shape)}) has {p.numel()} elements at {p.data_ptr():#x} (gradient at '
-                                 f'{p.grad.data_ptr():#x}); {tail}')
 
     @contextlib.contextmanager
     def _with_hyper(self, lr_scale, weight_decay):
@@ -341,8 +330,6 @@ class FusedAdamW:
         lib().dclip_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), self.lr, self.betas[0],
                           self.betas[1], self.eps, self.weight_decay, self.step_count, 1 if zero_grad else 0, st)
 
-    _adamw = _adamw_hip
-
     def _sumsq_hip(self, views, out, st):
         """out (f32, ops.SUMSQ_PARTIALS slots per 24 views, every slot written) <- partial sums of the squares of the 1-D f32 `views`.
         (`_sumsq` and `_coef` can be substituted by torch versions like `_adamw`, for the gloo rehearsals.)"""
@@ -351,14 +338,10 @@ class FusedAdamW:
             k = i // ops.ADAMW_MAX_RANGES
             ops.sumsq_multi(views[i:i + ops.ADAMW_MAX_RANGES], out[k * ops.SUMSQ_PARTIALS:(k + 1) * ops.SUMSQ_PARTIALS], st)
 
-    _sumsq = _sumsq_hip
-
     def _coef_hip(self, partials, extra, out, st):
         """out[0] <- sqrt(sum(partials) + extra[0]) (extra may be None), out[1] <- min(1, max_grad_norm / (out[0] + 1e-6))"""
         from . import ops
         ops.clip_coef(partials, self.max_grad_norm, out, extra, st)
-
-    _coef = _coef_hip
 
     def _prepare_hip(self, found_inf, grad_scale, partials, extra, record, skipped, st):
         """record <- this step's control record, skipped += (found_inf != 0) (ops.amp_prepare); partials None: the step does not clip.
@@ -367,55 +350,48 @@ class FusedAdamW:
         ops.amp_prepare(record, skipped, self.betas, self.step_count, found_inf, grad_scale, partials,
                         0.0 if partials is None else self.max_grad_norm, extra, st)
 
-    _prepare = _prepare_hip
-
     def _adamw_amp_hip(self, p, g, m, v, zero_grad, st, record):
         from . import ops
         ops.adamw_multi_amp([(p, g, m, v)], self.lr, self.betas, self.eps, self.weight_decay, zero_grad, record, st)
-
-    _adamw_amp = _adamw_amp_hip
 
     def _adamw_ema_hip(self, items, zero_grad, st, ema_weight, gscale, record):
         """items: at most ops.ADAMW_MAX_RANGES of (p, g, m, v, e).  (`_adamw_ema` and `_swap` can be substituted by torch versions like `_adamw`.)"""
         from . import ops
         ops.adamw_multi_ema(items, self.lr, self.betas, self.eps, self.weight_decay, self.step_count, zero_grad, ema_weight, gscale, record, st)
 
-    _adamw_ema = _adamw_ema_hip
-
     def _swap_hip(self, pairs, st):
         from . import ops
         ops.swap_multi(pairs, st)
 
-    _swap = _swap_hip
+    # The hook seam: step() and ema_weights() launch through these nine names, which a CPU rehearsal substitutes by name with torch versions
+    # (tests/test_parallel_cpu.py was the first); _is_hip() tells which checks a stand-in, which takes any range, switches off.
+    _adamw, _sumsq, _coef, _prepare, _adamw_amp = _adamw_hip, _sumsq_hip, _coef_hip, _prepare_hip, _adamw_amp_hip
+    _adamw_ema, _swap, _adamw_table, _lamb_table = _adamw_ema_hip, _swap_hip, _adamw_table_hip, _lamb_table_hip
 
     def _adamw_many(self, items, zero_grad, st, gscale=None, record=None, ema_weight=None):
         """items: [(p, g, m, v)] of equally long 1-D f32 views — ONE multi-range launch per ops.ADAMW_MAX_RANGES ranges (the sharded step
         has one owned slice per gradient bucket: nine launches per step for the two l_clip students became one per tower).  A substituted
         `_adamw`, an odd length or a misaligned pointer: one `_adamw` call per range.  record: the scaler-driven step, every range reads
-        that record instead (step() has refused an odd length or a misaligned pointer before it began: _refuse_scalar_ranges).
+        that record instead (step() has refused an odd length or a misaligned pointer before it began: _refuse_misaligned).
         ema_weight: items are [(p, g, m, v, e)] and every launch is dclip_adamw_multi_ema, whichever of the three steps it is."""
         from . import ops
+        chunks = [items[i:i + ops.ADAMW_MAX_RANGES] for i in range(0, len(items), ops.ADAMW_MAX_RANGES)]
+        hyper = self.lr, self.betas, self.eps, self.weight_decay
         if ema_weight is not None:                           # items: [(p, g, m, v, e)], plain, clipped or scaler-driven alike
-            for i in range(0, len(items), ops.ADAMW_MAX_RANGES):
-                self._adamw_ema(items[i:i + ops.ADAMW_MAX_RANGES], zero_grad, st, ema_weight, gscale, record)
-            return
-        if record is not None:
-            if type(self)._adamw_amp is not FusedAdamW._adamw_amp_hip:
-                for p, g, m, v in items:
-                    self._adamw_amp(p, g, m, v, zero_grad, st, record)
-                return
-            for i in range(0, len(items), ops.ADAMW_MAX_RANGES):
-                ops.adamw_multi_amp(items[i:i + ops.ADAMW_MAX_RANGES], self.lr, self.betas, self.eps, self.weight_decay, zero_grad, record, st)
-            return
-        scale = () if gscale is None else (gscale,)
-        if type(self)._adamw is not FusedAdamW._adamw_hip or any(p.numel() % 4 or (p.data_ptr() | g.data_ptr() | m.data_ptr() | v.data_ptr()) % 16
-                                                                  for p, g, m, v in items):
+            for chunk in chunks:
+                self._adamw_ema(chunk, zero_grad, st, ema_weight, gscale, record)
+        elif record is not None and self._is_hip('_adamw_amp'):
+            for chunk in chunks:
+                ops.adamw_multi_amp(chunk, *hyper, zero_grad, record, st)
+        elif record is not None:
             for p, g, m, v in items:
-                self._adamw(p, g, m, v, zero_grad, st, *scale)
-            return
-        for i in range(0, len(items), ops.ADAMW_MAX_RANGES):
-            ops.adamw_multi_scaled(items[i:i + ops.ADAMW_MAX_RANGES], self.lr, self.betas, self.eps, self.weight_decay, self.step_count, zero_grad,
-                                   gscale, st)
+                self._adamw_amp(p, g, m, v, zero_grad, st, record)
+        elif self._is_hip('_adamw') and not any(p.numel() % 4 or (p.data_ptr() | g.data_ptr() | m.data_ptr() | v.data_ptr()) % 16 for p, g, m, v in items):
+            for chunk in chunks:
+                ops.adamw_multi_scaled(chunk, *hyper, self.step_count, zero_grad, gscale, st)
+        else:
+            for p, g, m, v in items:
+                self._adamw(p, g, m, v, zero_grad, st, *(() if gscale is None else (gscale,)))
 
     def zero_grad(self, set_to_none=False):
         from .model.component._tower import autograd_params_mode
@@ -437,8 +413,7 @@ class FusedAdamW:
         tensors (or a DistributedDataParallel reducer's bucket views) and tower.flat_grad, which the kernel below reads, was never
         written.  Copy them into the flat buffer (one multi-tensor copy); a trainable parameter without a gradient counts as zero."""
         dst, src = [], []
-        live = [p for p in tw._params() if p is not None]
-        for p, off in zip(live, tw._offsets):
+        for p, off in FusedAdamW._placed(tw):
             if not p.requires_grad:
                 continue
             view = tw.flat_grad[off:off + p.numel()]
@@ -531,9 +506,8 @@ class FusedAdamW:
         return e
 
     def _jobs(self, overlap, main, clip, ema=False):
-        """[(tower, stream, items, sharded)] of the materialised towers, in tower order: the stream the tower's update runs on and the
-        [(p, g, m, v)] ranges it updates (a sharded tower's: only for the sums of a clipping step, _step_sharded takes its own);
-        ema: [(p, g, m, v, e)]"""
+        """[_Job] of the materialised towers, in tower order: the stream the tower's update runs on and the [(p, g, m, v)] ranges it
+        updates (a sharded tower's: only for the sums of a clipping step, _step_sharded takes its own); ema: [(p, g, m, v, e)]"""
         from .model.component._tower import autograd_params_mode
         jobs = []
         for tw in self.towers:
@@ -541,22 +515,19 @@ class FusedAdamW:
                 continue
             m, v = self._moments(tw)
             if self._sharded(tw):
-                jobs.append((tw, tw.sync.stream_for(tw.flat, tw), self._shard_items(tw, m, v) if clip else [], True))
+                jobs.append(_Job(tw, tw.sync.stream_for(tw.flat, tw), self._shard_items(tw, m, v) if clip else [], True))
                 continue
             # (gradients that went through autograd may have been written by anybody's stream — a DDP reducer's —: take them on `main`)
             stream = tw.bwd_stream if (overlap and not autograd_params_mode(tw) and getattr(tw, 'bwd_stream', None) is not None) else main
-            items = [(tw.flat[b:e], tw.flat_grad[b:e], m[b:e], v[b:e]) for b, e in self._ranges(tw)]
-            if ema:
-                avg = self._ema_of(id(tw), tw.flat)
-                items = [it + (avg[b:e],) for it, (b, e) in zip(items, self._ranges(tw))]
-            jobs.append((tw, stream, items, False))
+            bufs = (tw.flat, tw.flat_grad, m, v) + ((self._ema_of(id(tw), tw.flat),) if ema else ())
+            jobs.append(_Job(tw, stream, [tuple(t[b:e] for t in bufs) for b, e in self._ranges(tw)], False))
         return jobs
 
     def _await_grads(self, job, main):
         """a tower that is not sharded: its stream waits for the caller's and for the tower's gradients, which then lie in flat_grad"""
         from .model.component._tower import autograd_params_mode
         from .parallel import GradSync
-        tw, stream = job[0], job[1]
+        tw, stream = job.tower, job.stream
         if stream != main:
             stream.wait_stream(main)                         # whatever the caller enqueued before step() (e.g. zero_grad of others)
         if getattr(tw, 'grads_ready', None) is not None:
@@ -566,34 +537,35 @@ class FusedAdamW:
             with GradSync._On(stream):
                 self._pack_autograd_grads(tw)
 
-    def _update(self, job, zero_grad, overlap, main, coef=None, record=None, ema_weight=None):
-        """one tower's AdamW, on g * coef if given or driven by the scaler's record, and what follows it on the tower's stream.  Returns
-        the stream the current one has to join, None if there is none.  ema_weight: the step keeps the average; a new average is
-        first filled from the whole flat buffer (frozen ranges too: they never change), on the same stream."""
+    def _multi(self, items, ctl):
+        """`items` through the 24-range entries (_adamw_many) under the step's control"""
+        self._adamw_many(items, ctl.zero_grad, ctl.st, ctl.gscale, ctl.record, ctl.ema_weight)
+
+    def _update(self, job, plan, ctl, overlap, main):
+        """one tower's update by the launch the plan names, on g * ctl.gscale if given or driven by the scaler's record, and what follows
+        it on the tower's stream.  Returns the stream the current one has to join, None if there is none.  A step that keeps the
+        average first fills a new one from the whole flat buffer (frozen ranges too: they never change), on the same stream."""
         from .parallel import GradSync
-        tw, stream, items, sharded = job
-        if sharded:
-            return self._step_sharded(tw, coef)              # (its exchange stream waits for the current one: the coefficient)
-        if (coef is not None or record is not None) and stream != main:
+        tw, stream = job.tower, job.stream
+        if job.sharded:
+            return self._step_sharded(tw, ctl.gscale)        # (its exchange stream waits for the current one: the coefficient)
+        if (ctl.gscale is not None or ctl.record is not None) and stream != main:
             stream.wait_stream(main)
         with GradSync._On(stream):
             if id(tw) in self._ema_unseeded:
                 self._ema[id(tw)].copy_(tw.flat)
                 self._ema_unseeded.discard(id(tw))
-            st = stream.cuda_stream if stream is not None else None
-            if self.trust_ratio:                             # one unit per tensor: moments and partial norms, ratios, apply
-                m, v = self._moments(tw)
-                self.last_trust_stats[self.towers.index(tw)] = self._lamb_table(
-                    id(tw), (tw.flat, tw.flat_grad, m, v, self._ema[id(tw)] if ema_weight is not None else None),
-                    self._group_ranges(tw, units=True), zero_grad, st, ema_weight, coef, record)
-            elif self.groups is None:
-                self._adamw_many(items, zero_grad, st, coef, record, ema_weight)
-            else:                                            # one table-driven launch for the tower, whichever of the three steps it is
-                m, v = self._moments(tw)
-                self._adamw_table(tw, (tw.flat, tw.flat_grad, m, v, self._ema[id(tw)] if ema_weight is not None else None),
-                                  self._group_ranges(tw), zero_grad, st, ema_weight, coef, record)
+            ctl = ctl._replace(st=stream.cuda_stream if stream is not None else None)
+            if plan.kind == 'multi':
+                self._multi(job.items, ctl)
+            else:                                            # the whole flat buffers and a table of ranges
+                bufs = (tw.flat, tw.flat_grad, *self._moments(tw), self._ema[id(tw)] if ctl.ema_weight is not None else None)
+                if plan.kind == 'table':                     # ONE launch for the tower, whichever of the three steps it is
+                    self._adamw_table(tw, bufs, self._layout(plan, 'table', tw), *ctl)
+                else:                                        # one unit per tensor: moments and partial norms, ratios, apply
+                    self.last_trust_stats[self.towers.index(tw)] = self._lamb_table(id(tw), bufs, self._layout(plan, 'lamb', tw), *ctl)
             tw.wcache_dirty = True
-            tw._grad_clean = bool(zero_grad) and self._ranges_cover_everything(tw)
+            tw._grad_clean = bool(ctl.zero_grad) and self._ranges_cover_everything(tw)
             if overlap and self.refresh_cache_in_step:
                 tw._prepare_always = False                   # from now on this optimizer keeps the bf16 cache in step
                 tw.prepare()
@@ -602,6 +574,28 @@ class FusedAdamW:
         tw.opt_done = torch.cuda.Event()
         tw.opt_done.record(stream)
         return stream
+
+    def _update_extras(self, extras, plan, ctl):
+        """the parameters outside the tower buffers (`extras`: _extra_items()), on the current stream: their gradients were written by
+        autograd on it.  Every tensor is a one-range layout of its own, [(0, numel, lr_scale, weight_decay)]: the trust-ratio step
+        launches it as that; with groups the tensors of one (lr_scale, weight_decay) go through the 24-range entries together."""
+        if not extras:
+            return
+        if plan.kind == 'multi':
+            return self._multi([it for _, it in extras], ctl)
+        hyper = {j: plan.hyper.get(id(self.extras[j]), (1.0, self.weight_decay)) for j, _ in extras}
+        if plan.kind == 'lamb':
+            for j, it in extras:
+                p = self.extras[j]
+                self.last_trust_stats[('extra', j)] = self._lamb_table(id(p), it if ctl.ema_weight is not None else it + (None,),
+                                                                       [(0, p.numel()) + hyper[j]], *ctl)
+            return
+        by_key = {}
+        for j, it in extras:
+            by_key.setdefault(hyper[j], []).append(it)
+        for (scale, wd), its in by_key.items():
+            with self._with_hyper(scale, wd):
+                self._multi(its, ctl)
 
     def _clip_coef(self, jobs, extras, main, amp=None):
         """max_grad_norm is set: (norm, coef) as two 1-element device tensors, ordered by events only:
@@ -617,22 +611,22 @@ class FusedAdamW:
         from . import ops
         from .parallel import GradSync, all_reduce_sum
         G, R = ops.SUMSQ_PARTIALS, ops.ADAMW_MAX_RANGES
-        slots = [G * ((len(j[2]) + R - 1) // R) for j in jobs] + [G * ((len(extras) + R - 1) // R)]
-        device = jobs[0][0].flat.device if jobs else self.extras[0].device
+        slots = [G * ((len(j.items) + R - 1) // R) for j in jobs] + [G * ((len(extras) + R - 1) // R)]
+        device = jobs[0].tower.flat.device if jobs else self.extras[0].device
         if self._clip_parts is None or self._clip_parts.numel() != max(sum(slots), 1) or self._clip_parts.device != device:
             self._clip_parts = torch.zeros(max(sum(slots), 1), dtype=torch.float32, device=device)
             self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
         parts, out = self._clip_parts, self._clip_out
         at = 0
         for job, n in zip(jobs, slots):
-            tw, stream, items, sharded = job
-            if not sharded:
+            stream = job.stream
+            if not job.sharded:
                 self._await_grads(job, main)
             elif stream != main:
                 stream.wait_stream(main)
-            if items:
+            if job.items:
                 with GradSync._On(stream):
-                    self._sumsq([it[1] for it in items], parts[at:at + n], stream.cuda_stream if stream is not None else None)
+                    self._sumsq([it[1] for it in job.items], parts[at:at + n], stream.cuda_stream if stream is not None else None)
             if stream != main:
                 ev = torch.cuda.Event()
                 ev.record(stream)
@@ -640,11 +634,11 @@ class FusedAdamW:
             at += n
         st = main.cuda_stream if main is not None else None
         if extras:
-            self._sumsq([it[1] for it in extras], parts[at:at + slots[-1]], st)
+            self._sumsq([it[1] for _, it in extras], parts[at:at + slots[-1]], st)
         if amp is not None:
             return self._amp_record(*amp, parts, st)
-        n_sharded = sum(n for j, n in zip(jobs, slots) if j[3])
-        if any(j[3] for j in jobs):                          # (the same on every rank, whatever this rank owns)
+        n_sharded = sum(n for j, n in zip(jobs, slots) if j.sharded)
+        if any(j.sharded for j in jobs):                     # (the same on every rank, whatever this rank owns)
             total = parts[:n_sharded].sum(dtype=torch.float64).view(1)
             all_reduce_sum(total)
             rest = parts[n_sharded:sum(slots)]
@@ -666,51 +660,107 @@ class FusedAdamW:
         self._prepare(one(found_inf), one(grad_scale), partials, None, self._amp_rec, self._skipped, st)
         return (None if partials is None else self._amp_rec[ops.AMP_NORM:ops.AMP_NORM + 1]), self._amp_rec
 
-    def _refuse_scalar_ranges(self, clip, amp, ema=False):
-        """A clipping step, a scaler-driven step and a step that keeps an EMA have float4 kernels only (dclip_sumsq_multi,
-        dclip_adamw_multi_scaled, dclip_adamw_multi_amp, dclip_adamw_multi_ema): a range of a length that is no multiple of 4, or off a 16-byte boundary, is refused here, on the host,
-        before the step counter moves and before anything is launched, not by a kernel's entry half-way through the step.  (The
-        moments and the average start on an allocation's boundary and share the parameters' offsets.)  A substituted torch version
-        takes any range."""
-        cls = type(self)
-        if ema:
-            if cls._adamw_ema is not FusedAdamW._adamw_ema_hip and not (clip and cls._sumsq is FusedAdamW._sumsq_hip):
-                return
-        elif not ((clip and (cls._sumsq is FusedAdamW._sumsq_hip or (not amp and cls._adamw is FusedAdamW._adamw_hip)))
-                  or (amp and cls._adamw_amp is FusedAdamW._adamw_amp_hip)):
-            return
+    def _norm_coef_record(self, plan, jobs, extras, main):
+        """-> (norm, coef, record) of the step, device tensors or None, for {clipping or not} x {a loss scaler or not}: a clipping step
+        forms the sums and from them (norm, coef), under a scaler (norm, record); a scaler alone needs no gradient for its record, so the
+        updates can then go on tower by tower; the plain step has none of the three."""
+        if plan.clip:
+            norm, made = self._clip_coef(jobs, extras, main, plan.amp)
+            return (norm, made, None) if plan.amp is None else (norm, None, made)
+        if plan.amp is None:
+            return None, None, None
+        return None, None, self._amp_record(*plan.amp, None, main.cuda_stream if main is not None else None)[1]
+
+    # ---- what a step cannot do: refused by _plan(), on the host, before the step counter moves and before anything is launched or written ----
+    _NOT_SHARDED = {                                         # feature -> why the sharded data-parallel exchange does not carry it
+        'amp': 'a loss scaler (precision: 16) cannot drive the sharded data-parallel exchange: after backward_and_sync() p.grad holds zeros, so the '
+               'scaler\'s overflow check sees nothing.  The modes that work under precision: 16 are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off',
+        'ema': 'ema_decay is not kept under the sharded data-parallel exchange: every rank updates and holds the state of 1/W of each gradient '
+               'bucket only, and an average in shards would have to be gathered to be used.  The modes that keep an EMA are '
+               'DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off',
+        'groups': 'parameter groups are not stepped under the sharded data-parallel exchange: every rank updates 1/W of each gradient bucket, '
+                  'cut by the exchange plan and not by the groups.  The modes that take groups are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off',
+        'trust': 'trust ratios are not formed under the sharded data-parallel exchange: every rank updates 1/W of each gradient bucket, cut by '
+                 'the exchange plan and not at the tensors, so no rank holds a whole unit\'s norm.  The modes that take trust_ratio are '
+                 'DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off',
+    }
+    _FLOAT4_ONLY = {                                         # launch kind -> what its float4 kernels need of every range
+        'multi': 'a step that clips the gradient norm, is driven by a loss scaler or keeps an EMA (ema_decay) needs every range to be a multiple '
+                 'of 4 elements on a 16-byte boundary.  Only the plain step has an element-wise kernel (dclip_adamw)',
+        'table': 'a step with parameter groups (dclip_adamw_table) needs every range, cut at the group boundaries, to be a multiple of 4 elements '
+                 'on a 16-byte boundary',
+        'lamb': 'a step with trust ratios (dclip_lamb_table) needs every unit, one per parameter tensor, to be a multiple of 4 elements on a '
+                '16-byte boundary',
+    }
+
+    def _features(self, amp):
+        """(feature, what this step has of it or None) of the four features the sharded exchange does not carry, in the order in which
+        they refuse.  Lazily: a setting of a feature's own that cannot be stepped (raised here) comes after the refusals of those before it."""
+        yield 'amp', amp
+        if self._ema_in_use:
+            raise RuntimeError('FusedAdamW.step: inside ema_weights() the towers hold the averaged weights; leave the context first')
+        yield 'ema', self._ema_weight()
+        yield 'groups', None if self.groups is None else self._hyper_of()       # (a value spoiled since construction: ValueError)
+        if self.trust_ratio:
+            self._trust_clip_value()
+        yield 'trust', True if self.trust_ratio else None
+
+    def _plan(self):
+        """-> the _Plan of the step about to be taken.  The only place that refuses: a feature under the sharded exchange, then a range
+        that a float4-only launch of this step cannot take."""
+        found_inf, grad_scale = getattr(self, 'found_inf', None), getattr(self, 'grad_scale', None)
+        amp = None if found_inf is None and grad_scale is None else (found_inf, grad_scale)
+        sharded = any(tw.flat is not None and self._sharded(tw) for tw in self.towers)
+        on = {}
+        for feature, value in self._features(amp):
+            if value is not None and sharded:
+                raise RuntimeError(f'FusedAdamW.step: {self._NOT_SHARDED[feature]}')
+            on[feature] = value
+        kind = 'lamb' if on['trust'] else 'multi' if on['groups'] is None else 'table'
+        plan = _Plan(self.max_grad_norm is not None, amp, on['ema'], kind, on['groups'] or {}, {})
+        # Which ranges must be float4 ranges.  The table kernels have no other form: their ranges are checked unless the hook is a torch
+        # stand-in, which takes any range (with groups AND trust ratios the groups' cut is still checked first, and named first).  The
+        # fixed ranges and the extras go through the 24-range entries and dclip_sumsq_multi, float4 only except for the plain step; H(x): hook
+        # x is the HIP launch:
+        #     EMA  clip  scaler | checked if
+        #      1    0     any   | H(_adamw_ema)
+        #      1    1     any   | H(_adamw_ema) or H(_sumsq)
+        #      0    0     0     | never: dclip_adamw takes any range
+        #      0    0     1     | H(_adamw_amp)
+        #      0    1     0     | H(_sumsq) or H(_adamw)
+        #      0    1     1     | H(_sumsq) or H(_adamw_amp)
+        H, clip, scaler = self._is_hip, plan.clip, amp is not None
+        if plan.ema_w is not None:
+            multi = H('_adamw_ema') or (clip and H('_sumsq'))
+        else:
+            multi = (clip and (H('_sumsq') or (not scaler and H('_adamw')))) or (scaler and H('_adamw_amp'))
+        for check, due in (('table', on['groups'] is not None and H('_adamw_table')), ('lamb', on['trust'] and H('_lamb_table')), ('multi', multi)):
+            if due:
+                self._refuse_misaligned(plan, check)
+        return plan
+
+    def _layout(self, plan, kind, tw):
+        """the ranges a launch of `kind` takes over tower `tw` in this step: what _plan() checks is what _update() launches, cut once"""
+        if (kind, id(tw)) not in plan.layouts:
+            plan.layouts[kind, id(tw)] = self._ranges(tw) if kind == 'multi' else self._group_ranges(tw, plan.hyper, units=kind == 'lamb')
+        return plan.layouts[kind, id(tw)]
+
+    def _refuse_misaligned(self, plan, kind):
+        """ValueError naming the first range of a launch of `kind` (_layout; except for 'table', whose extras go through the 24-range
+        entries, also an extra parameter that has a gradient) that is no multiple of 4 elements or off a 16-byte boundary.  (The moments
+        and the average start on an allocation's boundary and share the parameters' offsets.)"""
         found = []
         for i, tw in enumerate(self.towers):
             if tw.flat is None or self._sharded(tw):         # (a sharded tower's owned slices are cut by the plan of parallel.GradSync)
                 continue
             found += [(f'tower {i} range [{a}, {e})', e - a, tw.flat.data_ptr() + 4 * a, tw.flat_grad.data_ptr() + 4 * a, 4 * a)
-                      for a, e in self._ranges(tw)]
-        found += [(f'extra parameter {i} ({tuple(p.shape)})', p.numel(), p.data_ptr(), p.grad.data_ptr(), 0)
-                  for i, p in enumerate(self.extras) if p.grad is not None]
+                      for a, e, *_ in self._layout(plan, kind, tw)]
+        if kind != 'table':
+            found += [(f'extra parameter {i} ({tuple(p.shape)})', p.numel(), p.data_ptr(), p.grad.data_ptr(), 0)
+                      for i, p in enumerate(self.extras) if p.grad is not None]
         for what, n, *ptrs in found:
             if n % 4 or any(x % 16 for x in ptrs):
-                raise ValueError(f'FusedAdamW.step: {what} has {n} elements at {ptrs[0]:#x} (gradient at {ptrs[1]:#x}); a step that clips '
-                                 'the gradient norm, is driven by a loss scaler or keeps an EMA (ema_decay) needs every range to be a multiple '
-                                 'of 4 elements on a 16-byte boundary.  Only the plain step has an element-wise kernel (dclip_adamw)')
-
-    def _refuse_grouped_step(self):
-        """parameter groups: the table kernel is float4 only and has no sharded form.  Refused here, before the step counter moves: a
-        group value that has become negative or non-finite, the sharded exchange, a cut range that is odd or off a 16-byte boundary"""
-        hyper = self._hyper_of()                             # (raises ValueError on a bad value)
-        if any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
-            raise RuntimeError('FusedAdamW.step: parameter groups are not stepped under the sharded data-parallel exchange: every rank updates '
-                               '1/W of each gradient bucket, cut by the exchange plan and not by the groups.  The modes that take groups are '
-                               'DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
-        if type(self)._adamw_table is not FusedAdamW._adamw_table_hip:
-            return
-        for i, tw in enumerate(self.towers):
-            if tw.flat is None:
-                continue
-            for a, e, _, _ in self._group_ranges(tw, hyper):
-                if (e - a) % 4 or a % 4 or (tw.flat.data_ptr() | tw.flat_grad.data_ptr()) % 16:
-                    raise ValueError(f'FusedAdamW.step: tower {i} range [{a}, {e}) has {e - a} elements at {tw.flat.data_ptr() + 4 * a:#x} (gradient at '
-                                     f'{tw.flat_grad.data_ptr() + 4 * a:#x}); a step with parameter groups (dclip_adamw_table) needs every range, '
-                                     'cut at the group boundaries, to be a multiple of 4 elements on a 16-byte boundary')
+                raise ValueError(f'FusedAdamW.step: {what} has {n} elements at {ptrs[0]:#x} (gradient at {ptrs[1]:#x}); {self._FLOAT4_ONLY[kind]}')
 
     @torch.no_grad()
     def step(self, zero_grad=False, overlap=False, join=True):
@@ -725,69 +775,24 @@ class FusedAdamW:
         dependency (backward -> exchange -> update -> next forward of that tower) and the next step's frozen teacher towers
         may start while the last gradient exchange and update are still running; join() orders the current stream after them
         (zero_grad() and state_dict() call it)."""
-        found_inf, grad_scale = getattr(self, 'found_inf', None), getattr(self, 'grad_scale', None)
-        amp = None if found_inf is None and grad_scale is None else (found_inf, grad_scale)
-        if amp is not None and any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
-            raise RuntimeError('FusedAdamW.step: a loss scaler (precision: 16) cannot drive the sharded data-parallel exchange: after '
-                               'backward_and_sync() p.grad holds zeros, so the scaler\'s overflow check sees nothing.  The modes that work '
-                               'under precision: 16 are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
-        if self._ema_in_use:
-            raise RuntimeError('FusedAdamW.step: inside ema_weights() the towers hold the averaged weights; leave the context first')
-        ema_w = self._ema_weight()
-        if ema_w is not None and any(tw.flat is not None and self._sharded(tw) for tw in self.towers):
-            raise RuntimeError('FusedAdamW.step: ema_decay is not kept under the sharded data-parallel exchange: every rank updates and '
-                               'holds the state of 1/W of each gradient bucket only, and an average in shards would have to be gathered '
-                               'to be used.  The modes that keep an EMA are DCLIP_DP_MODE=allreduce and DCLIP_DP_MODE=off')
-        if self.groups is not None:
-            self._refuse_grouped_step()
-        if self.trust_ratio:
-            self._refuse_trust_step()
-        self._refuse_scalar_ranges(self.max_grad_norm is not None, amp is not None, ema_w is not None)
+        plan = self._plan()                                  # (every refusal)
         self.step_count += 1
         # decided by where the parameters live, not by asking the runtime: a CPU step (the gloo rehearsals) leaves the GPU closed
         on_gpu = any(t.is_cuda for t in [tw.flat for tw in self.towers if tw.flat is not None] + self.extras)
         main = torch.cuda.current_stream() if on_gpu else None
-        jobs = self._jobs(overlap, main, self.max_grad_norm is not None, ema_w is not None)
-        record = None
-        if self.max_grad_norm is None:
-            self.last_grad_norm = coef = None
-            if amp is not None:                              # (the record needs no gradient: the updates go on tower by tower)
-                _, record = self._amp_record(*amp, None, main.cuda_stream if main is not None else None)
-            joined = []
-            for job in jobs:                                 # tower by tower
-                if not job[3]:
-                    self._await_grads(job, main)
-                joined.append(self._update(job, zero_grad, overlap, main, None, record, ema_w))
-            extras = self._extra_items(ema_w is not None)
-        else:
-            jobs.sort(key=lambda j: not j[3])                # (stable) the sharded towers' partial sums lie first
-            extras = self._extra_items(ema_w is not None)
-            if amp is None:
-                self.last_grad_norm, coef = self._clip_coef(jobs, extras, main)
-            else:
-                coef = None
-                self.last_grad_norm, record = self._clip_coef(jobs, extras, main, amp)
-            joined = [self._update(job, zero_grad, overlap, main, coef, record, ema_w) for job in jobs]
-        if extras:
-            # the parameters outside the tower buffers, on the current stream (their gradients were written by autograd on it)
-            st = main.cuda_stream if main is not None else None
-            if self.trust_ratio:                             # every tensor is its own one-range layout
-                hyper = self._extra_hyper()
-                for j, p in enumerate(self.extras):
-                    if p.grad is None:
-                        continue
-                    it = extras.pop(0)
-                    self.last_trust_stats[('extra', j)] = self._lamb_table(id(p), it if ema_w is not None else it + (None,), [(0, p.numel()) + hyper[id(p)]],
-                                                                           zero_grad, st, ema_w, coef, record)
-            elif self.groups is None:
-                self._adamw_many(extras, zero_grad, st, coef, record, ema_w)
-            else:                                            # per distinct (lr_scale, weight_decay), through the existing entries
-                hyper, by_key = self._hyper_of(), {}
-                for p, it in zip([p for p in self.extras if p.grad is not None], extras):
-                    by_key.setdefault(hyper.get(id(p), (1.0, self.weight_decay)), []).append(it)
-                for (scale, wd), its in by_key.items():
-                    with self._with_hyper(scale, wd):
-                        self._adamw_many(its, zero_grad, st, coef, record, ema_w)
+        jobs = self._jobs(overlap, main, plan.clip, plan.ema_w is not None)
+        extras = None
+        if plan.clip:                                        # all sums before the first update: the extras are taken now, not after the towers
+            jobs.sort(key=lambda j: not j.sharded)           # (stable) the sharded towers' partial sums lie first
+            extras = self._extra_items(plan.ema_w is not None)
+        self.last_grad_norm, coef, record = self._norm_coef_record(plan, jobs, extras, main)
+        ctl = _Control(zero_grad, main.cuda_stream if main is not None else None, plan.ema_w, coef, record)
+        joined = []
+        for job in jobs:
+            if not plan.clip and not job.sharded:            # tower by tower (a clipping step has awaited them all for its sums)
+                self._await_grads(job, main)
+            joined.append(self._update(job, plan, ctl, overlap, main))
+        self._update_extras(self._extra_items(plan.ema_w is not None) if extras is None else extras, plan, ctl)
         if join:
             for stream in joined:
                 if stream is not None:
@@ -803,14 +808,14 @@ class FusedAdamW:
         return st
 
     def _extra_items(self, ema=False):
-        """[(p, g, m, v)] of the extras that have a gradient, the gradients averaged over the ranks; ema: [(p, g, m, v, e)], a new average
-        filled from its parameter here, on the current stream, which the extras' update runs on"""
+        """[(j, (p, g, m, v))] of the extras[j] that have a gradient, the gradients averaged over the ranks; ema: (p, g, m, v, e), a new
+        average filled from its parameter here, on the current stream, which the extras' update runs on"""
         if not self.extras:
             return []
         from .parallel import all_reduce_avg
         sync = next((tw.sync for tw in self.towers if getattr(tw, 'sync', None) is not None), None)
         items = []
-        for p in self.extras:
+        for j, p in enumerate(self.extras):
             if p.grad is None:
                 continue                                  # torch.optim.AdamW skips parameters without a gradient
             if not (p.is_contiguous() and p.grad.is_contiguous() and p.dtype == torch.float32 and p.grad.dtype == torch.float32):
@@ -818,13 +823,14 @@ class FusedAdamW:
             if sync is not None and sync.enabled:
                 all_reduce_avg(p.grad)
             m, v = self._extra_moments(p)
-            items.append((p.data.view(-1), p.grad.view(-1), m, v))
+            item = (p.data.view(-1), p.grad.view(-1), m, v)
             if ema:
                 e = self._ema_of(id(p), p)
                 if id(p) in self._ema_unseeded:
                     e.copy_(p.data.view(-1))
                     self._ema_unseeded.discard(id(p))
-                items[-1] += (e,)
+                item += (e,)
+            items.append((j, item))
         return items
 
     def join(self):
@@ -958,24 +964,24 @@ class FusedAdamW:
         taken = {p.data_ptr() for g in self.groups for p in g['params']}
         return parts + [[x for x in items if ptr_of(x) not in taken]]
 
+    @staticmethod
+    def _slot_ptr(slot):
+        """the address of a slot's parameter"""
+        return slot[0].data_ptr() if slot[1] is None else slot[0].flat.data_ptr() + 4 * slot[1]
+
     def _slots(self, params=None):
         """[(tower, offset, numel, shape)] of the trainable parameters, in `params` order (default: tower order).  With parameter groups:
         group by group as torch numbers them, the declared groups first, then the default group in `params` order."""
         slots = self._slots_flat(params)
         if self.groups is None:
             return slots
-        return sum(self._partition(slots, lambda s: s[0].data_ptr() if s[1] is None else s[0].flat.data_ptr() + 4 * s[1]), [])
+        return sum(self._partition(slots, self._slot_ptr), [])
 
     def _slots_flat(self, params=None):
         where = {}
         for tw in self.towers:
-            if tw.flat is None:
-                continue
-            live = [p for p in tw._params() if p is not None]
-            rng = self._ranges(tw)
-            for p, off in zip(live, tw._offsets):
-                if any(a <= off < b for a, b in rng):        # the set captured at construction, not the live flags
-                    where[p.data_ptr()] = (tw, off, p.numel(), tuple(p.shape))
+            if tw.flat is not None:
+                where.update((p.data_ptr(), (tw, off, p.numel(), tuple(p.shape))) for p, off in self._owned(tw))
         for p in self.extras:
             where[p.data_ptr()] = (p, None, p.numel(), tuple(p.shape))
         if params is None:
@@ -985,8 +991,7 @@ class FusedAdamW:
             if p.data_ptr() not in where and not p.requires_grad:
                 continue
             if p.data_ptr() not in where:
-                if any(p.data_ptr() == q.data_ptr() for tw in self.towers if tw.flat is not None
-                       for q in tw._params() if q is not None):
+                if any(p.data_ptr() == q.data_ptr() for tw in self.towers if tw.flat is not None for q, _ in self._placed(tw)):
                     continue                                  # unfrozen after the optimizer was built: not one of its slots
                 raise ValueError('FusedAdamW.state_dict: a trainable parameter is not a view of a tower buffer')
             out.append(where[p.data_ptr()])
@@ -994,13 +999,7 @@ class FusedAdamW:
 
     def _trainable(self):
         """the parameters behind _slots(), in its order: tower by tower, extras last"""
-        out = []
-        for tw in self.towers:
-            if tw.flat is None:
-                continue
-            rng = self._ranges(tw)
-            out += [p for p, off in zip([p for p in tw._params() if p is not None], tw._offsets) if any(a <= off < b for a, b in rng)]
-        out += list(self.extras)
+        out = [p for tw in self.towers if tw.flat is not None for p, _ in self._owned(tw)] + list(self.extras)
         return out if self.groups is None else sum(self._partition(out, lambda p: p.data_ptr()), [])
 
     @property
@@ -1056,7 +1055,7 @@ class FusedAdamW:
         if self.groups is not None:
             # torch's multi-group layout: parameter ids count on from group to group (_slots() is in that order), lr_scale an extra key
             sd['param_groups'], at = [], 0
-            sizes = [len(part) for part in self._partition(slots, lambda s: s[0].data_ptr() if s[1] is None else s[0].flat.data_ptr() + 4 * s[1])]
+            sizes = [len(part) for part in self._partition(slots, self._slot_ptr)]
             for g, n in zip(self.groups + [{'lr_scale': 1.0, 'weight_decay': None}], sizes):
                 s, wd = g['lr_scale'], self.weight_decay if g['weight_decay'] is None else g['weight_decay']
                 sd['param_groups'].append(dict(group, lr=self.lr * s, initial_lr=self.base_lr * s, weight_decay=wd, lr_scale=s, params=list(range(at, at + n))))
@@ -1081,7 +1080,7 @@ class FusedAdamW:
                              f'({here - 1} declared in `groups` and the default group): build it with the groups the dict was saved with')
         group = saved[-1]                                    # the default group carries the optimizer's own lr and weight_decay
         if self.groups is not None:
-            sizes = [len(part) for part in self._partition(slots, lambda s: s[0].data_ptr() if s[1] is None else s[0].flat.data_ptr() + 4 * s[1])]
+            sizes = [len(part) for part in self._partition(slots, self._slot_ptr)]
             for i, (g, n) in enumerate(zip(saved, sizes)):
                 if len(g['params']) != n:
                     raise ValueError(f"FusedAdamW.load_state_dict: group {i} has {len(g['params'])} saved parameters, {n} here")
