@@ -4,19 +4,18 @@
 //   icl = (mean_i (lse_j A_ij - A_ii) + mean_i (lse_j C_ij - C_ii)) / 2 ; anchors are the student rows, the teacher has no gradient
 //   D = weight (softmax_rows(A) - I) / (2 B tau) ; G = D q^ ; d a_i = (G_i - a^_i (a^_i . G_i)) / |a_i|        (the same of b with C, p^)
 //
-// The structure is that of loss.hip's cross-modal passes on the pieces of sim_tiles.h, with ONE dot_tile per tile (there is no second
+// The stripe skeleton of loss_stripes.h (shared with loss.hip's cross-modal passes), with ONE dot_tile per tile (there is no second
 // logit matrix) and no atomics: four launches on the caller's stream,
 //   normalise  one wave per row of the four matrices: x / |x| (no epsilon), 1 / |x| of the student rows kept
 //   stripe A   (16 rows, direction, column slice): running (max, sum) of every row with the row's TRUE maximum, merged over lanes,
 //              waves (stripe_put / stripe_get) and written as one log-sum-exp per slice; the diagonal logit of every row
 //   stripe B   recomputes the tiles, forms D of the slice in LDS ([16][columns of the slice + 4] f32, at most 33 024 bytes) and
-//              multiplies it with the teacher rows on the f32 MFMA: one partial gradient row per slice, plain stores.  Slice 0 leaves
-//              one record per stripe: sum over its rows of (lse - diagonal)
-//   close      adds the slices' partial rows in slice order, does the normalisation backward; one extra workgroup adds the stripe
-//              records in a fixed tree and writes the four scalars
+//              multiplies it with the teacher rows (stripe_times_rows): one partial gradient row per slice, plain stores.  Slice 0
+//              leaves one record per stripe: sum over its rows of (lse - diagonal)
+//   close      stripe_close_row (the slices' partial rows in slice order, the normalisation backward); one extra workgroup adds the
+//              stripe records in a fixed tree and writes the four scalars
 // Every store has one writer and every sum a fixed shape: the same call gives the same bits.
-#include "sim_tiles.h"
-#include <math.h>
+#include "loss_stripes.h"
 
 namespace {
 
@@ -24,6 +23,7 @@ constexpr int ICL_MAX_B = 4096, ICL_MAX_E = 1024;
 constexpr int ICL_MAX_SLICES = 8;
 constexpr int ICL_LDS_COLS = 512;             // columns of a slice that stripe B holds in LDS: 16 x (512 + 4) f32 = 33 024 bytes
 constexpr int ICL_MAX_STRIPES = ICL_MAX_B / 16;   // = the threads of the workgroup that adds the stripe records
+static_assert(ICL_MAX_SLICES == STRIPE_MAX_SLICES && ICL_MAX_E == STRIPE_MAX_E, "the shared skeleton's limits");
 
 struct IclArgs {
     const float* src[4];                      // s_img, s_txt, t_img, t_txt
@@ -39,27 +39,6 @@ struct IclArgs {
     float itau, k, weight;                    // 1 / tau ; weight / (2 B tau)
 };
 
-// running softmax statistic of one lane: maximum m and sum l of exp(x - m) over the values seen so far.  A NaN logit makes l NaN
-// (fmaxf drops it from m) and lse() hands it on.
-struct IclRun {
-    float m = -INFINITY, l = 0.f;
-    __device__ __forceinline__ void add(float x) {
-        const float mn = fmaxf(m, x);
-        l = l * __expf(m - mn) + __expf(x - mn);
-        m = mn;
-    }
-    __device__ __forceinline__ float lse() const { return l == 0.f ? -INFINITY : m + __logf(l); }
-};
-
-// log(exp(a) + exp(b)); -inf stands for an empty sum, a NaN on either side gives NaN
-struct IclLogAddExp {
-    __device__ __forceinline__ float operator()(float a, float b) const {
-        if (a == -INFINITY && b == -INFINITY) return a;
-        const float m = fmaxf(a, b);
-        return m + __logf(__expf(a - m) + __expf(b - m));
-    }
-};
-
 // dot product / tau, rounded HERE: without the barrier the compiler contracts the product into the subtraction that follows it
 // (x - max in stripe A, x - lse in stripe B), and the two passes would see different logits (B = 1 would not give P = 1 exactly)
 __device__ __forceinline__ float icl_logit(float s, float itau) {
@@ -73,20 +52,7 @@ __global__ __launch_bounds__(256) void icl_normalize_kernel(IclArgs a) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), mat = blockIdx.y;
     if (b >= a.B) return;
-    const int E = a.E;
-    const float* src = a.src[mat] + (int64_t)b * E;
-    float* dst = a.nrm[mat] + (int64_t)b * E;
-    float s = 0.f;
-    for (int c = lane * 4; c < E; c += 256) {
-        const float4 v = *(const float4*)(src + c);
-        s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-    }
-    s = wave_sum(s);
-    const float inv = 1.f / sqrtf(s);
-    for (int c = lane * 4; c < E; c += 256) {
-        const float4 v = *(const float4*)(src + c);
-        *(float4*)(dst + c) = float4{v.x * inv, v.y * inv, v.z * inv, v.w * inv};
-    }
+    const float inv = normalize_row<false>(a.src[mat] + (int64_t)b * a.E, a.nrm[mat] + (int64_t)b * a.E, a.E, lane);
     if (mat < 2 && lane == 0) a.inv[mat][b] = inv;
 }
 
@@ -99,10 +65,10 @@ __global__ __launch_bounds__(256) void icl_stripe_a_kernel(IclArgs a) {
     const int i0 = blockIdx.x * 16;
     const float* sa = a.nrm[dir], *tb = a.nrm[3 - dir];            // student rows / teacher columns of the other modality
     const int64_t ia = (int64_t)min(i0 + (lane & 15), B - 1) * E;  // this lane's row of the panel, clamped inside the matrix
-    IclRun run[4];
-    const int ntile = (B + 15) / 16;
-    const int z = blockIdx.z, t0 = (int)((int64_t)ntile * z / a.zs), t1 = (int)((int64_t)ntile * (z + 1) / a.zs);
-    for (int jt = t0 + wave; jt < t1; jt += 4) {
+    RunLse run[4];
+    const int z = blockIdx.z;
+    const StripeSlice sl = stripe_slice(B, a.zs, z);
+    for (int jt = sl.t0 + wave; jt < sl.t1; jt += 4) {
         const int col = jt * 16 + (lane & 15);
         const int64_t jb = (int64_t)min(col, B - 1) * E;
         const f32x4 S = dot_tile(sa + ia, tb + jb, E, lane);
@@ -119,17 +85,15 @@ __global__ __launch_bounds__(256) void icl_stripe_a_kernel(IclArgs a) {
     float v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) v[q] = run[q].lse();
-    stripe_put(red, v, lane, wave, IclLogAddExp{});
+    stripe_put(red, v, lane, wave, LogAddExp{});
     __syncthreads();
     if (threadIdx.x < 16 && i0 + threadIdx.x < B)
-        a.stats[((int64_t)z * 2 + dir) * B + i0 + threadIdx.x] = stripe_get(red, threadIdx.x, IclLogAddExp{});
+        a.stats[((int64_t)z * 2 + dir) * B + i0 + threadIdx.x] = stripe_get(red, threadIdx.x, LogAddExp{});
 }
 
-// log-sum-exp of row `row` of direction `dir`: the slices' partials merged in slice order
+// log-sum-exp of row `row` of direction `dir`
 __device__ __forceinline__ float icl_row_lse(const IclArgs& a, int dir, int row) {
-    float v = -INFINITY;
-    for (int zz = 0; zz < a.zs; ++zz) v = IclLogAddExp{}(v, a.stats[((int64_t)zz * 2 + dir) * a.B + row]);
-    return v;
+    return slices_lse(a.stats + (int64_t)dir * a.B + row, (int64_t)2 * a.B, a.zs);
 }
 
 __global__ __launch_bounds__(256) void icl_stripe_b_kernel(IclArgs a) {
@@ -137,16 +101,16 @@ __global__ __launch_bounds__(256) void icl_stripe_b_kernel(IclArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int dir = blockIdx.y;
     const int B = a.B, E = a.E;
-    const int ntile = (B + 15) / 16;
-    const int ldl = ((ntile + a.zs - 1) / a.zs) * 16 + 4;         // the LDS stripe holds this slice's columns only
+    const int ldl = stripe_ldl(B, a.zs);                          // the LDS stripe holds this slice's columns only
     const int i0 = blockIdx.x * 16;
     const float* sa = a.nrm[dir], *tb = a.nrm[3 - dir];
     const int64_t ia = (int64_t)min(i0 + (lane & 15), B - 1) * E;
     float rr[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) rr[q] = icl_row_lse(a, dir, min(i0 + (lane >> 4) * 4 + q, B - 1));
-    const int z = blockIdx.z, t0 = (int)((int64_t)ntile * z / a.zs), t1 = (int)((int64_t)ntile * (z + 1) / a.zs);
-    for (int jt = t0 + wave; jt < t1; jt += 4) {
+    const int z = blockIdx.z;
+    const StripeSlice sl = stripe_slice(B, a.zs, z);
+    for (int jt = sl.t0 + wave; jt < sl.t1; jt += 4) {
         const int col = jt * 16 + (lane & 15);
         const int64_t jb = (int64_t)min(col, B - 1) * E;
         const f32x4 S = dot_tile(sa + ia, tb + jb, E, lane);
@@ -155,7 +119,7 @@ __global__ __launch_bounds__(256) void icl_stripe_b_kernel(IclArgs a) {
             const int rl = (lane >> 4) * 4 + q, row = i0 + rl;
             float d = 0.f;
             if (row < B && col < B) d = a.k * (__expf(icl_logit(S[q], a.itau) - rr[q]) - (row == col ? 1.f : 0.f));
-            dsl[rl * ldl + col - t0 * 16] = d;
+            dsl[rl * ldl + col - sl.t0 * 16] = d;
         }
     }
     // the stripe's record of the scalar: sum over its rows of (lse - diagonal), a fixed tree over 16 lanes
@@ -166,67 +130,8 @@ __global__ __launch_bounds__(256) void icl_stripe_b_kernel(IclArgs a) {
         if (lane == 0) a.rec[dir * gridDim.x + blockIdx.x] = v;
     }
     __syncthreads();
-    // partial gradient rows: G[16, E] = D_stripe[16, columns of the slice] @ Y[columns, E],  Y = normalised teacher rows
-    const float* Y = tb;
-    float* G = a.dsh[dir] + (int64_t)z * B * E;
-    const float* arow = dsl + (lane & 15) * ldl + (lane >> 4) * 4;
-    for (int e0 = wave * 16; e0 < E; e0 += 64) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        const float* yb = Y + e0 + (lane & 15);
-        for (int o = 0; o < (t1 - t0) * 16; o += 16) {
-            const float4 av = *(const float4*)(arow + o);
-            const int k0 = t0 * 16 + o + (lane >> 4) * 4;
-            // columns beyond B carry zero weights in dsl; clamp the address only
-            const float b0 = yb[(int64_t)min(k0 + 0, B - 1) * E], b1 = yb[(int64_t)min(k0 + 1, B - 1) * E];
-            const float b2 = yb[(int64_t)min(k0 + 2, B - 1) * E], b3 = yb[(int64_t)min(k0 + 3, B - 1) * E];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, b0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, b1, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, b2, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, b3, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = i0 + (lane >> 4) * 4 + q;
-            if (row < B) G[(int64_t)row * E + e0 + (lane & 15)] = acc[q];
-        }
-    }
-}
-
-// normalisation backward of row b of tower `tow` by one wave: g = the slices' partial rows added in slice order,
-// d x = (g - x^ (x^ . g)) / |x|
-__device__ __forceinline__ void icl_close_row(const IclArgs& a, int tow, int b, int lane) {
-    const int E = a.E;
-    const float* xh = a.nrm[tow] + (int64_t)b * E;
-    const float* g = a.dsh[tow] + (int64_t)b * E;
-    float* d = a.ds[tow] + (int64_t)b * E;
-    const int64_t zstride = (int64_t)a.B * E;
-    float4 y[ICL_MAX_E / 256];
-    float dot = 0.f;
-#pragma unroll
-    for (int i = 0; i < ICL_MAX_E / 256; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        y[i] = float4{0.f, 0.f, 0.f, 0.f};
-        if (c < E) {
-            y[i] = *(const float4*)(g + c);
-            for (int zz = 1; zz < a.zs; ++zz) {
-                const float4 p = *(const float4*)(g + zz * zstride + c);
-                y[i].x += p.x; y[i].y += p.y; y[i].z += p.z; y[i].w += p.w;
-            }
-            const float4 x = *(const float4*)(xh + c);
-            dot += (x.x * y[i].x + x.y * y[i].y) + (x.z * y[i].z + x.w * y[i].w);
-        }
-    }
-    dot = wave_sum(dot);
-    const float inv = a.inv[tow][b];
-#pragma unroll
-    for (int i = 0; i < ICL_MAX_E / 256; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < E) {
-            const float4 x = *(const float4*)(xh + c);
-            *(float4*)(d + c) = float4{(y[i].x - x.x * dot) * inv, (y[i].y - x.y * dot) * inv,
-                                       (y[i].z - x.z * dot) * inv, (y[i].w - x.w * dot) * inv};
-        }
-    }
+    // partial gradient rows of the slice against Y = the normalised teacher rows
+    stripe_times_rows(dsl, ldl, tb, sl, B, E, a.dsh[dir] + (int64_t)z * B * E, i0, 0, B, lane, wave);
 }
 
 // grid = ceil(B / 4) + 1: one wave per row, both towers; the extra last workgroup adds the stripe records (thread t holds record t,
@@ -251,28 +156,22 @@ __global__ __launch_bounds__(256) void icl_close_kernel(IclArgs a) {
     }
     const int b = blockIdx.x * 4 + wave;
     if (b >= a.B) return;
-    icl_close_row(a, 0, b, lane);
-    icl_close_row(a, 1, b, lane);
+    const int64_t row = (int64_t)b * a.E, zstride = (int64_t)a.B * a.E;
+#pragma unroll
+    for (int tow = 0; tow < 2; ++tow)
+        stripe_close_row<false>(a.nrm[tow] + row, a.dsh[tow] + row, zstride, a.zs, a.inv[tow][b], a.ds[tow] + row, a.E, lane);
 }
 
 bool icl_shape_ok(int64_t B, int64_t E) { return B >= 1 && B <= ICL_MAX_B && E >= 16 && E <= ICL_MAX_E && E % 16 == 0; }
 
-// column slices: loss.hip's rule (enough workgroups for the chip from the row stripes, at most 8, at most one per column tile), then
-// as many more as keep a slice within ICL_LDS_COLS columns
-int icl_slices(int64_t B) {
-    const int tiles = (int)((B + 15) / 16);
-    int zs = 256 / (2 * tiles);
-    zs = zs < 1 ? 1 : (zs > ICL_MAX_SLICES ? ICL_MAX_SLICES : zs);
-    zs = zs > tiles ? tiles : zs;
-    while (zs < ICL_MAX_SLICES && ((tiles + zs - 1) / zs) * 16 > ICL_LDS_COLS) ++zs;
-    return zs;
-}
+// column slices: every call owns all rows, and a slice stays within ICL_LDS_COLS columns
+int icl_slices(int64_t B) { return stripe_slices(stripe_tiles(B), stripe_tiles(B), ICL_LDS_COLS); }
 
 // carves the workspace (a null base only counts)
 size_t icl_carve(IclArgs& a, void* base, int64_t B, int64_t E) {
     Bump w(base);
     const int zs = icl_slices(B);
-    const size_t stripes = (size_t)((B + 15) / 16);
+    const size_t stripes = (size_t)stripe_tiles(B);
     for (int i = 0; i < 4; ++i) a.nrm[i] = w.take<float>((size_t)B * E);
     for (int i = 0; i < 2; ++i) a.dsh[i] = w.take<float>((size_t)zs * B * E);
     a.inv[0] = w.take<float>((size_t)B); a.inv[1] = w.take<float>((size_t)B);
@@ -316,9 +215,8 @@ extern "C" int dclip_interactive_loss(const float* s_img, const float* t_img, co
     hipStream_t st = (hipStream_t)stream;
     // algorithmic HBM bytes: read 4 B E 4, write 2 B E 4; the logits contribute none
     TraceScope tr(DCLIP_TRACE_LOSS, 0.0, 6.0 * (double)B * E * 4.0, stream);
-    const unsigned stripes = (unsigned)((B + 15) / 16);
-    const int cols = (((int)stripes + a.zs - 1) / a.zs) * 16;
-    const size_t lds = (size_t)16 * (cols + 4) * sizeof(float);
+    const unsigned stripes = (unsigned)stripe_tiles(B);
+    const size_t lds = stripe_lds_bytes(a.B, a.zs);
     hipLaunchKernelGGL(icl_normalize_kernel, dim3((unsigned)((B + 3) / 4), 4), dim3(256), 0, st, a);
     hipLaunchKernelGGL(icl_stripe_a_kernel, dim3(stripes, 2, (unsigned)a.zs), dim3(256), 0, st, a);
     hipLaunchKernelGGL(icl_stripe_b_kernel, dim3(stripes, 2, (unsigned)a.zs), dim3(256), lds, st, a);

@@ -14,8 +14,9 @@
 // Every softmax statistic is a natural-log log-sum-exp with the row's true maximum: a running (max, sum) per lane while pass A walks
 // its column tiles, merged across lanes, waves and column slices with the usual rescale (slices in order: deterministic).  A fixed
 // maximum of 1 / tau (cosines are bounded by 1) would underflow the whole row sum once the row's largest cosine sits ~87 tau below 1.
-#include "sim_tiles.h"
-#include <math.h>
+// The stripe skeleton (running log-sum-exp and its merges, slice geometry, the stripe product, the closing row) is loss_stripes.h,
+// shared with interactive.hip; the kernels here hold the terms.  A NaN logit makes its row's and column's statistics NaN.
+#include "loss_stripes.h"
 #include <stdlib.h>
 
 namespace {
@@ -177,33 +178,9 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
 // C layout: acc[q] = X[row 4*g + q][col l & 15].
 // -------------------------------------------------------------------------------------------------------------
 
-// log(exp(a) + exp(b)); -inf stands for an empty sum
-__device__ __forceinline__ float log_add_exp(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m == -INFINITY ? m : m + __logf(__expf(a - m) + __expf(b - m));
-}
-
-// running softmax statistic of one lane: maximum m and sum l of exp(x - m) over the values seen so far
-struct RunLse {
-    float m = -INFINITY, l = 0.f;
-    __device__ __forceinline__ void add(float x) {
-        const float mn = fmaxf(m, x);
-        l = l * __expf(m - mn) + __expf(x - mn);
-        m = mn;
-    }
-    __device__ __forceinline__ float lse() const { return l > 0.f ? m + __logf(l) : -INFINITY; }
-};
-
-__device__ __forceinline__ float rowgroup_lse(const RunLse& r) {   // log-sum-exp over the 16 lanes that share l >> 4
-    float v = r.lse();
-    v = log_add_exp(v, __shfl_xor(v, 1)); v = log_add_exp(v, __shfl_xor(v, 2));
-    v = log_add_exp(v, __shfl_xor(v, 4)); v = log_add_exp(v, __shfl_xor(v, 8));
-    return v;
-}
-
-// grid = (ceil(B/16), 2 directions)
+// grid = (ceil(Bl/16), 2 directions, column slices)
 __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
-    __shared__ float red[4][16][3];
+    __shared__ float red[3][4][16];                               // log-sum-exps of S, S / tau, T / tau
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int dir = blockIdx.y;
     const int B = a.B, E = a.E;
@@ -214,9 +191,9 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
     const int64_t ia = (int64_t)min(i0 + (lane & 15), B - 1) * E;   // this lane's row of the panel, clamped inside the matrix
     RunLse r1[4], rs[4], rt[4];
     float pos = 0.f, neg = 0.f, mse = 0.f, diag = 0.f;
-    const int ntile = (B + 15) / 16;
-    const int z = blockIdx.z, t0 = (int)((int64_t)ntile * z / a.zs), t1 = (int)((int64_t)ntile * (z + 1) / a.zs);   // this slice's column tiles
-    for (int jt = t0 + wave; jt < t1; jt += 4) {
+    const int z = blockIdx.z;
+    const StripeSlice sl = stripe_slice(B, a.zs, z);              // this slice's column tiles
+    for (int jt = sl.t0 + wave; jt < sl.t1; jt += 4) {
         const int j0 = jt * 16;
         const int col = j0 + (lane & 15);
         const int64_t jb = (int64_t)min(col, B - 1) * E;
@@ -237,13 +214,12 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
             }
         }
     }
+    float v1[4], vs[4], vt[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float x = rowgroup_lse(r1[q]), y = rowgroup_lse(rs[q]), z = rowgroup_lse(rt[q]);
-        if ((lane & 15) == 0) {
-            red[wave][(lane >> 4) * 4 + q][0] = x; red[wave][(lane >> 4) * 4 + q][1] = y; red[wave][(lane >> 4) * 4 + q][2] = z;
-        }
-    }
+    for (int q = 0; q < 4; ++q) { v1[q] = r1[q].lse(); vs[q] = rs[q].lse(); vt[q] = rt[q].lse(); }
+    stripe_put(red[0], v1, lane, wave, LogAddExp{});
+    stripe_put(red[1], vs, lane, wave, LogAddExp{});
+    stripe_put(red[2], vt, lane, wave, LogAddExp{});
     if (dir == 0) {
         pos = wave_sum(pos); neg = wave_sum(neg); mse = wave_sum(mse); diag = wave_sum(diag);
         if (lane == 0) {
@@ -255,49 +231,16 @@ __global__ __launch_bounds__(256) void loss_stripe_a_kernel(LossArgs a) {
     __syncthreads();
     if (threadIdx.x < 48) {
         const int r = threadIdx.x % 16, k = threadIdx.x / 16;
-        if (i0 + r < iend) {
-            const float v = log_add_exp(log_add_exp(red[0][r][k], red[1][r][k]), log_add_exp(red[2][r][k], red[3][r][k]));
-            a.stats[((int64_t)z * 6 + dir * 3 + k) * a.Bl + i0 - a.r0 + r] = v;
-        }
-    }
-}
-
-// normalisation backward of one owned row (local index b) of tower `tow`, by one wave:  x_hat = x / |x|  =>
-// dx = (g - x_hat (x_hat . g)) / |x|, added to the tower-term gradient.  g = the column slices' partial rows, added in slice order.
-__device__ __forceinline__ void loss_finalize_row(const LossArgs& a, int tow, int b, int lane) {
-    const float* xh = a.nrm[tow] + (int64_t)(a.r0 + b) * a.E;
-    float* g = a.dsh[tow] + (int64_t)b * a.E;
-    const int64_t zstride = (int64_t)a.Bl * a.E;
-    float dot = 0.f;
-    for (int c = lane * 4; c < a.E; c += 256) {
-        float4 y = *(const float4*)(g + c);
-        for (int zz = 1; zz < a.zs; ++zz) {                     // slice order: deterministic
-            const float4 p = *(const float4*)(g + zz * zstride + c);
-            y.x += p.x; y.y += p.y; y.z += p.z; y.w += p.w;
-        }
-        *(float4*)(g + c) = y;                                  // slice 0 now holds the complete row
-        const float4 x = *(const float4*)(xh + c);
-        dot += (x.x * y.x + x.y * y.y) + (x.z * y.z + x.w * y.w);
-    }
-    dot = wave_sum(dot);
-    const float inv = a.inv[tow][b];
-    float* d = a.ds[tow] + (int64_t)b * a.E;
-    for (int c = lane * 4; c < a.E; c += 256) {
-        const float4 x = *(const float4*)(xh + c), y = *(const float4*)(g + c);
-        float4 o = *(const float4*)(d + c);
-        o.x += (y.x - x.x * dot) * inv; o.y += (y.y - x.y * dot) * inv;
-        o.z += (y.z - x.z * dot) * inv; o.w += (y.w - x.w * dot) * inv;
-        *(float4*)(d + c) = o;
+        if (i0 + r < iend) a.stats[((int64_t)z * 6 + dir * 3 + k) * a.Bl + i0 - a.r0 + r] = stripe_get(red[k], r, LogAddExp{});
     }
 }
 
 __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float dsl[];   // [16][B16 + 4]
+    extern __shared__ __attribute__((aligned(16))) float dsl[];   // [16][ldl]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int dir = blockIdx.y;
     const int B = a.B, E = a.E;
-    const int ntile = (B + 15) / 16;
-    const int ldl = ((ntile + a.zs - 1) / a.zs) * 16 + 4;       // the LDS stripe holds this slice's columns only
+    const int ldl = stripe_ldl(B, a.zs);                        // the LDS stripe holds this slice's columns only
     const int i0 = a.r0 + blockIdx.x * 16, iend = a.r0 + a.Bl;   // owned rows (global indices)
     const int Bl = a.Bl;
     const float* sa = a.nrm[dir], *sb = a.nrm[1 - dir];
@@ -308,11 +251,7 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
     const float* rst = a.stats + (int64_t)dir * 3 * Bl;
     const float* cst = a.stats + (int64_t)(1 - dir) * 3 * Bl;
     // the row / column log-sum-exps arrive as one partial per column slice of pass A: merged in slice order (deterministic)
-    auto stat = [&](const float* base, int idx) {
-        float v = -INFINITY;
-        for (int zz = 0; zz < a.zs; ++zz) v = log_add_exp(v, base[(int64_t)zz * 6 * Bl + idx]);
-        return v;
-    };
+    auto stat = [&](const float* base, int idx) { return slices_lse(base + idx, (int64_t)6 * Bl, a.zs); };
     // with gathered statistics: row k of direction d is a.gstats[(d * 3 + k) * B + global index]
     const float* grow = a.gstats ? a.gstats + (int64_t)dir * 3 * B : nullptr;
     const float* gcol = a.gstats ? a.gstats + (int64_t)(1 - dir) * 3 * B : nullptr;
@@ -324,13 +263,14 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
         if (grow) { rr1[q] = grow[a.r0 + row]; rrs[q] = grow[B + a.r0 + row]; rrt[q] = grow[2 * B + a.r0 + row]; }
         else { rr1[q] = stat(rst, row); rrs[q] = stat(rst, Bl + row); rrt[q] = stat(rst, 2 * Bl + row); }
     }
-    const int z = blockIdx.z, t0 = (int)((int64_t)ntile * z / a.zs), t1 = (int)((int64_t)ntile * (z + 1) / a.zs);
+    const int z = blockIdx.z;
+    const StripeSlice sl = stripe_slice(B, a.zs, z);
     const float k_cd_pos = a.c.w_cd / B, k_cd_neg = B > 1 ? a.c.w_cd / ((float)B * (B - 1)) : 0.f;
     const float k_mse = a.c.w_mse * 2.f / ((float)B * B);
     const float k_hl = a.c.w_hl * 0.5f / B;
     const float k_sl = a.c.w_sl * 0.5f * tau;
     float klacc = 0.f;
-    for (int jt = t0 + wave; jt < t1; jt += 4) {
+    for (int jt = sl.t0 + wave; jt < sl.t1; jt += 4) {
         const int j0 = jt * 16;
         const int col = j0 + (lane & 15);
         const int64_t jb = (int64_t)min(col, B - 1) * E;
@@ -360,7 +300,7 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
                     klacc += pt * (lpt - lps);
                 }
             }
-            dsl[rl * ldl + col - t0 * 16] = d;
+            dsl[rl * ldl + col - sl.t0 * 16] = d;
         }
     }
     if (a.c.w_sl != 0.f) {
@@ -370,40 +310,16 @@ __global__ __launch_bounds__(256) void loss_stripe_b_kernel(LossArgs a) {
     if (a.c.w_hl != 0.f && z == 0 && wave == 0 && lane < 16 && i0 + lane < iend)
         unsafeAtomicAdd(scal_slot(a) + (dir ? SC_LSE1 : SC_LSE0), grow ? grow[i0 + lane] : stat(rst, i0 - a.r0 + lane));
     __syncthreads();
-    // gradient rows: G[16, E] = dS_stripe[16, B] @ Y[B, E],  Y = normalised student embedding of the other modality
-    // (this slice's columns only: the slices' partial rows are added by the stripe's last-arriving slice, loss_finalize_row)
-    const float* Y = sb;
-    float* G = a.dsh[dir] + (int64_t)z * Bl * E;
-    const float* arow = dsl + (lane & 15) * ldl + (lane >> 4) * 4;
-    for (int e0 = wave * 16; e0 < E; e0 += 64) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        const float* yb = Y + e0 + (lane & 15);
-        for (int o = 0; o < (t1 - t0) * 16; o += 16) {
-            const float4 av = *(const float4*)(arow + o);
-            const int k0 = t0 * 16 + o + (lane >> 4) * 4;
-            // rows beyond B carry zero weights in dsl; clamp the address only
-            const float b0 = yb[(int64_t)min(k0 + 0, B - 1) * E], b1 = yb[(int64_t)min(k0 + 1, B - 1) * E];
-            const float b2 = yb[(int64_t)min(k0 + 2, B - 1) * E], b3 = yb[(int64_t)min(k0 + 3, B - 1) * E];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, b0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, b1, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, b2, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, b3, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = i0 + (lane >> 4) * 4 + q;
-            if (row < iend) G[(int64_t)(row - a.r0) * E + e0 + (lane & 15)] = acc[q];
-        }
-    }
+    // partial gradient rows of the owned rows against Y = the normalised student embedding of the other modality (this slice's columns
+    // only: loss_finalize_kernel adds the slices' rows)
+    stripe_times_rows(dsl, ldl, sb, sl, B, E, a.dsh[dir] + (int64_t)z * Bl * E, i0, a.r0, iend, lane, wave);
 }
 
 // pass-A-only call of the row-block mode: the owned rows' log-sum-exps, slices merged in order, for the caller's all-gather
 __global__ void loss_stats_out_kernel(LossArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 6 * a.Bl) return;
-    float v = -INFINITY;
-    for (int zz = 0; zz < a.zs; ++zz) v = log_add_exp(v, a.stats[(int64_t)zz * 6 * a.Bl + i]);
-    a.stats_out[i] = v;
+    a.stats_out[i] = slices_lse(a.stats + i, (int64_t)6 * a.Bl, a.zs);
 }
 
 // out[0] total ; [1..4] image l1,cos,kl,ce ; [5..8] text ; [9..12] cos_diff, hard_label, soft_label, logits_mse (raw)
@@ -444,24 +360,42 @@ __device__ void loss_write_total(const LossArgs& a) {
     for (int i = 0; i < 16; ++i) a.out[i] = o[i];
 }
 
-// default path: the normalisation backward of every owned row (one wave each) as a launch of its own; the extra last workgroup writes
-// the 16 scalars (they depend on the earlier launches only, not on this one)
+// default path: the normalisation backward of every owned row (one wave each: stripe_close_row, added onto the tower-term gradient that
+// loss_rows_kernel left) as a launch of its own; the extra last workgroup writes the 16 scalars (they depend on the earlier launches
+// only, not on this one)
 __global__ __launch_bounds__(256) void loss_finalize_kernel(LossArgs a) {
     if (blockIdx.x == gridDim.x - 1) { loss_write_total(a); return; }
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);          // owned row (local index)
     if (b >= a.Bl) return;
-    loss_finalize_row(a, 0, b, lane);
-    loss_finalize_row(a, 1, b, lane);
+    const int64_t row = (int64_t)b * a.E, zstride = (int64_t)a.Bl * a.E;
+#pragma unroll
+    for (int tow = 0; tow < 2; ++tow)
+        stripe_close_row<true>(a.nrm[tow] + (int64_t)(a.r0 + b) * a.E, a.dsh[tow] + row, zstride, a.zs, a.inv[tow][b], a.ds[tow] + row, a.E, lane);
 }
 __global__ __launch_bounds__(64) void loss_total_kernel(LossArgs a) { loss_write_total(a); }
+
+// a slice of stripe B stays within this many columns: an LDS stripe [16][columns + 4] f32 of at most 144 KiB
+constexpr int LOSS_LDS_COLS = 144 * 1024 / (16 * (int)sizeof(float)) - 4;
+
+// carves the workspace of a call that owns `rows` rows and runs zs column slices (a null base only counts)
+size_t loss_carve(LossArgs& a, void* base, int64_t B, int64_t E, int64_t rows, int zs) {
+    Bump w(base);
+    const size_t be = dclip_up256((size_t)B * E * sizeof(float));
+    for (int i = 0; i < 4; ++i) a.nrm[i] = w.take<float>((size_t)B * E);
+    for (int i = 0; i < 2; ++i) a.dsh[i] = (float*)w.take<char>(zs * be);       // one padded [B, E] per slice
+    a.inv[0] = w.take<float>((size_t)2 * B); a.inv[1] = a.inv[0] + rows;
+    a.stats = w.take<float>((size_t)zs * 6 * B);
+    a.scal = w.take<float>(NREP * SCSTRIDE);
+    a.zs = zs;
+    return w.off;
+}
 
 }  // namespace
 
 extern "C" size_t dclip_distill_loss_workspace(int64_t B, int64_t E) {
-    const size_t be = dclip_up256((size_t)B * E * sizeof(float));
-    const size_t zs = 8;                                     // upper bound of the column slices for any row block
-    return (4 + 2 * zs) * be + dclip_up256((size_t)2 * B * 4) + dclip_up256(zs * 6 * B * 4) + dclip_up256((size_t)NREP * SCSTRIDE * 4);
+    LossArgs a;
+    return loss_carve(a, nullptr, B, E, B, STRIPE_MAX_SLICES);   // the upper bound of the column slices for any row block
 }
 
 namespace {
@@ -492,22 +426,7 @@ int run_distill_loss(const float* s_img, const float* t_img, const float* s_txt,
     DCLIP_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", who);
     a.s[0] = s_img; a.s[1] = s_txt; a.t[0] = t_img; a.t[1] = t_txt; a.ds[0] = d_s_img; a.ds[1] = d_s_txt;
     a.B = (int)B; a.E = (int)E; a.r0 = (int)row0; a.Bl = (int)rows; a.out = out_scalars;
-    Bump w(workspace);
-    for (int i = 0; i < 4; ++i) a.nrm[i] = w.take<float>(B * E);
-    // column slices: enough workgroups for the chip from the owned row stripes
-    {
-        const int rtile = (int)((rows + 15) / 16), ctile = (int)((B + 15) / 16);
-        int zs = 256 / (2 * rtile);
-        zs = zs < 1 ? 1 : (zs > 8 ? 8 : zs);
-        zs = zs > ctile ? ctile : zs;
-        while (zs < 8 && (size_t)16 * (((ctile + zs - 1) / zs) * 16 + 4) * sizeof(float) > 144 * 1024) ++zs;   // LDS stripe budget
-        a.zs = zs;
-    }
-    const size_t be = dclip_up256((size_t)B * E * sizeof(float));
-    for (int i = 0; i < 2; ++i) a.dsh[i] = (float*)w.take<char>(a.zs * be);     // one padded [B, E] per slice
-    a.inv[0] = w.take<float>(2 * B); a.inv[1] = a.inv[0] + rows;
-    a.stats = w.take<float>((size_t)a.zs * 6 * B);
-    a.scal = w.take<float>(NREP * SCSTRIDE);
+    loss_carve(a, workspace, B, E, rows, stripe_slices(stripe_tiles(rows), stripe_tiles(B), LOSS_LDS_COLS));
     hipStream_t st = (hipStream_t)stream;
     // algorithmic HBM bytes: read 4*B*E*4 + write 2*rows*E*4 ; the logits contribute none
     TraceScope tr(DCLIP_TRACE_LOSS, 0.0, (a.c.two_tower ? 2.0 : 1.0) * (2.0 * (double)B + (double)rows) * E * 4.0, stream);
@@ -532,7 +451,7 @@ int run_distill_loss(const float* s_img, const float* t_img, const float* s_txt,
             hipLaunchKernelGGL(loss_stats_out_kernel, dim3((unsigned)((6 * rows + 255) / 256)), dim3(256), 0, st, a);
             return dclip_check_launch(who);
         }
-        const size_t lds = (size_t)16 * (((((B + 15) / 16) + a.zs - 1) / a.zs) * 16 + 4) * sizeof(float);
+        const size_t lds = stripe_lds_bytes(a.B, a.zs);
         DCLIP_REQUIRE(lds <= 160 * 1024, "%s: stripe does not fit LDS", who);
         hipLaunchKernelGGL(loss_stripe_b_kernel, grid, dim3(256), lds, st, a);
         hipLaunchKernelGGL(loss_finalize_kernel, dim3((unsigned)((rows + 3) / 4) + 1), dim3(256), 0, st, a);

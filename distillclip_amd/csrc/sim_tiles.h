@@ -1,5 +1,6 @@
-// Device pieces shared by the embedding-side kernels (loss.hip, metrics.hip, recall.hip): the 16 x 16 tile of dot products on the
-// exact-f32 MFMA, its diagonal, the reduction of a 16-row stripe over the four waves of a workgroup, and the row normaliser.
+// Device pieces shared by the embedding-side kernels (metrics.hip, recall.hip, topk.hip, and through loss_stripes.h loss.hip and
+// interactive.hip): the 16 x 16 tile of dot products on the exact-f32 MFMA, its diagonal, the reduction of a 16-row stripe over the four
+// waves of a workgroup, and the row normaliser.
 #pragma once
 #include "common.h"
 
@@ -55,8 +56,9 @@ __device__ __forceinline__ T stripe_get(T (*red)[16], int r, Op op) {
 
 // x / |x| of one row by one wave.  ZERO_SAFE = false: no epsilon and 1 / sqrt(0) on a zero row, as the reference's validation
 // metrics; true: a row whose squared norm is 0 (or not a positive finite number) becomes the zero row, so every cosine with it is 0.
+// Returns the scale it applied, 1 / |x| (every lane holds it).
 template <bool ZERO_SAFE>
-__device__ __forceinline__ void normalize_row(const float* src, float* dst, int E, int lane) {
+__device__ __forceinline__ float normalize_row(const float* src, float* dst, int E, int lane) {
     float s = 0.f;
     for (int c = lane * 4; c < E; c += 256) {
         const float4 v = *(const float4*)(src + c);
@@ -68,4 +70,5 @@ __device__ __forceinline__ void normalize_row(const float* src, float* dst, int 
         const float4 v = *(const float4*)(src + c);
         *(float4*)(dst + c) = float4{v.x * inv, v.y * inv, v.z * inv, v.w * inv};
     }
+    return inv;
 }

@@ -154,6 +154,23 @@ def test_row_blocks_with_gathered_statistics(B, world):
     assert _rel(di.cpu(), ogi) < 2e-4 and _rel(dt.cpu(), ogt) < 2e-4
 
 
+def test_a_nan_in_a_student_row_reaches_the_total_and_every_gradient_it_touches():
+    """One NaN element in one student image row, all eight terms on: the total is NaN, that row of d_s_img is NaN throughout (its own
+    normalisation), and no element of d_s_txt is finite (the row is a column of every text row's logits: its hard_label / soft_label
+    statistics and the stripe product carry it).  The log-sum-exp merges of csrc/loss_stripes.h hand a NaN on (the `loss_*` row; before the shared header these gradients were +-inf or NaN)."""
+    from distillclip_amd import ops
+    B, E, row = 17, 48, 5
+    g = torch.Generator().manual_seed(17 * 48)
+    e = {k: torch.randn(B, E, generator=g) for k in ('si', 'ti', 'st', 'tt')}
+    e['si'][row, 7] = float('nan')
+    e = {k: v.cuda() for k, v in e.items()}
+    w = dict(out_l1=0.5, out_cos=1.5, out_kl=0.25, out_ce=0.75, cos_diff=0.125, hard_label=2.0, soft_label=0.375, logits_mse=1.25)
+    out, di, dt = ops.distill_loss(e['si'], e['ti'], e['st'], e['tt'], weights=w, temperature=0.5)
+    assert torch.isnan(out[0]).item(), out[0].item()
+    assert torch.isnan(di[row]).all(), di[row]
+    assert not torch.isfinite(dt).any(), int(torch.isfinite(dt).sum())
+
+
 def test_row_block_rejects_terms_that_need_every_row():
     from distillclip_amd import ops
     x = torch.randn(32, 64, device='cuda')
