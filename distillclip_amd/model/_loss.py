@@ -7,6 +7,10 @@ One `dclip_distill_loss` call computes every enabled term and d loss / d student
 Two names beyond the reference complete the CLIP-KD recipe (Yang et al., CVPR 2024) next to `soft_label`: `out_mse` (feature distillation:
 the MSE of the `last_representation`s, a tower term on `dclip_feature_mse`) and `icl` (interactive contrastive learning: student rows
 against the other modality's TEACHER rows, a cross-modal term on `dclip_interactive_loss`).
+
+`intra_kl` distils the geometry INSIDE one modality (relational KD; the uni-modal distance preservation of DIME-FM, Sun et al., ICCV 2023):
+tau^2 times the batch mean of the KL between the teacher's and the student's softmax over the same-modality in-batch similarities, a tower
+term on `dclip_relation_kl` (one call per tower over the rank's own rows, with one tower and with two).
 """
 from typing import Dict, List
 
@@ -22,6 +26,8 @@ _CROSS_FUSED = ('cos_diff', 'hard_label', 'soft_label', 'logits_mse')
 _FEATURE = ('hidden_rep_mse', 'embedding_mse', 'attention_score_mse', 'attention_probs_mse', 'out_mse')
 _CROSS_OWN = ('icl',)                             # cross-modal terms with a kernel call of their own
 _ICL_MAX_B = 4096                                 # include/dclip.h: dclip_interactive_loss
+_TOWER_OWN = ('intra_kl',)                        # tower terms with a kernel call of their own
+_REL_MAX_B = 4096                                 # include/dclip.h: dclip_relation_kl
 _KNOWN_UNSUPPORTED = ('attention_probs_kl', 'last_value_map_kl', 'vit_kd', 'fine_grain', 'smd')
 _SLOT_TOWER = {'out_l1': 1, 'out_cos': 2, 'out_kl': 3, 'out_ce': 4}
 _SLOT_CROSS = {'cos_diff': 9, 'hard_label': 10, 'soft_label': 11, 'logits_mse': 12}
@@ -122,6 +128,26 @@ class _InteractiveLossFn(torch.autograd.Function):
         return d_i * g_loss, d_t * g_loss, None, None, None, None
 
 
+class _RelationKLFn(torch.autograd.Function):
+    """weight * intra_kl and the four scalars of dclip_relation_kl (one tower); the kernel's gradient of the student embedding is kept for
+    the backward, the teacher gets none"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, s, t, temperature, weight):
+        prep = lambda x: x.detach().float().contiguous()
+        out, d_s = ops.relation_kl(prep(s), prep(t), temperature, weight)
+        ctx.save_for_backward(d_s)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, g_loss, _g_out):
+        (d_s,) = ctx.saved_tensors
+        return d_s * g_loss, None, None, None
+
+
 def _map_mse(s, t):
     """_FeatureMSEFn on one pair of head-mean maps [B, 1, N, N]: dclip_feature_mse reads 4 elements at a time, so an element count that is
     not a multiple of 4 (odd N at odd B) is zero-padded and the mean rescaled to the true count"""
@@ -166,7 +192,8 @@ class LossCalculator(nn.Module):
             if n in _KNOWN_UNSUPPORTED:
                 raise NotImplementedError(f"loss '{n}' is registered by the reference but used by no shipped config; it is "
                                           f'outside the HIP hot path (SURVEY.md §2.1)')
-            if n not in _TOWER_FUSED and n not in _CROSS_FUSED and n not in _FEATURE and n not in _CROSS_OWN:
+            if n not in _TOWER_FUSED and n not in _CROSS_FUSED and n not in _FEATURE and n not in _CROSS_OWN \
+                    and n not in _TOWER_OWN:
                 raise ValueError('Invalid Loss Type!')
 
     def get_control_output(self):
@@ -176,7 +203,8 @@ class LossCalculator(nn.Module):
                              need_attn_prob='attention_probs_mse' in self.loss_name)
 
     def _feature_terms(self, stu, tea):
-        """-> (weighted sum, {name: scaled value}) of the hidden-state / embedding MSE terms of one tower"""
+        """-> (weighted sum, {name: scaled value}) of one tower's terms outside the fused kernel: the hidden-state / embedding / map MSEs
+        and intra_kl"""
         total, res = 0, {}
         for n in self.loss_name:
             if n == 'hidden_rep_mse':
@@ -195,6 +223,13 @@ class LossCalculator(nn.Module):
             elif n == 'out_mse':
                 # feature distillation of CLIP-KD: the plain MSE of the output embeddings
                 val = _map_mse(stu.last_representation, tea.last_representation)
+            elif n == 'intra_kl':
+                # one dclip_relation_kl call over this tower's (local) rows: scale * percent goes into the kernel's gradient
+                val, out = _RelationKLFn.apply(stu.last_representation, tea.last_representation, float(self.temperature),
+                                               float(self.loss_scale[n] * self.percent[n]))
+                res[n] = out[1] * self.loss_scale[n]
+                total = total + val
+                continue
             else:
                 continue
             res[n] = val * self.loss_scale[n]
@@ -212,9 +247,15 @@ class LossCalculator(nn.Module):
         for n in self.loss_name:
             if n in _TOWER_FUSED or (two_tower and n in _CROSS_FUSED):
                 w[n] = self.loss_scale[n] * self.percent[n]
-        if 'out_kl' in w or 'soft_label' in w or (two_tower and 'icl' in self.loss_name):
+        if 'out_kl' in w or 'soft_label' in w or (two_tower and 'icl' in self.loss_name) or 'intra_kl' in self.loss_name:
             assert self.temperature, 'You should give the temperature for the kl loss'     # reference :133,:166
         return w
+
+    def _check_relation(self, rep):
+        """intra_kl: the batch limit of its kernel, decided before anything launches"""
+        if 'intra_kl' in self.loss_name and rep.shape[0] > _REL_MAX_B:
+            raise ValueError(f"loss 'intra_kl': batch {rep.shape[0]} exceeds the kernel's {_REL_MAX_B} rows "
+                             f'(include/dclip.h: dclip_relation_kl)')
 
     def _interactive(self, stu_out, tea_out):
         """-> (loss_scale * percent * icl with its autograd, loss_scale * icl) by one dclip_interactive_loss call"""
@@ -244,6 +285,7 @@ class LossCalculator(nn.Module):
         if icl and stu_out.visual_output.last_representation.shape[0] > _ICL_MAX_B:
             raise ValueError(f"loss 'icl': batch {stu_out.visual_output.last_representation.shape[0]} exceeds the kernel's "
                              f'{_ICL_MAX_B} rows (include/dclip.h: dclip_interactive_loss)')
+        self._check_relation(stu_out.visual_output.last_representation)
         loss, scal = _FusedLossFn.apply(stu_out.visual_output.last_representation, stu_out.text_output.last_representation,
                                         tea_out.visual_output.last_representation, tea_out.text_output.last_representation,
                                         self._weights(True), self.temperature, self.global_negatives)
@@ -267,6 +309,7 @@ class LossCalculator(nn.Module):
         return loss, res
 
     def cal_one_tower_loss(self, stu_out, tea_out):
+        self._check_relation(stu_out.last_representation)
         loss, scal = _FusedLossFn.apply(stu_out.last_representation, None, tea_out.last_representation, None,
                                         self._weights(False), self.temperature)
         scaled = scal * self._scale_vector(scal.device)

@@ -234,6 +234,25 @@ def interactive_loss(s_img, t_img, s_txt, t_txt, temperature, weight=1.0):
     return out, d_i, d_t
 
 
+def relation_kl(s, t, temperature, weight=1.0):
+    """Intra-modal relational KL distillation fwd+bwd of one tower (include/dclip.h: dclip_relation_kl): the KL between the teacher's and
+    the student's softmax over the same-modality in-batch similarities.  f32 [B, E] contiguous device tensors.
+    -> (out[4] = weight * intra_kl, intra_kl, mean_i KL_i, +0 ; d_s = weight * d intra_kl / d student rows)"""
+    _chk(s, t)
+    for x in (s, t):
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape != s.shape or not x.is_contiguous():
+            raise ValueError(f'relation_kl: need two contiguous f32 [B, E] tensors of one shape, got {tuple(x.shape)} {x.dtype}')
+    B, E = s.shape
+    ws_bytes = lib().dclip_relation_kl_workspace(B, E)
+    if ws_bytes == 0:
+        raise ValueError(f'relation_kl: need 1 <= B <= 4096, E % 16 == 0, 16 <= E <= 1024, got B={B} E={E}')
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
+    out = torch.empty(4, dtype=torch.float32, device=s.device)
+    d_s = torch.empty_like(s)
+    lib().dclip_relation_kl(_p(s), _p(t), B, E, float(temperature), float(weight), _p(out), _p(d_s), _p(ws), ws_bytes, _stream())
+    return out, d_s
+
+
 def attn_fused_fwd(qkv, B, N, H, hd, causal=False):
     """ctx = softmax(q k^T / sqrt(hd) (+ causal mask)) v for plain multi-head attention; qkv: [B*N, 3*H*hd] bf16."""
     _chk(qkv)

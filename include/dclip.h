@@ -729,6 +729,38 @@ size_t dclip_interactive_loss_workspace(int64_t B, int64_t E);
 int dclip_interactive_loss(const float* s_img, const float* t_img, const float* s_txt, const float* t_txt, int64_t B, int64_t E,
                            float tau, float weight, float* out, float* d_s_img, float* d_s_txt, void* workspace, size_t ws_bytes,
                            void* stream);
+/*
+ * Intra-modal relational KL distillation, forward + backward of ONE tower (the `intra_kl` term; uni-modal distance preservation as in
+ * DIME-FM, Sun et al., ICCV 2023): the KL between the teacher's and the student's softmax over the same-modality in-batch similarities.
+ *   s_i, t_i = rows of s, t ; x^ = x / |x|, no epsilon (as dclip_interactive_loss).  For j != i (the diagonal is EXCLUDED from every sum):
+ *       a_ij = s^_i . s^_j / tau                 b_ij = t^_i . t^_j / tau
+ *       lseS_i = log sum_{j != i} exp a_ij       lseT_i = log sum_{j != i} exp b_ij       (natural log, the row's true maximum)
+ *       p_ij = exp(a_ij - lseS_i)                q_ij = exp(b_ij - lseT_i)
+ *       KL_i = sum_{j != i} q_ij ((b_ij - lseT_i) - (a_ij - lseS_i))                      (from logits and lse, never log of a probability)
+ *       intra_kl = tau^2 mean_i KL_i                                                      (batch mean and tau^2; not soft_label's sum)
+ *   The teacher receives no gradient.  The student rows are anchors and columns of their symmetric Gram matrix:
+ *       M = p - q (zero diagonal) ;  D = weight (tau / B) (M + M^T) ;  G = D s^ ;  d s_i = (G_i - s^_i (s^_i . G_i)) / |s_i|
+ *   B = 1 has no column and B = 2 one (p = q = 1): out and d_s are zeros, by construction.
+ *   s, t       : DEVICE, f32 [B, E], 16-byte aligned.  Limits: 1 <= B <= 4096, E % 16 == 0, 16 <= E <= 1024, tau finite and > 0,
+ *                weight finite.  One tower per call.
+ *   out        : DEVICE, 4 f32, 16-byte aligned: weight * intra_kl, intra_kl, mean_i KL_i, +0.
+ *   d_s        : DEVICE, f32 [B, E], 16-byte aligned, OVERWRITTEN with weight * d intra_kl / d row.
+ *   workspace  : DEVICE, 256-byte aligned, ws_bytes >= dclip_relation_kl_workspace(B, E) (0 for a refused shape); contents need not
+ *                survive between calls.  The [B, B] matrices never reach HBM.
+ *   Five launches on `stream` (normalise, row statistics per column slice, their merge, gradient stripes, close).  No atomics, no
+ *   allocation, no synchronisation, no global state: the same call gives the same bits.
+ *   Zero and non-finite rows: there is no epsilon, so a zero row normalises to 0 * (1 / 0) = NaN in every element, and a row that
+ *   holds a NaN or an infinity to a row that holds a NaN: every dot product with it is NaN.  With B >= 2 such a row in EITHER matrix makes every element of d_s and out[0..2] NaN: the NaN sits
+ *   in a column of every other row's sum, so every row statistic of that matrix is NaN, and every element of D reads one.  out[3] stays
+ *   +0.  With B = 1 no statistic is read: out is zeros, and d_s is NaN in every element for such a row of s (0 * NaN in the product with
+ *   s^) and zeros for such a row of t.
+ *   Refused on the host with DCLIP_EINVAL, nothing launched, nothing written: B or E outside the limits, tau not finite or <= 0, a
+ *   non-finite weight, any null pointer, a misaligned pointer, a workspace smaller than the query.
+ *   Added without a version bump: no existing signature changed.
+ */
+size_t dclip_relation_kl_workspace(int64_t B, int64_t E);
+int dclip_relation_kl(const float* s, const float* t, int64_t B, int64_t E, float tau, float weight, float* out, float* d_s,
+                      void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Tower-level runtime: one call issues the whole launch sequence of an encoder tower on `stream`.
