@@ -8,7 +8,9 @@
  * No synchronisation inside any entry point, no allocation, no global mutable state on the compute path: the process-global state is
  * the opt-in profiling hooks (dclip_trace_*: launch trace, GEMM stamps / clock stamps; the wgrad fallback counter) and a handful of
  * tuning knobs read from DCLIP_* environment variables, latched once on first use and constant
- * afterwards.  Every function returns
+ * afterwards.  The stream half of this paragraph is tested for every entry that takes a stream: launched on `stream`
+ * and nowhere else, no host wait, HOST arrays consumed before the call returns, two calls in flight sharing nothing
+ * (tests/stream_cases.py, tests/test_stream_contract_gpu.py; a new stream-taking prototype needs a case there).  Every function returns
  * 0 on success, DCLIP_EINVAL (-1) for a bad argument, DCLIP_ELAUNCH (-2) for a HIP launch failure, and
  * dclip_last_error_string() (thread-local) explains the last failure.
  *
